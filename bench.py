@@ -7,6 +7,11 @@ over N GPUs (one process per GPU, RCCL gradient all-reduce overlapped with the b
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
         bench.py --gpus N --steps K --warmup W
 
+--dump-outputs DIR writes what the last timed step computed (loss, logits, seeded samples of the updated parameters and
+their gradients) as float32 DIR/<name>.npy; with the same arguments the inputs are the same in every run, so two builds can
+be compared output for output.  The GPU train step is not bitwise reproducible: two runs of the same build agree to about
+1e-2 relative on logits and gradients after the default 35 bf16 steps (1e-4 on parameters), so compare with a tolerance.
+
 Rank 0 prints ONE JSON line.  Besides the contract fields it carries
   roofline      -- the dominant hot-path kernel (largest total time among the four C-ABI kernels), its
                    algorithmic bytes (vivim_amd/_lib.py:algorithmic_bytes) divided by its
@@ -50,7 +55,51 @@ def parse():
     ap.add_argument("--stock-backbone-dwconv", action="store_true",
                     help="leave the SegFormer blocks stock: Mix-FFN depthwise convs on MIOpen instead of csrc/dwconv.hip, "
                          "transformers' own DropPath")
-    return ap.parse_args()
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step computed as DIR/<name>.npy (float32): "
+                         "loss, logits, and fixed seeded samples of the updated parameters and their gradients (<= 64 MB)")
+    a = ap.parse_args()
+    if a.steps < 1:
+        ap.error("--steps must be at least 1")
+    if a.warmup < 0:
+        ap.error("--warmup must not be negative")
+    return a
+
+
+DUMP_SEED = 1234                  # fixed: the same elements are sampled in every run and every build
+DUMP_MAX_ELEMS = {"logits": 8 << 20, "params_sample": 1 << 20, "grads_sample": 1 << 20}   # float32: <= 40 MB in all
+
+
+def _sample(flat, k, seed):
+    """flat (1-D) whole when it has at most k elements, else k elements at fixed seeded positions (ascending)."""
+    if flat.numel() <= k:
+        return flat
+    g = torch.Generator().manual_seed(seed)
+    idx = torch.randperm(flat.numel(), generator=g)[:k].sort().values
+    return flat[idx.to(flat.device)]
+
+
+def dump_outputs(out_dir, loss, logits, model):
+    """What the timed path hands its caller after its last step: the loss, the logits of the forward, and the model it
+    updated (parameters after the optimizer step, and the gradients that step applied), as float32 .npy files.  Arrays
+    above DUMP_MAX_ELEMS are sampled at positions that depend only on DUMP_SEED and the array's size."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    logits = logits if torch.is_tensor(logits) else logits[0]     # (logits, edge) when the model has the edge head
+    params = [p for p in model.parameters() if p.requires_grad]
+    with torch.no_grad():
+        flat_p = torch.cat([p.detach().reshape(-1).float() for p in params])
+        flat_g = torch.cat([(p.grad if p.grad is not None else torch.zeros_like(p)).detach().reshape(-1).float()
+                            for p in params])
+        arrays = {"loss": loss.detach().float().reshape(1),
+                  "logits": _sample(logits.detach().float().reshape(-1), DUMP_MAX_ELEMS["logits"], DUMP_SEED),
+                  "params_sample": _sample(flat_p, DUMP_MAX_ELEMS["params_sample"], DUMP_SEED + 1),
+                  "grads_sample": _sample(flat_g, DUMP_MAX_ELEMS["grads_sample"], DUMP_SEED + 1)}
+    if logits.numel() <= DUMP_MAX_ELEMS["logits"]:
+        arrays["logits"] = arrays["logits"].view(logits.shape)
+    for name, t in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), t.cpu().numpy().astype(np.float32))
+    print(f"bench.py: wrote {', '.join(n + '.npy' for n in arrays)} to {out_dir}", file=sys.stderr)
 
 
 def cpu_baseline(seconds_budget=12.0):
@@ -300,14 +349,22 @@ def main():
         train_step(step_model, opt, clip, onehot, a.num_classes, amp)
     barrier()
     _lib.profile_begin()                     # HIP events around the hot-path kernels only (pooled events)
+    last_out, hook = [], None
     t0 = time.perf_counter()
-    for _ in range(a.steps):
+    for i in range(a.steps):
+        if a.dump_outputs and i == a.steps - 1:            # keep the last step's forward output (a reference, no copy)
+            hook = model.register_forward_hook(lambda m, args, out: last_out.append(out))
         loss = train_step(step_model, opt, clip, onehot, a.num_classes, amp)
     barrier()
     elapsed = time.perf_counter() - t0
     records = _lib.profile_end()
     elapsed = dp.max_over_ranks(elapsed, dev)
     assert torch.isfinite(loss), "non-finite loss"
+    if hook is not None:
+        hook.remove()
+        if rank == 0:                                          # before comm_probe, whose extra steps update the model again
+            dump_outputs(a.dump_outputs, loss, last_out[-1], model)
+        del last_out
     comm = {}
     try:                                                       # every rank takes part; rank 0 reports
         comm = dp.comm_probe(step_model, lambda: train_step(step_model, opt, clip, onehot, a.num_classes, amp),

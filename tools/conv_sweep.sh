@@ -1,7 +1,7 @@
 #!/bin/bash
 # conv1d pipelined kernels: kernel durations (rocprofv3) against the wave target VIVIM_CONV_WAVES, cfg 2 and cfg 5 grouped shapes
 #   gpurun -- 'bash tools/conv_sweep.sh > gpurun_out/conv_sweep.txt'
-root=${GRAFT_REPO_ROOT:-/root/repo}
+root=$(cd "$(dirname "${BASH_SOURCE[0]}")/.." && pwd)
 out=$root/gpurun_out
 mkdir -p "$out"
 for cfg in 2 5; do

@@ -1,7 +1,7 @@
 #!/bin/bash
 # FETCH_SIZE calibration on known byte counts (tools/fetch_cal.hip):  gpurun -- 'bash tools/fetch_cal.sh'
 set -e -o pipefail
-root=${GRAFT_REPO_ROOT:-/root/repo}
+root=$(cd "$(dirname "${BASH_SOURCE[0]}")/.." && pwd)
 out=$root/gpurun_out
 mkdir -p "$out"
 cd /tmp && export TMPDIR=/tmp

@@ -3,7 +3,7 @@
 # (MI355X_MICROARCH.md, DVFS give-back; reads high on dispatches shorter than ~0.3 ms):  bash tools/kclk.sh <tag> <kbench args...>
 set -e -o pipefail
 tag=${1:?tag}; shift
-root=${GRAFT_REPO_ROOT:-/root/repo}
+root=$(cd "$(dirname "${BASH_SOURCE[0]}")/.." && pwd)
 out=$root/gpurun_out
 mkdir -p "$out"
 cd /tmp && export TMPDIR=/tmp

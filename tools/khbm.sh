@@ -4,7 +4,7 @@
 # other than 16 B per lane, MI355X_MICROARCH.md HBM section).  Kernel trace only.
 set -e -o pipefail
 tag=${1:?tag}; shift
-root=${GRAFT_REPO_ROOT:-/root/repo}
+root=$(cd "$(dirname "${BASH_SOURCE[0]}")/.." && pwd)
 out=$root/gpurun_out
 mkdir -p "$out"
 cd /tmp && export TMPDIR=/tmp

@@ -2,7 +2,7 @@
 # second SQ counter pass (LDS / memory side) over one tools/kbench.py invocation:  bash tools/kpmc2.sh <tag> <kbench args...>
 set -e -o pipefail
 tag=${1:?tag}; shift
-root=${GRAFT_REPO_ROOT:-/root/repo}
+root=$(cd "$(dirname "${BASH_SOURCE[0]}")/.." && pwd)
 out=$root/gpurun_out
 mkdir -p "$out"
 cd /tmp && export TMPDIR=/tmp

@@ -3,7 +3,7 @@
 # (counters in their own run, kernel trace only -- never combined with the hip/hsa trace domains)
 set -e -o pipefail
 tag=${1:?tag}; shift
-root=${GRAFT_REPO_ROOT:-/root/repo}
+root=$(cd "$(dirname "${BASH_SOURCE[0]}")/.." && pwd)
 out=$root/gpurun_out
 mkdir -p "$out"
 cd /tmp && export TMPDIR=/tmp

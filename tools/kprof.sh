@@ -3,7 +3,7 @@
 # (VIVIM_FWD_VARIANT / VIVIM_BWD_VARIANT are inherited by python3 directly: no env/bash hop behind rocprofv3)
 set -e -o pipefail
 tag=${1:?tag}; shift
-root=${GRAFT_REPO_ROOT:-/root/repo}
+root=$(cd "$(dirname "${BASH_SOURCE[0]}")/.." && pwd)
 out=$root/gpurun_out
 mkdir -p "$out"
 cd /tmp && export TMPDIR=/tmp

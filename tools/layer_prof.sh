@@ -2,7 +2,7 @@
 # GPU time of one MambaLayer forward + backward, kernel by kernel, per stage shape of configs[1]:  bash tools/layer_prof.sh <tag>
 set -e -o pipefail
 tag=${1:?tag}
-root=${GRAFT_REPO_ROOT:-/root/repo}
+root=$(cd "$(dirname "${BASH_SOURCE[0]}")/.." && pwd)
 out=$root/gpurun_out
 mkdir -p "$out"
 cd /tmp && export TMPDIR=/tmp

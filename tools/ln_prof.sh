@@ -2,7 +2,7 @@
 # rocprofv3 kernel durations of tools/ln_bench.py, one stage shape per run:  bash tools/ln_prof.sh <tag>
 set -e -o pipefail
 tag=${1:?tag}
-root=${GRAFT_REPO_ROOT:-/root/repo}
+root=$(cd "$(dirname "${BASH_SOURCE[0]}")/.." && pwd)
 out=$root/gpurun_out
 mkdir -p "$out"
 cd /tmp && export TMPDIR=/tmp

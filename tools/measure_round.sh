@@ -6,7 +6,7 @@
 # Stops at the first failing GPU step (set -e): no GPU step is started after one that timed out.
 set -e -o pipefail
 tag=${1:?tag}
-root=${GRAFT_REPO_ROOT:-/root/repo}
+root=$(cd "$(dirname "${BASH_SOURCE[0]}")/.." && pwd)
 out=$root/gpurun_out
 mkdir -p "$out"
 cd "$root"

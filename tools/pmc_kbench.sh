@@ -4,7 +4,7 @@
 #   gpurun --timeout 900 -- 'bash tools/pmc_kbench.sh r03_v1'      then copy gpurun_out/<tag>_kbench_pmc_traffic.json to profiles/
 set -e -o pipefail
 tag=${1:?tag}
-root=${GRAFT_REPO_ROOT:-/root/repo}
+root=$(cd "$(dirname "${BASH_SOURCE[0]}")/.." && pwd)
 out=$root/gpurun_out
 scratch=$out/pmck_$tag
 mkdir -p "$scratch"

@@ -3,7 +3,7 @@
 #   gpurun --timeout 1000 -- 'bash tools/pmc_round.sh r02_v2'
 set -e -o pipefail
 tag=${1:?tag}
-root=${GRAFT_REPO_ROOT:-/root/repo}
+root=$(cd "$(dirname "${BASH_SOURCE[0]}")/.." && pwd)
 out=$root/gpurun_out
 mkdir -p "$out"
 cd /tmp && export TMPDIR=/tmp

@@ -1,7 +1,7 @@
 #!/bin/bash
 # Round-3 evidence for the second-generation lanes=states backward: stamps, SQ counters, HBM counters, clock.
 #   gpurun --timeout 900 -- 'bash tools/profile_ls2.sh'      -> gpurun_out/r03_*; copy what is to be kept to profiles/
-root=${GRAFT_REPO_ROOT:-/root/repo}
+root=$(cd "$(dirname "${BASH_SOURCE[0]}")/.." && pwd)
 out=$root/gpurun_out
 cd "$root"
 export VIVIM_FWD_VARIANT=5 VIVIM_BWD_VARIANT=5

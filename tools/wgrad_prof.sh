@@ -1,6 +1,6 @@
 #!/bin/bash
 # kernel durations of tools/wgrad_bench.py per stage shape:  bash tools/wgrad_prof.sh   (VIVIM_WGRAD_* are inherited)
-root=${GRAFT_REPO_ROOT:-/root/repo}
+root=$(cd "$(dirname "${BASH_SOURCE[0]}")/.." && pwd)
 out=$root/gpurun_out
 mkdir -p "$out"
 cd /tmp && export TMPDIR=/tmp
