@@ -72,6 +72,42 @@ def test_checkpoint_length_is_a_function_of_shape_and_tuning():
         L.vivim_set_tuning(0, prev)
 
 
+def test_scan_plan_queries_pinned():
+    """vivim_scan_ckpt_len / vivim_scan_*_workspace_bytes for one shape per forward family and for the backward families,
+    as literals.  None of them depends on an occupancy query (those differ between a build host and the GPU)."""
+    L = _lib.lib()
+
+    def query(itype, batch, dim, groups, dstate, seqlen, variable=1):
+        s = _lib.SsmFwdParams()
+        s.batch, s.dim, s.n_groups, s.dstate, s.seqlen, s.itype = batch, dim, groups, dstate, seqlen, itype
+        s.is_variable_B = s.is_variable_C = variable
+        s.u_d_stride = s.delta_d_stride = s.out_d_stride = s.B_dstate_stride = s.C_dstate_stride = seqlen
+        s.u_batch_stride = s.delta_batch_stride = s.out_batch_stride = seqlen * dim
+        s.B_group_stride = s.C_group_stride = seqlen * dstate
+        s.B_batch_stride = s.C_batch_stride = seqlen * dstate * groups
+        return (L.vivim_scan_ckpt_len(ctypes.byref(s)), L.vivim_scan_fwd_workspace_bytes(ctypes.byref(s)),
+                L.vivim_scan_bwd_workspace_bytes(ctypes.byref(s)))
+
+    prev = (L.vivim_set_tuning(0, 0), L.vivim_set_tuning(1, 0))
+    try:
+        # lanes = channels forward (fp32 B / C copy + segment carries), lanes = tokens backward (8 segments)
+        assert query(_lib.BF16, 2, 768, 3, 16, 40960) == (256, 39813888, 1622016)
+        assert query(_lib.F16, 2, 768, 3, 64, 8192) == (256, 50727936, 6340608)
+        assert query(_lib.BF16, 2, 768, 3, 24, 5124)[:2] == (256, 0)                     # n-split forward: no workspace
+        assert query(_lib.F32, 2, 64, 1, 16, 1280, variable=0) == (256, 0, 0)           # generic kernels
+        ck, fwd_ws, _ = query(_lib.BF16, 2, 64, 1, 16, 1280)                              # lanes = states forward, 20 segments
+        assert (ck, fwd_ws) == (16, 337920)
+        # lanes = states backward: whole (batch, dim, segment) records of 2 * dstate + 1 floats; none when unsegmented
+        unit = 2 * 768 * (2 * 16 + 1) * 4
+        for seqlen in (320, 1280, 20480):
+            ck, _, bwd_ws = query(_lib.BF16, 2, 768, 3, 16, seqlen)
+            assert ck == 16 and bwd_ws % unit == 0 and bwd_ws // unit >= 2
+        assert query(_lib.BF16, 2, 768, 3, 16, 64)[2] == 0                                 # four checkpoint blocks: one segment
+    finally:
+        L.vivim_set_tuning(0, prev[0])
+        L.vivim_set_tuning(1, prev[1])
+
+
 def test_rejects_before_launch():
     """Invalid params are refused on the host (no GPU needed): null struct, bad width, bad dtype."""
     L = _lib.lib()

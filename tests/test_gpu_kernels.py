@@ -461,19 +461,31 @@ def test_scan_kernel_families_dstate64(fwd, bwd, dtype, batch, dim, L, G, cuda, 
 
 @pytest.mark.parametrize("opts", [dict(), dict(has_z=False), dict(has_D=False, has_bias=False), dict(softplus=False)])
 @pytest.mark.parametrize("dtype,batch,dim,L,G,strided", [(torch.bfloat16, 3, 128, 20480, 1, True), (torch.float32, 2, 96, 5124, 3, False),
-                                                        (torch.float16, 1, 80, 1288, 1, False)])
+                                                        (torch.float16, 1, 80, 1288, 1, False),
+                                                        (torch.bfloat16, 3, 128, 20480, 1, "C_odd_offset"),
+                                                        (torch.bfloat16, 3, 128, 20480, 1, "C_odd_stride")])
 def test_scan_second_generation_states_backward(opts, dtype, batch, dim, L, G, strided, cuda, ops, tuning):
     """scan_ls2.hip pinned (backward 5) behind the forward that writes 16-token checkpoints for every row length: long
     (L, B*L, 1)-strided rows cut into many segments at multiples of 256 tokens (lanes=tokens pre-pass + carry in front of the
     lanes=states main kernel), a row length that is not a multiple of a span or a tile, ragged channel blocks (96 = 64 + 32
-    channels, three groups; 80 = 64 + 16), and every optional input off in turn (no z: the other instantiation)."""
+    channels, three groups; 80 = 64 + 16), and every optional input off in turn (no z: the other instantiation).
+    C_odd_offset / C_odd_stride: the same long rows with a C whose rows cannot be read as vectors (a view at an odd element
+    offset; a dstate stride of L + 3): the recurrence-form pre-pass stands in for the closed-form one, which loads C with
+    vectors, and the main kernel reads B / C element-wise."""
     ss, _ = ops
     tuning(FWD_VARIANTS["channels"], BWD_VARIANTS["states2"])
     gen = torch.Generator().manual_seed(dim + L)
     # without softplus delta itself is the step size: the module initialisation has negative ones (states grow without bound
     # over 20480 tokens, in the oracle too), the reference tests' distribution (0.5 * U(0, 1), test_selective_scan.py:87) has not
     init = "module" if opts.get("softplus", True) else "test"
-    _check_scan(_rand_scan(gen, batch, dim, 16, L, G, dtype, cuda, strided=strided, init=init, **opts), ss)
+    t = _rand_scan(gen, batch, dim, 16, L, G, dtype, cuda, strided=bool(strided), init=init, **opts)
+    if strided == "C_odd_offset":
+        t["C"] = torch.empty(t["C"].numel() + 1, dtype=dtype, device=cuda)[1:].view(t["C"].shape).copy_(t["C"])
+        assert t["C"].storage_offset() == 1 and t["C"].is_contiguous()
+    elif strided == "C_odd_stride":
+        t["C"] = torch.empty(*t["C"].shape[:-1], L + 3, dtype=dtype, device=cuda)[..., :L].copy_(t["C"])
+        assert t["C"].stride(2) == L + 3
+    _check_scan(t, ss)
 
 
 @pytest.mark.parametrize("fwd", ["nsplit_k8", "channels", "states"])

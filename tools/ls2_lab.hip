@@ -8,8 +8,16 @@
 #include <vector>
 #include "../vivim_amd/csrc/scan_ls.hip"
 #include "../vivim_amd/csrc/scan_ls2.hip"
+#include "../vivim_amd/csrc/scan_plan.hip"
 
-namespace vivim { bool fast_bwd_prepass(const vivim_ssm_bwd_params&, int, int, float*, float*, float*, hipStream_t) { return false; }   // (scan_bwd.hip is not part of the lab: the recurrence pre-pass of scan_ls.hip runs)
+// (scan_fwd*.hip / scan_bwd.hip are not part of the lab: tuning 6 / 5 never plans their families, and where the plan picks the
+// closed-form pre-pass of scan_bwd.hip the lab launches none -- the timing is then the main kernel's, as are the stamps)
+namespace vivim { void launch_fwd_nsplit(const vivim_ssm_fwd_params&, const FwdPlan&, hipStream_t) {}
+                  void launch_fwd_generic(const vivim_ssm_fwd_params&, hipStream_t) {}
+                  void launch_fwd_chan(const vivim_ssm_fwd_params&, const FwdPlan&, hipStream_t) {}
+                  void launch_bwd_fast(const vivim_ssm_bwd_params&, const BwdPlan&, hipStream_t) {}
+                  void launch_bwd_generic(const vivim_ssm_bwd_params&, int, hipStream_t) {}
+                  void launch_bwd_closed_prepass(const vivim_ssm_bwd_params&, const LsSeg&, int, hipStream_t) {}
                   int tuning_fwd_variant() { return 6; }
                   int tuning_bwd_variant() { const char* e = getenv("VIVIM_BWD_VARIANT"); return e ? atoi(e) : 5; } }
 
@@ -45,8 +53,8 @@ int main(int argc, char** argv) {
     p.B_batch_stride = p.C_batch_stride = (int64_t)G * N * L; p.B_group_stride = p.C_group_stride = (int64_t)N * L;
     p.B_dstate_stride = p.C_dstate_stride = L;
     p.u = u; p.delta = dl; p.A = A; p.B = Bm; p.C = Cm; p.D = Dv; p.delta_bias = bias; p.z = z; p.out = out; p.out_z = outz; p.x = x;
-    p.workspace_bytes = (int64_t)vivim::ls_fwd_workspace_bytes(p); if (p.workspace_bytes) CK(hipMalloc(&p.workspace, p.workspace_bytes));
-    if (!vivim::try_ls_fwd(p, 0)) { printf("forward refused\n"); return 1; }
+    p.workspace_bytes = (int64_t)vivim::scan_fwd_workspace_bytes(p); if (p.workspace_bytes) CK(hipMalloc(&p.workspace, p.workspace_bytes));
+    if (!vivim::ssm_fwd_dispatch(p, 0)) { printf("forward refused\n"); return 1; }
     CK(hipDeviceSynchronize());
 
     vivim_ssm_bwd_params q = {};
@@ -57,7 +65,7 @@ int main(int argc, char** argv) {
     q.dB_batch_stride = q.dC_batch_stride = (int64_t)G * N * L; q.dB_group_stride = q.dC_group_stride = (int64_t)N * L;
     q.dB_dstate_stride = q.dC_dstate_stride = L;
     q.dout = dout; q.du = du; q.ddelta = ddl; q.dz = dz; q.dA = dA; q.dB = dB; q.dC = dC; q.dD = dD; q.ddelta_bias = dbias;
-    q.workspace_bytes = (int64_t)vivim::ls_bwd_workspace_bytes(q.f);
+    q.workspace_bytes = (int64_t)vivim::scan_bwd_workspace_bytes(q.f);
     if (q.workspace_bytes) CK(hipMalloc(&q.workspace, q.workspace_bytes));
 
     const int nstamp = 2 * vivim::kStampWaves * vivim::kStampSteps * vivim::kStampSlots;
@@ -65,11 +73,11 @@ int main(int argc, char** argv) {
     CK(hipMalloc(&dbg, nstamp * 8)); CK(hipMemset(dbg, 0, nstamp * 8));
     CK(hipMemcpyToSymbol(HIP_SYMBOL(vivim::g_stamp_buf), &dbg, sizeof(dbg)));
     hipEvent_t e0, e1; CK(hipEventCreate(&e0)); CK(hipEventCreate(&e1));
-    for (int i = 0; i < 2; ++i) if (!vivim::try_ls_bwd(q, 0)) { printf("backward refused\n"); return 1; }
+    for (int i = 0; i < 2; ++i) if (!vivim::ssm_bwd_dispatch(q, 0)) { printf("backward refused\n"); return 1; }
     CK(hipDeviceSynchronize());
     CK(hipMemset(dbg, 0, nstamp * 8));
     CK(hipEventRecord(e0));
-    for (int i = 0; i < 3; ++i) vivim::try_ls_bwd(q, 0);
+    for (int i = 0; i < 3; ++i) vivim::ssm_bwd_dispatch(q, 0);
     CK(hipEventRecord(e1)); CK(hipDeviceSynchronize());
     float ms; CK(hipEventElapsedTime(&ms, e0, e1));
     printf("BWD B=%d D=%d L=%d G=%d: %.1f us per launch (stamped build; read the SHARES)\n", B, D, L, G, ms * 1e3 / 3);

@@ -7,9 +7,8 @@
 namespace vivim {
 
 // Kernel-selection overrides (capi.hip): 0 = automatic.  Initialised from VIVIM_FWD_VARIANT / VIVIM_BWD_VARIANT,
-// changed at run time through vivim_set_tuning() (tests and tools sweep the variants in one process).
-//   forward : 1 n-split K=8, 2 n-split K=4, 3 generic, 5 lanes=channels (needs the forward workspace)
-//   backward: 3 generic
+// changed at run time through vivim_set_tuning() (tests and tools sweep the variants in one process).  Values: FwdTune /
+// BwdTune (scan_plan.cuh).
 int tuning_fwd_variant();
 int tuning_bwd_variant();
 

@@ -14,16 +14,9 @@
 // second wave scan seeded by the carry of the step to the right (kept in per-wave LDS together with that
 // step's first decay factor), dB/dC are summed over the wave's R channels in registers before they leave
 // the wave.  No inter-wave communication, no barrier.
-#include <stdlib.h>
-#include "common.cuh"
+#include "scan_plan.cuh"
 
 namespace vivim {
-
-int scan_ckpt_len(const vivim_ssm_fwd_params&);                          // scan_fwd.hip
-bool ls_shape_ok(const vivim_ssm_fwd_params&);                           // scan_ls.hip
-int ls_ckpt_len(const vivim_ssm_fwd_params&);
-bool try_ls_bwd(const vivim_ssm_bwd_params&, hipStream_t);
-size_t ls_bwd_workspace_bytes(const vivim_ssm_fwd_params&);
 
 constexpr int kBwdWaves = 4;
 
@@ -266,8 +259,6 @@ __global__ void __launch_bounds__(kBwdWaves * kWave) ssm_bwd_generic_kernel(cons
 //     rate.  Slots are double-buffered on the state parity, so one barrier per state suffices;
 //   * every per-(channel, state) scalar the step needs (checkpoint, g carry, first decay of the step to the
 //     right, A, A*log2e, running dA) sits in a per-wave LDS record read with one ds_read_b128 pair.
-constexpr int kBwWmax = 8;         // waves per workgroup: 8 or 4 (template parameter W of the fast kernel)
-constexpr int kBwR = 2;            // channels per wave
 constexpr int kRec = 8;            // floats per (state, channel) record
 
 // Segment scratch (only when the token axis is split over S > 1 workgroups): the reverse recurrence needs,
@@ -833,247 +824,91 @@ __global__ void ssm_bwd_carry_kernel(const vivim_ssm_bwd_params p, const BwdSeg 
     }
 }
 
-// Tokens per lane of the fast backward.  Most of a state iteration is scan machinery whose cost does not depend on K
-// (DESIGN.md 4.3), so 8 tokens per lane (512-token steps, 229-243 VGPRs of the 256 available at two waves per SIMD, no
-// scratch) nearly halve the instructions per state update: measured -4 ... -25 % on Vivim's bf16 shapes, -4 ... -9 % on
-// the fp32 ones -- except where the last 512-token step would be mostly empty (L = 1280: three steps, 20 % of the
-// slots idle, +6 % against five full 256-token steps).  A pure function of the shape: the workspace query and the
-// launch must agree.
-static int bwd_tokens_per_lane(int /*itype*/, int seqlen) {
-    const int64_t slots8 = (int64_t)((seqlen + 511) / 512) * 512, slots4 = (int64_t)((seqlen + 255) / 256) * 256;
-    return slots8 * 100 > slots4 * 115 ? 4 : 8;
+// The closed-form pre-pass + carry on the plan's cut of the token axis: S - 1 segments of seg_steps K-token-per-lane steps.
+// DS: 16 = the dstate-16 instantiation, 0 = any dstate.
+template <typename T, int K, int DS>
+static void launch_prepass(const vivim_ssm_bwd_params& p, const BwdSeg& sg, hipStream_t stream) {
+    const vivim_ssm_fwd_params& f = p.f;
+    const int ppg = (f.dim / f.n_groups + kBwR - 1) / kBwR;
+    const size_t per_wave = (size_t)f.dstate * kBwR * kWave * sizeof(float);            // 8 KB at N = 16, 32 KB at N = 64
+    int nw = (int)((size_t)65536 / per_wave);
+    nw = nw > kPreW ? kPreW : (nw < 1 ? 1 : nw);
+    const dim3 gpre(((ppg + nw - 1) / nw) * f.n_groups, f.batch, sg.S - 1);
+    if (f.z) hipLaunchKernelGGL((ssm_bwd_prepass_kernel<T, K, true, DS>), gpre, dim3(nw * kWave), nw * per_wave, stream, p, sg);
+    else     hipLaunchKernelGGL((ssm_bwd_prepass_kernel<T, K, false, DS>), gpre, dim3(nw * kWave), nw * per_wave, stream, p, sg);
+    const int64_t nthr = (int64_t)f.batch * f.dim * f.dstate;
+    hipLaunchKernelGGL(ssm_bwd_carry_kernel, dim3((unsigned)((nthr + 255) / 256)), dim3(256), 0, stream, p, sg);
 }
 
-// How the token axis is cut.  One 8-wave workgroup is resident per CU and all workgroups of a launch take the same
-// time, so the launch runs in rounds of `ncu` workgroups: cost(S) ~ ceil(base * S / ncu) * (ceil(nsteps / S) + fixed), with
-// base = workgroups before the split and `fixed` ~ 0.3 step for a workgroup's prologue / final reductions.  Measured
-// against the former fixed target of 1024 workgroups: per-direction stage 0 287 -> 243 us (S 40 -> 10), grouped
-// stage 2 255 -> 227 us (S 3 -> 2); grouped stage 0 unchanged (S 14 -> 7..10).  Ties go to the smaller S (less pre-pass).
-static int device_cu_count() {
-    static const int n = [] {
-        int dev = 0, v = 0;
-        if (hipGetDevice(&dev) != hipSuccess ||
-            hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || v <= 0)
-            v = 256;                                    // MI355X; also what a GPU-less build host reports
-        return v;
-    }();
-    return n;
-}
-
-// Token-axis cut for workgroups of W waves: minimise rounds-of-the-chip x (steps per segment + fixed cost).
-static void bwd_segmentation(const vivim_ssm_fwd_params& f, int W, int& S, int& seg_steps, int64_t& workgroups) {
-    const int tile = kWave * bwd_tokens_per_lane(f.itype, f.seqlen);
-    const int nsteps = (f.seqlen + tile - 1) / tile;
-    const int cpg = f.dim / f.n_groups;
-    const int ppg = (cpg + kBwR - 1) / kBwR;
-    const int64_t base = (int64_t)((ppg + W - 1) / W) * f.n_groups * f.batch;
-    // workgroups in flight per CU: two waves per SIMD at K = 8 (240-248 VGPRs), three at K = 4 with 4-wave workgroups (145)
-    const int slots = device_cu_count() * (tile == 4 * kWave && W == 4 ? 3 : kBwWmax / W);
-    int best = 1;
-    double best_cost = 1e300;
-    for (int s = 1; s <= nsteps && s <= 64; ++s) {
-        const int steps = (nsteps + s - 1) / s;
-        if ((nsteps + steps - 1) / steps != s) continue;            // not a distinct cut
-        const double rounds = (double)((base * s + slots - 1) / slots);
-        // a cut adds the pre-pass over all segments but the first (~0.4 of a main-pass step per step) and the carry kernel
-        const double cost = rounds * (steps * (1.0 + 0.4 * (s - 1) / s) + 0.3);
-        if (cost < best_cost - 1e-9) { best_cost = cost; best = s; }
-    }
-    seg_steps = (nsteps + best - 1) / best;
-    S = (nsteps + seg_steps - 1) / seg_steps;
-    workgroups = base * S;
-}
-
-// Waves per workgroup.  Eight waves share one B/C tile and one set of dB/dC atomics (half as many atomics per address as
-// two 4-wave workgroups) and win on short rows that fit the chip in one round (D 1024, L 320: 55 us with 8 waves, 73 us
-// with 4; D 640, L 1280: 96 vs 102 us).  Two independent 4-wave workgroups per CU win when a workgroup walks several
-// steps -- one runs while the other waits at its per-state barrier -- and past one round, where the last round is cut
-// finer (MI355X, cfg 2 grouped stages 0-3: 597/314/225/147 -> 583/293/198/145 us; cfg 3 stages 0-2:
-// 2241/1103/779 -> 2151/981/625 us).  vivim_set_tuning(1, 1 / 2) pins 8 / 4.
-struct BwdPlan { int W, S, seg_steps; };
-static BwdPlan bwd_plan(const vivim_ssm_fwd_params& f) {
-    BwdPlan q;
-    int64_t wgs = 0;
-    q.W = kBwWmax;
-    bwd_segmentation(f, q.W, q.S, q.seg_steps, wgs);
-    const int tv = tuning_bwd_variant();
-    if (tv == 2 || (tv != 1 && (wgs > device_cu_count() || q.seg_steps >= 4))) {
-        q.W = 4;
-        bwd_segmentation(f, q.W, q.S, q.seg_steps, wgs);
-    }
-    return q;
-}
-
-// The lanes = states family (scan_ls.hip) takes every shape whose checkpoints were written for it (scan_ckpt_len), unless
-// the tuning selector pins one of the kernels of this file (1 / 2: fast kernel with 8 / 4 waves, 3: generic; 4 pins its first-generation main kernel, 5 the second-generation one of scan_ls2.hip).
-static bool bwd_takes_ls(const vivim_ssm_fwd_params& f) {
-    const int tv = tuning_bwd_variant();
-    return ls_shape_ok(f) && scan_ckpt_len(f) == ls_ckpt_len(f) && (tv == 0 || tv == 4 || tv == 5);
-}
-
-static size_t fast_bwd_workspace_bytes(const vivim_ssm_fwd_params& f);
-size_t scan_bwd_workspace_bytes(const vivim_ssm_fwd_params& f) {
-    if (bwd_takes_ls(f)) return ls_bwd_workspace_bytes(f);
-    return fast_bwd_workspace_bytes(f);
-}
-static size_t fast_bwd_workspace_bytes(const vivim_ssm_fwd_params& f) {
-    if (!f.is_variable_B || !f.is_variable_C || f.dstate > 64) return 0;
-    const BwdPlan q = bwd_plan(f);
-    if (q.S <= 1) return 0;
-    return ((size_t)f.batch * f.dim * q.S * (2 * f.dstate + 1)) * sizeof(float);
+// The same pre-pass + carry on the lanes = states cut (scan_ls.hip, dstate 16, segments of a multiple of 256 tokens): same
+// workspace layout and the same meaning of agg / dsum / gin.
+void launch_bwd_closed_prepass(const vivim_ssm_bwd_params& p, const LsSeg& ls, int K, hipStream_t stream) {
+    const BwdSeg sg = {ls.S, ls.seg_blocks * 16 / (K * kWave), ls.agg, ls.dsum, ls.gin};
+    with_itype(p.f.itype, [&](auto t) {
+        typedef decltype(t) T;
+        if (K == 8) launch_prepass<T, 8, 16>(p, sg, stream); else launch_prepass<T, 4, 16>(p, sg, stream);
+    });
 }
 
 template <typename T, int K, int W>
-static void launch_bwd_fast(const vivim_ssm_bwd_params& p, const BwdPlan& plan, hipStream_t stream) {
+static void launch_bwd_fast_kw(const vivim_ssm_bwd_params& p, const BwdPlan& q, hipStream_t stream) {
     const vivim_ssm_fwd_params& f = p.f;
-    const int cpg = f.dim / f.n_groups;
-    const int ppg = (cpg + kBwR - 1) / kBwR;
+    const int ppg = (f.dim / f.n_groups + kBwR - 1) / kBwR;
     const int bpg = (ppg + W - 1) / W;
-    BwdSeg sg = {1, (f.seqlen + kWave * K - 1) / (kWave * K), nullptr, nullptr, nullptr};
-    const size_t need = fast_bwd_workspace_bytes(f);
-    if (need && p.workspace && (size_t)p.workspace_bytes >= need) {
-        sg.S = plan.S;
-        sg.seg_steps = plan.seg_steps;
+    BwdSeg sg = {q.S, q.seg, nullptr, nullptr, nullptr};
+    if (q.S > 1) {
         const size_t nbd = (size_t)f.batch * f.dim * sg.S;
         sg.agg = static_cast<float*>(p.workspace);
         sg.gin = sg.agg + nbd * f.dstate;
         sg.dsum = sg.gin + nbd * f.dstate;
+        if (f.dstate == 16) launch_prepass<T, K, 16>(p, sg, stream);
+        else                launch_prepass<T, K, 0>(p, sg, stream);
     }
-    const dim3 block(W * kWave);
     // LDS at W = 8: 2 slot buffers (32 KB) + records (N * 512 B) + per-lane dA partials when used (N * 4 KB): 104 KB at
     // N = 16, half of that at W = 4 -- the registers (two waves per SIMD) bound the residency either way
-    // per-lane dA partials in LDS pay off once a workgroup walks several steps (grouped stage 0, 6 steps: 724 -> 698 us);
-    // for one or two steps their zero-fill and final reduction cost more than the per-state wave reductions they
-    // replace (stage 3: 74 -> 80 us)
-    const bool da_lds = f.dstate <= 16 && sg.seg_steps >= 2;
     const size_t smem = ((size_t)2 * W * 2 * K * kWave + (size_t)W * f.dstate * kBwR * kRec +
-                         (da_lds ? (size_t)W * f.dstate * kWave * 2 : 0)) * sizeof(float);
-    if (sg.S > 1) {
-        const size_t per_wave = (size_t)f.dstate * kBwR * kWave * sizeof(float);            // 8 KB at N = 16, 32 KB at N = 64
-        int nw = (int)((size_t)65536 / per_wave);
-        nw = nw > kPreW ? kPreW : (nw < 1 ? 1 : nw);
-        dim3 gpre(((ppg + nw - 1) / nw) * f.n_groups, f.batch, sg.S - 1);
-        if (f.dstate == 16) {
-            if (f.z) hipLaunchKernelGGL((ssm_bwd_prepass_kernel<T, K, true, 16>), gpre, dim3(nw * kWave), nw * per_wave, stream, p, sg);
-            else     hipLaunchKernelGGL((ssm_bwd_prepass_kernel<T, K, false, 16>), gpre, dim3(nw * kWave), nw * per_wave, stream, p, sg);
-        } else {
-            if (f.z) hipLaunchKernelGGL((ssm_bwd_prepass_kernel<T, K, true, 0>), gpre, dim3(nw * kWave), nw * per_wave, stream, p, sg);
-            else     hipLaunchKernelGGL((ssm_bwd_prepass_kernel<T, K, false, 0>), gpre, dim3(nw * kWave), nw * per_wave, stream, p, sg);
-        }
-        const int64_t nthr = (int64_t)f.batch * f.dim * f.dstate;
-        hipLaunchKernelGGL(ssm_bwd_carry_kernel, dim3((unsigned)((nthr + 255) / 256)), dim3(256), 0, stream, p, sg);
-    }
-    dim3 grid(bpg * f.n_groups, f.batch, sg.S);
+                         (q.da_lds ? (size_t)W * f.dstate * kWave * 2 : 0)) * sizeof(float);
+    const dim3 grid(bpg * f.n_groups, f.batch, sg.S), block(W * kWave);
     auto launch = [&](auto kernel) {
-        // The four <HAS_Z, DA_LDS> instantiations share one function-pointer TYPE, so a cache inside this generic lambda would
-        // be shared between them (and between devices): the attribute is simply set on every launch that needs it -- a
-        // host-side table write, no synchronisation.
-        if (smem > 65536)
-            (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
+        allow_smem(kernel, smem);
         hipLaunchKernelGGL(kernel, grid, block, smem, stream, p, sg);
     };
-    if (f.z) { if (da_lds) launch(ssm_bwd_fast_kernel<T, K, true, W, true>); else launch(ssm_bwd_fast_kernel<T, K, true, W, false>); }
-    else     { if (da_lds) launch(ssm_bwd_fast_kernel<T, K, false, W, true>); else launch(ssm_bwd_fast_kernel<T, K, false, W, false>); }
+    if (f.z) { if (q.da_lds) launch(ssm_bwd_fast_kernel<T, K, true, W, true>); else launch(ssm_bwd_fast_kernel<T, K, true, W, false>); }
+    else     { if (q.da_lds) launch(ssm_bwd_fast_kernel<T, K, false, W, true>); else launch(ssm_bwd_fast_kernel<T, K, false, W, false>); }
 }
 
-// The lanes = tokens pre-pass + carry on somebody else's cut of the token axis: S segments of seg_tokens tokens each, a
-// multiple of 256 (scan_ls.hip uses it for the lanes = states main kernels on long rows: the closed-form pre-pass of this
-// file runs at half the time of the recurrence form there -- cfg 3 grouped stage 0: 989 against 1931 us).  Same workspace
-// layout and the same meaning of agg / dsum / gin.  The caller has checked 16-byte aligned rows of delta, dout, z and C.
-template <typename T, int K>
-static void launch_prepass_only(const vivim_ssm_bwd_params& p, const BwdSeg& sg, hipStream_t stream) {
-    const vivim_ssm_fwd_params& f = p.f;
-    const int cpg = f.dim / f.n_groups;
-    const int ppg = (cpg + kBwR - 1) / kBwR;
-    const size_t per_wave = (size_t)f.dstate * kBwR * kWave * sizeof(float);
-    int nw = (int)((size_t)65536 / per_wave);
-    nw = nw > kPreW ? kPreW : (nw < 1 ? 1 : nw);
-    dim3 gpre(((ppg + nw - 1) / nw) * f.n_groups, f.batch, sg.S - 1);
-    if (f.z) hipLaunchKernelGGL((ssm_bwd_prepass_kernel<T, K, true, 16>), gpre, dim3(nw * kWave), nw * per_wave, stream, p, sg);
-    else     hipLaunchKernelGGL((ssm_bwd_prepass_kernel<T, K, false, 16>), gpre, dim3(nw * kWave), nw * per_wave, stream, p, sg);
-    const int64_t nthr = (int64_t)f.batch * f.dim * f.dstate;
-    hipLaunchKernelGGL(ssm_bwd_carry_kernel, dim3((unsigned)((nthr + 255) / 256)), dim3(256), 0, stream, p, sg);
-}
-bool fast_bwd_prepass(const vivim_ssm_bwd_params& p, int S, int seg_tokens, float* agg, float* gin, float* dsum, hipStream_t stream) {
-    const vivim_ssm_fwd_params& f = p.f;
-    if (S <= 1 || f.dstate != 16 || seg_tokens % 256 != 0) return false;
-    const bool k8 = seg_tokens % 512 == 0 && f.seqlen % 8 == 0;
-    if (!k8 && f.seqlen % 4 != 0) return false;
-    const BwdSeg sg = {S, seg_tokens / (k8 ? 512 : 256), agg, dsum, gin};
-    switch (f.itype) {
-        case VIVIM_F32: if (k8) launch_prepass_only<float, 8>(p, sg, stream); else launch_prepass_only<float, 4>(p, sg, stream); break;
-        case VIVIM_F16: if (k8) launch_prepass_only<f16_t, 8>(p, sg, stream); else launch_prepass_only<f16_t, 4>(p, sg, stream); break;
-        case VIVIM_BF16: if (k8) launch_prepass_only<bf16_t, 8>(p, sg, stream); else launch_prepass_only<bf16_t, 4>(p, sg, stream); break;
-        default: return false;
-    }
-    return true;
+// Two waves per SIMD (__launch_bounds__(W * 64, 2)): registers uncapped (144-152 VGPRs at K = 4, 229-248 at K = 8; one
+// 8-wave or two 4-wave workgroups per CU, 256 VGPRs available).  A 128-VGPR build of the K = 4 kernel (four waves per SIMD, two
+// workgroups per CU) measured ~12% faster but needs 28-48 bytes of scratch per lane, and hipcc (ROCm 7.2) may
+// place such a VGPR spill at the top of the join block of a divergent loop, BEFORE the s_or_b64 that
+// restores EXEC: the store then runs with EXEC = 0, nothing is saved, and the reload returns garbage (seen as
+// wrong gradients and a GPU memory fault in fp32 once an unrelated edit changed the allocation).  No kernel
+// of this library may use scratch: `make check-scratch` (part of the default build) enforces it.
+void launch_bwd_fast(const vivim_ssm_bwd_params& p, const BwdPlan& q, hipStream_t stream) {
+    with_itype(p.f.itype, [&](auto t) {
+        typedef decltype(t) T;
+        if (q.K == 8) { if (q.W == 4) launch_bwd_fast_kw<T, 8, 4>(p, q, stream); else launch_bwd_fast_kw<T, 8, kBwWmax>(p, q, stream); }
+        else          { if (q.W == 4) launch_bwd_fast_kw<T, 4, 4>(p, q, stream); else launch_bwd_fast_kw<T, 4, kBwWmax>(p, q, stream); }
+    });
 }
 
-template <typename T, int K>
-static bool try_bwd_fast_k(const vivim_ssm_bwd_params& p, hipStream_t stream) {
+void launch_bwd_generic(const vivim_ssm_bwd_params& p, int ck, hipStream_t stream) {
+    constexpr int K = 4, R = 2;
     const vivim_ssm_fwd_params& f = p.f;
-    if (!f.is_variable_B || !f.is_variable_C || f.dstate > 64 || f.x == nullptr) return false;
-    if (tuning_bwd_variant() == 3) return false;
-    if (scan_ckpt_len(f) != kChunk) return false;          // this family reads one checkpoint row per kChunk tokens
-    // unconditional K-element vectors: rows aligned to the vector size, seqlen a whole number of lanes
-    const int64_t vb = K * (int64_t)sizeof(T) >= 16 ? 16 : K * (int64_t)sizeof(T);
-    const int64_t epv = vb / (int64_t)sizeof(T);
-    auto al = [&](const void* q) { return (reinterpret_cast<uintptr_t>(q) & (vb - 1)) == 0; };
-    auto st = [&](int64_t e) { return e % epv == 0; };
-    if (f.seqlen % K != 0 || !al(f.u) || !al(f.delta) || !al(f.B) || !al(f.C) || !al(p.dout) || !al(p.du) || !al(p.ddelta) ||
-        !st(f.u_batch_stride) || !st(f.u_d_stride) || !st(f.delta_batch_stride) || !st(f.delta_d_stride) ||
-        !st(p.dout_batch_stride) || !st(p.dout_d_stride) || !st(p.du_batch_stride) || !st(p.du_d_stride) ||
-        !st(p.ddelta_batch_stride) || !st(p.ddelta_d_stride) || !st(f.B_batch_stride) || !st(f.B_group_stride) ||
-        !st(f.B_dstate_stride) || !st(f.C_batch_stride) || !st(f.C_group_stride) || !st(f.C_dstate_stride))
-        return false;
-    if (f.z && (!al(f.z) || !al(f.out) || !al(p.dz) || !st(f.z_batch_stride) || !st(f.z_d_stride) ||
-                !st(f.out_batch_stride) || !st(f.out_d_stride) || !st(p.dz_batch_stride) || !st(p.dz_d_stride) ||
-                (f.out_z && (!al(f.out_z) || !st(f.out_z_batch_stride) || !st(f.out_z_d_stride)))))
-        return false;
-    // Two waves per SIMD (__launch_bounds__(W * 64, 2)): registers uncapped (144-152 VGPRs at K = 4, 229-248 at K = 8; one
-    // 8-wave or two 4-wave workgroups per CU, 256 VGPRs available).  A 128-VGPR build of the K = 4 kernel (four waves per SIMD, two
-    // workgroups per CU) measured ~12% faster but needs 28-48 bytes of scratch per lane, and hipcc (ROCm 7.2) may
-    // place such a VGPR spill at the top of the join block of a divergent loop, BEFORE the s_or_b64 that
-    // restores EXEC: the store then runs with EXEC = 0, nothing is saved, and the reload returns garbage (seen as
-    // wrong gradients and a GPU memory fault in fp32 once an unrelated edit changed the allocation).  No kernel
-    // of this library may use scratch: `make check-scratch` (part of the default build) enforces it.
-    const BwdPlan plan = bwd_plan(f);
-    if (plan.W == 4) launch_bwd_fast<T, K, 4>(p, plan, stream);
-    else             launch_bwd_fast<T, K, kBwWmax>(p, plan, stream);
-    return true;
-}
-
-template <typename T>
-static bool try_bwd_fast(const vivim_ssm_bwd_params& p, hipStream_t stream) {
-    if (bwd_tokens_per_lane(p.f.itype, p.f.seqlen) == 8) return try_bwd_fast_k<T, 8>(p, stream);
-    return try_bwd_fast_k<T, 4>(p, stream);
-}
-
-template <typename T, int K, int R>
-static void launch_bwd(const vivim_ssm_bwd_params& p, hipStream_t stream) {
-    const vivim_ssm_fwd_params& f = p.f;
-    const int cpg = f.dim / f.n_groups;
-    const int sets = ((cpg + R - 1) / R) * f.n_groups;
-    dim3 grid((sets + kBwdWaves - 1) / kBwdWaves, f.batch);
+    const int sets = ((f.dim / f.n_groups + R - 1) / R) * f.n_groups;
+    const dim3 grid((sets + kBwdWaves - 1) / kBwdWaves, f.batch), block(kBwdWaves * kWave);
     const size_t smem = (size_t)kBwdWaves * 3 * R * f.dstate * sizeof(float);
     const bool var = f.is_variable_B;
-    if (f.z) {
-        if (var) hipLaunchKernelGGL((ssm_bwd_generic_kernel<T, K, R, true, true>), grid, dim3(kBwdWaves * kWave), smem, stream, p, scan_ckpt_len(f));
-        else     hipLaunchKernelGGL((ssm_bwd_generic_kernel<T, K, R, true, false>), grid, dim3(kBwdWaves * kWave), smem, stream, p, scan_ckpt_len(f));
-    } else {
-        if (var) hipLaunchKernelGGL((ssm_bwd_generic_kernel<T, K, R, false, true>), grid, dim3(kBwdWaves * kWave), smem, stream, p, scan_ckpt_len(f));
-        else     hipLaunchKernelGGL((ssm_bwd_generic_kernel<T, K, R, false, false>), grid, dim3(kBwdWaves * kWave), smem, stream, p, scan_ckpt_len(f));
-    }
-}
-
-bool ssm_bwd_dispatch(const vivim_ssm_bwd_params& p, hipStream_t s) {
-    if (bwd_takes_ls(p.f) && try_ls_bwd(p, s)) return true;
-    switch (p.f.itype) {
-        case VIVIM_F32: if (!try_bwd_fast<float>(p, s)) launch_bwd<float, 4, 2>(p, s); return true;
-        case VIVIM_F16: if (!try_bwd_fast<f16_t>(p, s)) launch_bwd<f16_t, 4, 2>(p, s); return true;
-        case VIVIM_BF16: if (!try_bwd_fast<bf16_t>(p, s)) launch_bwd<bf16_t, 4, 2>(p, s); return true;
-    }
-    return false;
+    with_itype(f.itype, [&](auto t) {
+        typedef decltype(t) T;
+        if (f.z) {
+            if (var) hipLaunchKernelGGL((ssm_bwd_generic_kernel<T, K, R, true, true>), grid, block, smem, stream, p, ck);
+            else     hipLaunchKernelGGL((ssm_bwd_generic_kernel<T, K, R, true, false>), grid, block, smem, stream, p, ck);
+        } else {
+            if (var) hipLaunchKernelGGL((ssm_bwd_generic_kernel<T, K, R, false, true>), grid, block, smem, stream, p, ck);
+            else     hipLaunchKernelGGL((ssm_bwd_generic_kernel<T, K, R, false, false>), grid, block, smem, stream, p, ck);
+        }
+    });
 }
 
 }  // namespace vivim

@@ -23,8 +23,7 @@
 //
 // ssm_fwd_generic_kernel -- any dstate, constant B/C: a wave owns R channels and ALL states (carry in a
 //   per-wave LDS row, shuffle-based scan); slower, used only off Vivim's path.
-#include <stdlib.h>
-#include "common.cuh"
+#include "scan_plan.cuh"
 
 namespace vivim {
 
@@ -151,7 +150,6 @@ __global__ void __launch_bounds__(kScanWaves * kWave) ssm_fwd_generic_kernel(con
 
 
 // ------------------------------------------------------------------------------------------------
-constexpr int kNsR = 2;            // channels per workgroup
 constexpr int kLdsRow = 65;        // [slot][k][lane] tiles, rows padded to 65 floats: conflict-free both ways
 
 template <typename T, int K, int NS, bool HAS_Z, int MINW>
@@ -376,113 +374,40 @@ __global__ void __launch_bounds__(NS * kWave, MINW) ssm_fwd_nsplit_kernel(const 
     }
 }
 
-template <typename T, int K, int NS, int MINW>
-static void launch_fwd_nsplit(const vivim_ssm_fwd_params& p, hipStream_t stream) {
+// 8 waves per workgroup, dstate / 8 states per wave, K tokens per lane (the plan: scan_plan.hip).
+void launch_fwd_nsplit(const vivim_ssm_fwd_params& p, const FwdPlan& q, hipStream_t stream) {
     const int cpg = p.dim / p.n_groups;
-    dim3 grid(((cpg + kNsR - 1) / kNsR) * p.n_groups, p.batch);
-    if (p.z) hipLaunchKernelGGL((ssm_fwd_nsplit_kernel<T, K, NS, true, MINW>), grid, dim3(NS * kWave), 0, stream, p);
-    else     hipLaunchKernelGGL((ssm_fwd_nsplit_kernel<T, K, NS, false, MINW>), grid, dim3(NS * kWave), 0, stream, p);
+    const dim3 grid(((cpg + kNsR - 1) / kNsR) * p.n_groups, p.batch), block(8 * kWave);
+    with_itype(p.itype, [&](auto t) {
+        typedef decltype(t) T;
+        if (q.K == 4) {
+            if (p.z) hipLaunchKernelGGL((ssm_fwd_nsplit_kernel<T, 4, 8, true, 2>), grid, block, 0, stream, p);
+            else     hipLaunchKernelGGL((ssm_fwd_nsplit_kernel<T, 4, 8, false, 2>), grid, block, 0, stream, p);
+        } else {
+            if (p.z) hipLaunchKernelGGL((ssm_fwd_nsplit_kernel<T, 8, 8, true, 2>), grid, block, 0, stream, p);
+            else     hipLaunchKernelGGL((ssm_fwd_nsplit_kernel<T, 8, 8, false, 2>), grid, block, 0, stream, p);
+        }
+    });
 }
 
-// 8 waves per workgroup, dstate / 8 states per wave.  VIVIM_FWD_VARIANT (tuning only) picks the tiling.
-template <typename T>
-static bool try_fwd_nsplit(const vivim_ssm_fwd_params& p, hipStream_t stream) {
-    if (!p.is_variable_B || !p.is_variable_C || p.dstate % 8 != 0) return false;
-    // the fast kernel uses unconditional 16-byte vectors: every row must be 16-byte aligned and the
-    // sequence a whole number of 8-token lanes; anything else takes the generic kernel.
-    const int64_t epv = 16 / (int64_t)sizeof(T);
-    auto al = [&](const void* q) { return (reinterpret_cast<uintptr_t>(q) & 15) == 0; };
-    auto st = [&](int64_t e) { return e % epv == 0; };
-    if (p.seqlen % 8 != 0 || !al(p.u) || !al(p.delta) || !al(p.B) || !al(p.C) || !al(p.out) ||
-        !st(p.u_batch_stride) || !st(p.u_d_stride) || !st(p.delta_batch_stride) || !st(p.delta_d_stride) ||
-        !st(p.out_batch_stride) || !st(p.out_d_stride) || !st(p.B_batch_stride) || !st(p.B_group_stride) ||
-        !st(p.B_dstate_stride) || !st(p.C_batch_stride) || !st(p.C_group_stride) || !st(p.C_dstate_stride))
-        return false;
-    if (p.z && (!al(p.z) || !al(p.out_z) || !st(p.z_batch_stride) || !st(p.z_d_stride) ||
-                !st(p.out_z_batch_stride) || !st(p.out_z_d_stride)))
-        return false;
-    const int forced = tuning_fwd_variant();
-    // 512-token steps (K=8) halve the per-step fixed cost; 256-token steps (K=4) need 100 instead of 160 VGPRs,
-    // so several workgroups share a CU -- better once there are enough workgroups to fill the chip twice AND the
-    // rows are short (few steps per row: finer steps waste less of the last one).
-    const int64_t nwg = (int64_t)((p.dim / p.n_groups + kNsR - 1) / kNsR) * p.n_groups * p.batch;
-    // Measured at the grouped v3 shapes (dim = 3 * d_inner, tools/kbench.py --groups 3): K=8 wins for long rows (L 20480:
-    // 365 vs 503 us, L 5120: 160 vs 188 us), K=4 for short ones (L 1280: 112 vs 130 us, L 320: 68 vs 87 us).
-    int variant = (forced && forced < 5) ? forced : ((nwg >= 512 && p.seqlen < 4096) ? 2 : 1);
-    switch (variant) {
-        case 2:  launch_fwd_nsplit<T, 4, 8, 2>(p, stream); break;     // K=4
-        case 3:  return false;                                         // generic kernel (tuning only)
-        default: launch_fwd_nsplit<T, 8, 8, 2>(p, stream); break;     // K=8
-    }
-    return true;
-}
-
-template <typename T, int K, int R>
-static void launch_fwd(const vivim_ssm_fwd_params& p, hipStream_t stream) {
+static_assert(kWave * 4 == kChunk, "generic kernel step must equal the checkpoint chunk");
+void launch_fwd_generic(const vivim_ssm_fwd_params& p, hipStream_t stream) {
+    constexpr int K = 4, R = 2;
     const int cpg = p.dim / p.n_groups;
     const int sets = ((cpg + R - 1) / R) * p.n_groups;
-    dim3 grid((sets + kScanWaves - 1) / kScanWaves, p.batch);
+    const dim3 grid((sets + kScanWaves - 1) / kScanWaves, p.batch), block(kScanWaves * kWave);
     const size_t smem = (size_t)kScanWaves * R * p.dstate * sizeof(float);
     const bool var = p.is_variable_B;   // capi enforces is_variable_B == is_variable_C
-    if (p.z) {
-        if (var) hipLaunchKernelGGL((ssm_fwd_generic_kernel<T, K, R, true, true>), grid, dim3(kScanWaves * kWave), smem, stream, p);
-        else     hipLaunchKernelGGL((ssm_fwd_generic_kernel<T, K, R, true, false>), grid, dim3(kScanWaves * kWave), smem, stream, p);
-    } else {
-        if (var) hipLaunchKernelGGL((ssm_fwd_generic_kernel<T, K, R, false, true>), grid, dim3(kScanWaves * kWave), smem, stream, p);
-        else     hipLaunchKernelGGL((ssm_fwd_generic_kernel<T, K, R, false, false>), grid, dim3(kScanWaves * kWave), smem, stream, p);
-    }
-}
-
-// Tokens per checkpoint row of x.  The lanes = states backward (scan_ls.hip) rebuilds the forward states of a 16-token tile
-// from a checkpoint, so every shape it takes gets one row per 16 * (dstate / 16) tokens, written by the lanes = channels
-// and lanes = states forward kernels; the n-split / generic kernels write one row per kChunk tokens (two per 512-token
-// n-split step) and are only reached for other shapes or when the tuning selector pins them.  A pure function of the
-// shape and of the forward tuning value: forward and backward calls must see the same one.
-bool ls_shape_ok(const vivim_ssm_fwd_params&);                           // scan_ls.hip
-int ls_ckpt_len(const vivim_ssm_fwd_params&);
-bool try_ls_fwd(const vivim_ssm_fwd_params&, hipStream_t);
-size_t ls_fwd_workspace_bytes(const vivim_ssm_fwd_params&);
-bool try_fwd_chan(const vivim_ssm_fwd_params& p, hipStream_t stream);   // scan_fwd_chan.hip
-size_t fwd_chan_workspace_bytes(const vivim_ssm_fwd_params&);
-
-// Which checkpoint rows a shape gets -- and with them which backward family (the forward families that can write them
-// follow).  Measured on MI355X (tools/kb_round2.sh, profiles/r02_kbench_families.log), lanes = states against the round-1
-// families at dstate 16: the backward wins on short rows (cfg 2 grouped stages 1-3: 273 / 172 / 84 us against 288 / 185 /
-// 149) and loses a few per cent on long ones (L 20480: 592 against 564 us; L 81920: 2214 against 2111), where the
-// lanes = tokens kernel amortises its scans over 512-token steps; at dstate 32 / 64 its extra forward sweep per checkpoint
-// block costs more than it gains (cfg 5: 1018 against 820 us).  Forward tuning 5 / 6 pin the short rows for any such shape.
-static bool ls_plan(const vivim_ssm_fwd_params& f) {
-    if (!ls_shape_ok(f)) return false;
-    const int t = tuning_fwd_variant();
-    if (t == 5 || t == 6) return true;
-    if (t != 0) return false;
-    // Round 3: with the second-generation lanes = states backward (scan_ls2.hip) and the closed-form pre-pass the two backward
-    // families take the same time on long 16-bit rows (cfg 2 grouped stage 0: 547-561 against 555-588 us) while the lanes =
-    // states one moves half the bytes (0.58 against 1.08 GB per launch); the forward pays 20 us there for the denser
-    // checkpoints (262 against 242).  fp32 rows keep the old limit: the denser checkpoints cost the forward 15 % (cfg 3
-    // grouped stage 0: 2974 against 2586 us) for 4 % of the backward.
-    return f.dstate == 16 && f.seqlen <= (f.itype == VIVIM_F32 ? 8192 : 32768);
-}
-int scan_ckpt_len(const vivim_ssm_fwd_params& f) { return ls_plan(f) ? ls_ckpt_len(f) : kChunk; }
-int scan_chunk_len(int) { return kChunk; }
-static_assert(kWave * 4 == kChunk, "generic kernel step must equal the checkpoint chunk");
-
-size_t scan_fwd_workspace_bytes(const vivim_ssm_fwd_params& f) {
-    // either of two families may run (the lanes = channels one also wants aligned rows, known only at launch): the larger
-    const size_t a = fwd_chan_workspace_bytes(f), b = ls_plan(f) ? ls_fwd_workspace_bytes(f) : 0;
-    return a > b ? a : b;
-}
-
-bool ssm_fwd_dispatch(const vivim_ssm_fwd_params& p, hipStream_t s) {
-    const int tune = tuning_fwd_variant();
-    if (tune != 6 && try_fwd_chan(p, s)) return true;      // lanes = channels: long, wide problems (or tuning 5); either row length
-    if (ls_plan(p)) return try_ls_fwd(p, s);               // lanes = states (short checkpoint rows)
-    switch (p.itype) {
-        case VIVIM_F32: if (!try_fwd_nsplit<float>(p, s)) launch_fwd<float, 4, 2>(p, s); return true;
-        case VIVIM_F16: if (!try_fwd_nsplit<f16_t>(p, s)) launch_fwd<f16_t, 4, 2>(p, s); return true;
-        case VIVIM_BF16: if (!try_fwd_nsplit<bf16_t>(p, s)) launch_fwd<bf16_t, 4, 2>(p, s); return true;
-    }
-    return false;
+    with_itype(p.itype, [&](auto t) {
+        typedef decltype(t) T;
+        if (p.z) {
+            if (var) hipLaunchKernelGGL((ssm_fwd_generic_kernel<T, K, R, true, true>), grid, block, smem, stream, p);
+            else     hipLaunchKernelGGL((ssm_fwd_generic_kernel<T, K, R, true, false>), grid, block, smem, stream, p);
+        } else {
+            if (var) hipLaunchKernelGGL((ssm_fwd_generic_kernel<T, K, R, false, true>), grid, block, smem, stream, p);
+            else     hipLaunchKernelGGL((ssm_fwd_generic_kernel<T, K, R, false, false>), grid, block, smem, stream, p);
+        }
+    });
 }
 
 }  // namespace vivim

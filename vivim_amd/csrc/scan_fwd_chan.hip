@@ -20,8 +20,7 @@
 //     inflow plus sum(delta); a carry kernel chains them (h_in[s+1] = exp2(A*log2e*sum_s) * h_in[s] + H_s); PASS 2
 //     recomputes the recurrence from the true inflow and produces out / out_z and the checkpoints x.  The state
 //     is re-derived instead of stored: 2 exp per state update instead of a 16-float-per-token round trip.
-#include <stdlib.h>
-#include "common.cuh"
+#include "scan_plan.cuh"
 
 namespace vivim {
 
@@ -32,19 +31,6 @@ namespace vivim {
 #endif
 constexpr int kChAbl = CH_ABL;
 constexpr int kChN = 16;           // states (compile time: they live in registers)
-constexpr int kChWaves = 2;        // independent waves per workgroup
-// Tokens per tile: a tile row is ONE 128-byte line for every I/O type (32 fp32 / 64 16-bit tokens).  With 32-byte pieces (16
-// tokens of bf16, the first version) a line of a row was fetched for four separate tiles, microseconds apart, with 2048
-// waves x 64 rows x 3 streams of such lines in flight -- far more than the L2s hold: rocprofv3 counted 1.17 GB of HBM
-// traffic per launch against 0.25 GB algorithmic at cfg 2's grouped stage 0 (4.1 TB/s in 283 us) and 4.6 GB against 1.76 GB
-// at cfg 3's stage 0 (4.8 TB/s in 962 us): the launches were bound by their own over-fetch
-// (profiles/r02_hbm_counters_per_kernel.txt).  Whole lines need 18 KB of LDS per wave for TWO resident streams, which is
-// what 8 waves per CU can have: z no longer goes through LDS -- the gate out * silu(z) is applied in the store phase, where
-// the lanes lie along tokens again and z is read with the same coalesced vectors the outputs are written with; y waits for it
-// in LDS as fp32, in the bytes of the u / delta tokens it was computed from.
-template <typename T> struct ChTile { static constexpr int TT = 128 / (int)sizeof(T); };
-
-int scan_ckpt_len(const vivim_ssm_fwd_params&);                          // scan_fwd.hip
 
 struct FwdSeg {
     int S, seg_tiles;              // segments, TT-token tiles per segment
@@ -511,123 +497,37 @@ __global__ void __launch_bounds__(kWave) ssm_fwd_carry64_kernel(const vivim_ssm_
     }
 }
 
-static void fwd_chan_segmentation(const vivim_ssm_fwd_params& f, int tt, int& S, int& seg_tiles) {
-    const int ntiles = (f.seqlen + tt - 1) / tt;
-    const int cpg = f.dim / f.n_groups;
-    const int64_t waves = (int64_t)((cpg + kWave - 1) / kWave) * f.n_groups * f.batch;
-    // 2048 waves: swept 512 ... 8192 on the grouped cfg-2 shapes (309/144/106/64 us at 2048; 377/198/130/68 at 1024;
-    // 320/167/125/70 at 4096); again with the packed token update: 293/146/101/69 at 1536, 283/141/104/70 at 2048,
-    // 300/164/115/70 at 3072, 304/165/124/70 at 4096
-    static const int target = getenv("VIVIM_CHAN_WAVES") ? atoi(getenv("VIVIM_CHAN_WAVES")) : 2048;   // (sweeps)
-    int64_t want = (target + waves - 1) / waves;
-    if (want > ntiles) want = ntiles;
-    if (want > 512) want = 512;       // the carry kernel keeps a whole chain in LDS: 512 * 17 * 4 = 34 KB
-    if (want < 1) want = 1;
-    seg_tiles = (int)((ntiles + want - 1) / want);
-    S = (ntiles + seg_tiles - 1) / seg_tiles;
-}
-
-// shape_only: pointers are not inspected (the workspace query may come before they are final)
-static bool fwd_chan_eligible(const vivim_ssm_fwd_params& p, bool shape_only = false) {
-    if (!p.is_variable_B || !p.is_variable_C || (p.dstate != 16 && p.dstate != 64) || p.seqlen % 8 != 0) return false;
-    if (p.dim % p.n_groups != 0 || (p.dim / p.n_groups) % kWave != 0) return false;   // whole 64-channel blocks per group
-    // Automatic choice, from tools/kbench.py on MI355X (us, this family vs n-split; cols = batch * dim / 64 waves' worth of
-    // channels, work = cols * seqlen wave-tokens):
-    //   grouped v3 stages 0-3 (cols 18/36/90/144, work 368k/184k/115k/46k): 309/140/104/64 vs 369/159/112/68
-    //   per-direction stages 0-3 (cols 6/12/30/48, work 123k/61k/38k/15k):  135/84/60/37  vs 131/65/39/29
-    //   cfg 3 stage 0 fp32 (cols 16, work 1.3M): 997 vs 1189;  grouped (cols 48, 3.9M): 2883 vs 3453
-    // -> enough total work AND enough independent channel blocks; otherwise the two passes + carry are latency-bound
-    // and n-split wins.  Tuning 5 forces this family, any other non-zero value excludes it.
-    const int tune = tuning_fwd_variant();
-    if (tune != 5) {
-        if (tune != 0) return false;
-        if (p.dstate == 64 && p.itype == VIVIM_F32) return false;   // 255 + 4 registers: one wave per SIMD (n-split is faster)
-        const int64_t cols = (int64_t)p.batch * (p.dim / kWave);
-        // short checkpoint rows (scan_ckpt_len): the alternative is the lanes = states forward, which wins below ~150 k
-        // wave-tokens (cfg 2 grouped stages 1-3, 184 k / 115 k / 46 k: 150 / 98 / 51 us against 137 / 100 / 59 with 64-byte
-        // tile rows; cfg 3 stage 2, 410 k: 361 against 302)
-        const int64_t least = scan_ckpt_len(p) < kChunk ? 150000 : 110000;
-        if (cols < 8 || cols * p.seqlen < least) return false;
+// The B / C repack, then (segmented) PASS 1 + carry, then PASS 2, on the plan's cut of the token axis (scan_plan.hip).
+void launch_fwd_chan(const vivim_ssm_fwd_params& p, const FwdPlan& q, hipStream_t stream) {
+    FwdSeg sg = {q.S, q.seg, nullptr, nullptr, static_cast<const float*>(p.workspace), q.Lpad, q.ck, q.xcd};
+    if (q.S > 1) {
+        sg.H = static_cast<float*>(p.workspace) + q.bc_floats;
+        sg.dsum = sg.H + (size_t)p.batch * p.dim * q.S * p.dstate;
     }
-    const int64_t epv = p.itype == VIVIM_F32 ? 4 : 8;
-    auto al = [&](const void* q) { return shape_only || (reinterpret_cast<uintptr_t>(q) & 15) == 0; };
-    auto st = [&](int64_t e) { return e % epv == 0; };
-    if (!al(p.u) || !al(p.delta) || !al(p.out) ||
-        !st(p.u_batch_stride) || !st(p.u_d_stride) || !st(p.delta_batch_stride) || !st(p.delta_d_stride) ||
-        !st(p.out_batch_stride) || !st(p.out_d_stride))
-        return false;
-    if (p.z && (!al(p.z) || !al(p.out_z) || !st(p.z_batch_stride) || !st(p.z_d_stride) ||
-                !st(p.out_z_batch_stride) || !st(p.out_z_d_stride)))
-        return false;
-    return true;
-}
-
-static size_t fwd_chan_layout(const vivim_ssm_fwd_params& f, int tt, int& S, int& seg_tiles, int& Lpad,
-                              size_t& bc_floats) {
-    fwd_chan_segmentation(f, tt, S, seg_tiles);
-    Lpad = (f.seqlen + tt - 1) / tt * tt;
-    bc_floats = (size_t)f.batch * f.n_groups * (Lpad + 1) * 32 * (f.dstate / 16);
-    const size_t h_floats = S > 1 ? (size_t)f.batch * f.dim * S * (f.dstate + 1) : 0;
-    return (bc_floats + h_floats) * sizeof(float);
-}
-
-size_t fwd_chan_workspace_bytes(const vivim_ssm_fwd_params& f) {
-    if (!fwd_chan_eligible(f, true)) return 0;
-    int S, seg_tiles, Lpad;
-    size_t bc;
-    return fwd_chan_layout(f, f.itype == VIVIM_F32 ? ChTile<float>::TT : ChTile<bf16_t>::TT, S, seg_tiles, Lpad, bc);
-}
-
-template <typename T>
-static bool launch_fwd_chan(const vivim_ssm_fwd_params& p, hipStream_t stream) {
-    constexpr int TT = ChTile<T>::TT;
-    int S, seg_tiles, Lpad;
-    size_t bc_floats;
-    const size_t need = fwd_chan_layout(p, TT, S, seg_tiles, Lpad, bc_floats);
-    if (!p.workspace || (size_t)p.workspace_bytes < need || (reinterpret_cast<uintptr_t>(p.workspace) & 63)) return false;
-    // Measured, VIVIM_CHAN_XCD=0 / 1 (profiles/r02_chan_xcd_ab.log): the re-numbering gains 2 - 5 % on the bf16 grouped shapes
-    // and where two workgroups share a group's B / C rows (cfg 3 stage 1), and loses 2 - 10 % on fp32 problems with one
-    // workgroup per group (cfg 3 stage 0: 831 -> 845 us; grouped 2563 -> 2807 us).
-    static const int xcd_env = getenv("VIVIM_CHAN_XCD") ? atoi(getenv("VIVIM_CHAN_XCD")) : -1;
-    const int wg_per_group = ((p.dim / p.n_groups) / kWave + kChWaves - 1) / kChWaves;
-    const int xcd = xcd_env >= 0 ? xcd_env : ((wg_per_group >= 2 || p.itype != VIVIM_F32) ? 1 : 0);
-    FwdSeg sg = {S, seg_tiles, nullptr, nullptr, static_cast<const float*>(p.workspace), Lpad, scan_ckpt_len(p), xcd};
-    if (S > 1) {
-        sg.H = static_cast<float*>(p.workspace) + bc_floats;
-        sg.dsum = sg.H + (size_t)p.batch * p.dim * S * p.dstate;
-    }
-    hipLaunchKernelGGL((ssm_fwd_bc_kernel<T>), dim3((Lpad + 1 + 63) / 64, p.n_groups * (p.dstate / 16), p.batch), dim3(256), 0, stream, p,
-                       static_cast<float*>(p.workspace), Lpad);
     const int cpg = p.dim / p.n_groups;
     const int blocks = ((cpg / kWave) * p.n_groups + kChWaves - 1) / kChWaves;
     const dim3 block(kChWaves * kWave), grid(blocks, p.batch, sg.S);
-    if (p.dstate == 64) {
-        if (sg.S > 1) {
-            hipLaunchKernelGGL((ssm_fwd_chan_kernel<T, 1, false, 64>), grid, block, 0, stream, p, sg);
-            hipLaunchKernelGGL(ssm_fwd_carry64_kernel, dim3((unsigned)(p.batch * p.dim)), dim3(kWave), 0, stream, p, sg);
+    with_itype(p.itype, [&](auto t) {
+        typedef decltype(t) T;
+        hipLaunchKernelGGL((ssm_fwd_bc_kernel<T>), dim3((q.Lpad + 1 + 63) / 64, p.n_groups * (p.dstate / 16), p.batch), dim3(256),
+                           0, stream, p, static_cast<float*>(p.workspace), q.Lpad);
+        if (p.dstate == 64) {
+            if (sg.S > 1) {
+                hipLaunchKernelGGL((ssm_fwd_chan_kernel<T, 1, false, 64>), grid, block, 0, stream, p, sg);
+                hipLaunchKernelGGL(ssm_fwd_carry64_kernel, dim3((unsigned)(p.batch * p.dim)), dim3(kWave), 0, stream, p, sg);
+            }
+            if (p.z) hipLaunchKernelGGL((ssm_fwd_chan_kernel<T, 2, true, 64>), grid, block, 0, stream, p, sg);
+            else     hipLaunchKernelGGL((ssm_fwd_chan_kernel<T, 2, false, 64>), grid, block, 0, stream, p, sg);
+            return;
         }
-        if (p.z) hipLaunchKernelGGL((ssm_fwd_chan_kernel<T, 2, true, 64>), grid, block, 0, stream, p, sg);
-        else     hipLaunchKernelGGL((ssm_fwd_chan_kernel<T, 2, false, 64>), grid, block, 0, stream, p, sg);
-        return true;
-    }
-    if (sg.S > 1) {
-        hipLaunchKernelGGL((ssm_fwd_chan_kernel<T, 1, false>), grid, block, 0, stream, p, sg);
-        const size_t carry_lds = (size_t)sg.S * (kChN + 1) * sizeof(float);      // <= 34 KB (S <= 512)
-        hipLaunchKernelGGL(ssm_fwd_carry_kernel, dim3((unsigned)(p.batch * p.dim)), dim3(kWave), carry_lds, stream, p, sg);
-    }
-    if (p.z) hipLaunchKernelGGL((ssm_fwd_chan_kernel<T, 2, true>), grid, block, 0, stream, p, sg);
-    else     hipLaunchKernelGGL((ssm_fwd_chan_kernel<T, 2, false>), grid, block, 0, stream, p, sg);
-    return true;
-}
-
-bool try_fwd_chan(const vivim_ssm_fwd_params& p, hipStream_t stream) {
-    if (!fwd_chan_eligible(p)) return false;
-    switch (p.itype) {
-        case VIVIM_F32: return launch_fwd_chan<float>(p, stream);
-        case VIVIM_F16: return launch_fwd_chan<f16_t>(p, stream);
-        case VIVIM_BF16: return launch_fwd_chan<bf16_t>(p, stream);
-    }
-    return false;
+        if (sg.S > 1) {
+            hipLaunchKernelGGL((ssm_fwd_chan_kernel<T, 1, false>), grid, block, 0, stream, p, sg);
+            const size_t carry_lds = (size_t)sg.S * (kChN + 1) * sizeof(float);      // <= 34 KB (S <= 512)
+            hipLaunchKernelGGL(ssm_fwd_carry_kernel, dim3((unsigned)(p.batch * p.dim)), dim3(kWave), carry_lds, stream, p, sg);
+        }
+        if (p.z) hipLaunchKernelGGL((ssm_fwd_chan_kernel<T, 2, true>), grid, block, 0, stream, p, sg);
+        else     hipLaunchKernelGGL((ssm_fwd_chan_kernel<T, 2, false>), grid, block, 0, stream, p, sg);
+    });
 }
 
 }  // namespace vivim

@@ -25,10 +25,10 @@
 //     fixed order.  When the workgroup covers its whole group (Vivim stage 0: 128 channels) the result is STORED:
 //     no atomics, bit-reproducible; wider groups add one fp32 atomic per workgroup (reference: one per channel,
 //     selective_scan_bwd_kernel.cuh:312-313).
-//   * the token axis is cut into segments for parallelism (ls_segmentation); a segment's inflow (h from the left in
+//   * the token axis is cut into segments for parallelism (scan_plan.hip: ls_segmentation); a segment's inflow (h from the left in
 //     the forward, g from the right in the backward) comes from a pre-pass (recurrence only) and a carry kernel.
 // No alignment requirement: every activation access is one element per lane.
-#include "ls_common.cuh"
+#include "scan_plan.cuh"
 
 namespace vivim {
 
@@ -664,307 +664,101 @@ __global__ void __launch_bounds__(256) ssm_ls_fwd_kernel(const vivim_ssm_fwd_par
 // =========================================================================================================================
 // Host side
 // =========================================================================================================================
-static int ls_cu_count() {
-    static const int n = [] {
-        int dev = 0, v = 0;
-        if (hipGetDevice(&dev) != hipSuccess ||
-            hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || v <= 0)
-            v = 256;
-        return v;
-    }();
-    return n;
-}
-
-// Shape-only test (the checkpoint layout of `x` follows from it, so forward and backward must agree without looking at
-// pointers): variable B / C and a state count that fills whole rows.
-// ... whose (channel, token) byte offsets inside one batch element fit the 32-bit offsets of the buffer accesses (sizes
-// and strides only: the query must not depend on pointers).
-static bool ls_span_ok(int64_t rows, int64_t row_stride, int64_t len, int esize) {
-    return row_stride >= 0 && ((rows - 1) * row_stride + len) * esize < (int64_t)0xffff0000;
-}
-bool ls_shape_ok(const vivim_ssm_fwd_params& f) {
-    if (!(f.is_variable_B && f.is_variable_C && (f.dstate == 16 || f.dstate == 32 || f.dstate == 64) && f.dim % f.n_groups == 0))
-        return false;
-    const int es = f.itype == VIVIM_F32 ? 4 : 2;
-    // (the resource's size field carries the channel, 0xffff0000 + chu, and a lane that is off stores at offset 0xfffffff0,
-    // which must stay >= that size: chu < 65520)
-    if (f.dim > 65520 || !ls_span_ok(f.dim, f.u_d_stride, f.seqlen, es) || !ls_span_ok(f.dim, f.delta_d_stride, f.seqlen, es) ||
-        !ls_span_ok(f.dstate, f.B_dstate_stride, f.seqlen, es) || !ls_span_ok(f.dstate, f.C_dstate_stride, f.seqlen, es) ||
-        !ls_span_ok(f.dim, (int64_t)((f.seqlen + 15) / 16) * f.dstate, 0, 4))
-        return false;
-    if (f.z && (!ls_span_ok(f.dim, f.z_d_stride, f.seqlen, es))) return false;
-    return true;
-}
-int ls_ckpt_len(const vivim_ssm_fwd_params& f) { return 16 * (f.dstate / 16); }
-
-// Workgroup width of the backward: 16 * W channels (dstate 16) of one group share the dB / dC reduction.
-static int ls_bwd_waves(const vivim_ssm_fwd_params& f) {
-    const int cpw = (4 / (f.dstate / 16)) * kLsCPR;
-    const int cpg = f.dim / f.n_groups;
-    int w = (cpg + cpw - 1) / cpw;
-    // (8 waves = one workgroup per 128-channel group, plain dB / dC stores instead of two atomic contributions, measured
-    // SLOWER with the second-generation kernel: 583 against 557 us at cfg 2 grouped stage 0, 6466 against 5481 at cfg 3 --
-    // one workgroup per CU has nobody to run while it waits at its barriers)
-    return w > 4 ? 4 : w;
-}
-
-// Token-axis cut.  All workgroups of a launch take about the same time, so the launch runs in rounds of the resident
-// workgroups; one workgroup over a whole number of rounds costs a full extra round (the first build cut cfg 2 into 774
-// workgroups for 768 slots and took twice the time).  So: as many segments as FIT in `slots` waves (a whole number of
-// rounds when even one segment does not fit), whole checkpoint blocks per segment, at least `min_blocks` of them so that a
-// segment's prologue and the pre-pass stay a small part of it.
-static void ls_segmentation(const vivim_ssm_fwd_params& f, int waves_per_seg, int slots, int min_blocks, int& S, int& seg_blocks) {
-    const int ck = ls_ckpt_len(f);
-    const int nck = (f.seqlen + ck - 1) / ck;
-    int s = slots / waves_per_seg;                             // one round
-    const int smax = nck / min_blocks;
-    if (s > smax) s = smax;
-    if (s > 512) s = 512;
-    if (s < 1) s = 1;
-    seg_blocks = (nck + s - 1) / s;
-    S = (nck + seg_blocks - 1) / seg_blocks;
-}
-
-// Resident workgroups per CU of the backward instantiation that `f` selects, from the occupancy query (registers and LDS
-// differ between instantiations: 2 or 3 waves per SIMD); cached.  A build host without a GPU answers 3.
-template <typename T, int NS, bool HAS_Z> static int ls_bwd_blocks_per_cu_of(int W, size_t smem) {
-    static int cache[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};        // by W (1..8)
-    if (cache[W] == 0) {
-        int nb = 0;
-        if (smem > 65536)
-            (void)hipFuncSetAttribute(reinterpret_cast<const void*>(ssm_ls_bwd_kernel<T, NS, HAS_Z>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
-        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, ssm_ls_bwd_kernel<T, NS, HAS_Z>, W * kWave, smem) != hipSuccess || nb <= 0) {
-            (void)hipGetLastError();
-            nb = 3;
-        }
-        cache[W] = nb;
-    }
-    return cache[W];
-}
 static size_t ls_bwd_smem(int W, int NS) {
     // per wave: 8 KB of dB / dC slots + the channels' state (4 floats per lane and channel; dstate 32 / 64: + the rebuilt
     // states at the inner tile boundaries of a checkpoint block) + the D / bias table: 50.1 KB for 4 waves at dstate 16
     const int RPS = NS / 16, SPW = 4 / RPS;
-    static const size_t pad = getenv("VIVIM_LS_SMEM_PAD") ? (size_t)atoi(getenv("VIVIM_LS_SMEM_PAD")) : 0;   // occupancy experiments
     return ((size_t)W * SPW * 2 * NS * 16 + (size_t)W * kLsCPR * (4 + RPS - 1) * kWave + (size_t)W * kLsCPR * 8) * sizeof(float) +
-           (size_t)2 * NS * 16 * 4 + pad;                      // + the staged B / C rows of one tile (sized for fp32)
+           (size_t)2 * NS * 16 * 4 + scan_env().ls_smem_pad;   // + the staged B / C rows of one tile (sized for fp32)
 }
-template <typename T> static int ls_bwd_blocks_per_cu_t(const vivim_ssm_fwd_params& f, int W) {
-    const size_t smem = ls_bwd_smem(W, f.dstate);
-    const bool z = f.z != nullptr;
-    switch (f.dstate) {
-        case 16: return z ? ls_bwd_blocks_per_cu_of<T, 16, true>(W, smem) : ls_bwd_blocks_per_cu_of<T, 16, false>(W, smem);
-        case 32: return z ? ls_bwd_blocks_per_cu_of<T, 32, true>(W, smem) : ls_bwd_blocks_per_cu_of<T, 32, false>(W, smem);
-        case 64: return z ? ls_bwd_blocks_per_cu_of<T, 64, true>(W, smem) : ls_bwd_blocks_per_cu_of<T, 64, false>(W, smem);
+
+// Calls fn(T{}, LsGeom<NS>{}) for the element type and state count of `f`.
+template <typename F> static void with_itype_ns(const vivim_ssm_fwd_params& f, F&& fn) {
+    with_itype(f.itype, [&](auto t) {
+        switch (f.dstate) {
+            case 16: fn(t, LsGeom<16>{}); break;
+            case 32: fn(t, LsGeom<32>{}); break;
+            case 64: fn(t, LsGeom<64>{}); break;
+        }
+    });
+}
+
+int ls_bwd_occupancy(const vivim_ssm_fwd_params& f, int W) {
+    int nb = 3;
+    with_itype_ns(f, [&](auto t, auto g) {
+        typedef decltype(t) T;
+        constexpr int NS = decltype(g)::RPS * 16;
+        const size_t smem = ls_bwd_smem(W, NS);
+        nb = f.z ? occupancy_query(ssm_ls_bwd_kernel<T, NS, true>, W, smem, 3) : occupancy_query(ssm_ls_bwd_kernel<T, NS, false>, W, smem, 3);
+    });
+    return nb;
+}
+
+static LsSeg ls_seg(void* ws, const vivim_ssm_fwd_params& f, int S, int seg_blocks, bool bc_vec, int dbg) {
+    LsSeg sg = {S, seg_blocks, nullptr, nullptr, nullptr, bc_vec ? 1 : 0, dbg};
+    if (S > 1) {
+        const size_t nbd = (size_t)f.batch * f.dim * S;
+        sg.agg = static_cast<float*>(ws);
+        sg.gin = sg.agg + nbd * f.dstate;
+        sg.dsum = sg.gin + nbd * f.dstate;
     }
-    return 3;
-}
-static int ls_bwd_blocks_per_cu(const vivim_ssm_fwd_params& f, int W) {
-    switch (f.itype) {
-        case VIVIM_F32: return ls_bwd_blocks_per_cu_t<float>(f, W);
-        case VIVIM_F16: return ls_bwd_blocks_per_cu_t<f16_t>(f, W);
-        case VIVIM_BF16: return ls_bwd_blocks_per_cu_t<bf16_t>(f, W);
-    }
-    return 3;
+    return sg;
 }
 
-// second-generation main kernel (scan_ls2.hip): same workgroup geometry, its own residency
-bool ls2_bwd_ok(const vivim_ssm_bwd_params& p);
-bool fast_bwd_prepass(const vivim_ssm_bwd_params& p, int S, int seg_tokens, float* agg, float* gin, float* dsum, hipStream_t stream);   // scan_bwd.hip
-void ls2_bwd_launch(const vivim_ssm_bwd_params& p, const LsSeg& sg, int W, hipStream_t stream);
-int ls2_bwd_blocks_per_cu(int itype, bool has_z, int W);
-// Which main kernel a shape gets is decided from sizes alone (the workspace query has no pointers): dstate 16 and the
-// tuning selector (backward 0 automatic / 5 = second generation, 4 = first generation).  A call whose pointers or strides
-// then fail the vector checks of ls2_bwd_ok falls back to the first-generation kernel on the same segmentation.
-static bool ls2_wanted(const vivim_ssm_fwd_params& f) {
-    const int tv = tuning_bwd_variant();
-    const int epv = f.itype == VIVIM_F32 ? 4 : 8;
-    return f.dstate == 16 && f.seqlen % epv == 0 && (tv == 0 || tv == 5);
-}
-static void ls_bwd_plan(const vivim_ssm_fwd_params& f, int& W, int& S, int& seg_blocks) {
-    W = ls_bwd_waves(f);
-    const int cpw = (4 / (f.dstate / 16)) * kLsCPR;
-    const int cpg = f.dim / f.n_groups;
-    const int bpg = (cpg + W * cpw - 1) / (W * cpw);
-    const int waves_per_seg = bpg * W * f.n_groups * f.batch;
-    static int nb2[3][2][9] = {};
-    int nb;
-    if (ls2_wanted(f)) {
-        int& c = nb2[f.itype][f.z != nullptr][W];
-        if (c == 0) c = ls2_bwd_blocks_per_cu(f.itype, f.z != nullptr, W);
-        nb = c;
-    } else {
-        nb = ls_bwd_blocks_per_cu(f, W);
-    }
-    ls_segmentation(f, waves_per_seg, ls_cu_count() * nb * W, 4, S, seg_blocks);
-    // Long segments are cut at multiples of 256 tokens, so that the lanes = tokens pre-pass (scan_bwd.hip: fast_bwd_prepass,
-    // closed form, 16-byte vector loads) can stand in for the recurrence form of this file.
-    if (ls2_wanted(f) && S > 1 && seg_blocks >= 12) {
-        const int nck = (f.seqlen + 15) / 16;
-        seg_blocks = (seg_blocks + 8) / 16 * 16;
-        S = (nck + seg_blocks - 1) / seg_blocks;
-    }
-}
-// the forward / pre-pass kernels: 7 - 8 waves per SIMD (<= 72 VGPRs), no LDS
-static void ls_fwd_plan(const vivim_ssm_fwd_params& f, int& S, int& seg_blocks) {
-    const int cpw = (4 / (f.dstate / 16)) * kLsCPR;
-    const int cpg = f.dim / f.n_groups;
-    const int waves_per_seg = ((cpg + 4 * cpw - 1) / (4 * cpw)) * 4 * f.n_groups * f.batch;    // whole 4-wave workgroups
-    ls_segmentation(f, waves_per_seg, ls_cu_count() * 28, 4, S, seg_blocks);
-}
-
-size_t ls_bwd_workspace_bytes(const vivim_ssm_fwd_params& f) {
-    int W, S, sb;
-    ls_bwd_plan(f, W, S, sb);
-    if (S <= 1) return 0;
-    return (size_t)f.batch * f.dim * S * (2 * f.dstate + 1) * sizeof(float);
-}
-size_t ls_fwd_workspace_bytes(const vivim_ssm_fwd_params& f) {
-    int S, sb;
-    ls_fwd_plan(f, S, sb);
-    if (S <= 1) return 0;
-    return (size_t)f.batch * f.dim * S * (2 * f.dstate + 1) * sizeof(float);
-}
-
-static bool ls_bc_vec(const vivim_ssm_fwd_params& f) {
-    const int64_t epv = f.itype == VIVIM_F32 ? 4 : 8;
-    auto al = [&](const void* q) { return (reinterpret_cast<uintptr_t>(q) & 15) == 0; };
-    auto st = [&](int64_t e) { return e % epv == 0; };
-    return al(f.B) && al(f.C) && st(f.B_batch_stride) && st(f.B_group_stride) && st(f.B_dstate_stride) &&
-           st(f.C_batch_stride) && st(f.C_group_stride) && st(f.C_dstate_stride);
-}
-
-static void ls_seg_pointers(LsSeg& sg, void* ws, const vivim_ssm_fwd_params& f) {
-    const size_t nbd = (size_t)f.batch * f.dim * sg.S;
-    sg.agg = static_cast<float*>(ws);
-    sg.gin = sg.agg + nbd * f.dstate;
-    sg.dsum = sg.gin + nbd * f.dstate;
-}
-
-template <typename T, int NS>
-static bool launch_ls_bwd(const vivim_ssm_bwd_params& p, hipStream_t stream) {
-    typedef LsGeom<NS> G;
+// Segmented: the pre-pass (recurrence form, or the lanes = tokens closed form the plan picked) + carry; then the main kernel
+// of the plan's generation.
+void launch_ls_bwd(const vivim_ssm_bwd_params& p, const BwdPlan& q, hipStream_t stream) {
     const vivim_ssm_fwd_params& f = p.f;
-    int W, S, seg_blocks;
-    ls_bwd_plan(f, W, S, seg_blocks);
-    const int ck = G::CK;
-    const int nck = (f.seqlen + ck - 1) / ck;
-    LsSeg sg = {1, nck, nullptr, nullptr, nullptr, ls_bc_vec(f) ? 1 : 0, getenv("VIVIM_LS_DBG") ? atoi(getenv("VIVIM_LS_DBG")) : 0};
-    const size_t need = ls_bwd_workspace_bytes(f);
-    if (need && p.workspace && (size_t)p.workspace_bytes >= need) {
-        sg.S = S;
-        sg.seg_blocks = seg_blocks;
-        ls_seg_pointers(sg, p.workspace, f);
-    }
+    const LsSeg sg = ls_seg(p.workspace, f, q.S, q.seg, q.bc_vec, scan_env().ls_dbg);
     const int cpg = f.dim / f.n_groups;
-    const int bpg = (cpg + W * G::CPW - 1) / (W * G::CPW);
-    const bool second_gen = NS == 16 && ls2_wanted(f) && ls2_bwd_ok(p);
-    if (sg.S > 1 && second_gen && (sg.seg_blocks * 16) % 256 == 0 &&
-        fast_bwd_prepass(p, sg.S, sg.seg_blocks * 16, sg.agg, sg.gin, sg.dsum, stream)) {
-        // pre-pass + carry done by the lanes = tokens kernels
-    } else if (sg.S > 1) {
-        const int PW = 4;                                     // independent waves per pre-pass workgroup, one channel per row
-        const int pbpg = (cpg + PW * G::SPW - 1) / (PW * G::SPW);
-        const dim3 gpre(pbpg * f.n_groups, f.batch, sg.S - 1);
-        if (f.z) hipLaunchKernelGGL((ssm_ls_bwd_prepass_kernel<T, NS, true>), gpre, dim3(PW * kWave), 0, stream, p, sg);
-        else     hipLaunchKernelGGL((ssm_ls_bwd_prepass_kernel<T, NS, false>), gpre, dim3(PW * kWave), 0, stream, p, sg);
-        const int64_t nthr = (int64_t)f.batch * f.dim * f.dstate;
-        hipLaunchKernelGGL((ssm_ls_carry_kernel<true>), dim3((unsigned)((nthr + 255) / 256)), dim3(256), 0, stream,
-                           static_cast<const float*>(f.A), f.A_d_stride, f.A_dstate_stride, f.batch, f.dim, f.dstate, sg);
-    }
-    if (second_gen) {
-        ls2_bwd_launch(p, sg, W, stream);
-        return true;
-    }
-    const dim3 grid(bpg * f.n_groups, f.batch, sg.S);
-    const size_t smem = ls_bwd_smem(W, NS);
-    auto launch = [&](auto kernel) {
-        if (smem > 65536)
-            (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
-        hipLaunchKernelGGL(kernel, grid, dim3(W * kWave), smem, stream, p, sg);
-    };
-    if (f.z) launch(ssm_ls_bwd_kernel<T, NS, true>);
-    else     launch(ssm_ls_bwd_kernel<T, NS, false>);
-    return true;
+    if (q.closed_prepass) launch_bwd_closed_prepass(p, sg, q.K, stream);
+    with_itype_ns(f, [&](auto t, auto g) {
+        typedef decltype(t) T;
+        typedef decltype(g) G;
+        constexpr int NS = G::RPS * 16;
+        if (sg.S > 1 && !q.closed_prepass) {
+            const int PW = 4;                                     // independent waves per pre-pass workgroup, one channel per row
+            const int pbpg = (cpg + PW * G::SPW - 1) / (PW * G::SPW);
+            const dim3 gpre(pbpg * f.n_groups, f.batch, sg.S - 1);
+            if (f.z) hipLaunchKernelGGL((ssm_ls_bwd_prepass_kernel<T, NS, true>), gpre, dim3(PW * kWave), 0, stream, p, sg);
+            else     hipLaunchKernelGGL((ssm_ls_bwd_prepass_kernel<T, NS, false>), gpre, dim3(PW * kWave), 0, stream, p, sg);
+            const int64_t nthr = (int64_t)f.batch * f.dim * f.dstate;
+            hipLaunchKernelGGL((ssm_ls_carry_kernel<true>), dim3((unsigned)((nthr + 255) / 256)), dim3(256), 0, stream,
+                               static_cast<const float*>(f.A), f.A_d_stride, f.A_dstate_stride, f.batch, f.dim, f.dstate, sg);
+        }
+        if (q.ls2) return;
+        const int bpg = (cpg + q.W * G::CPW - 1) / (q.W * G::CPW);
+        const dim3 grid(bpg * f.n_groups, f.batch, sg.S);
+        const size_t smem = ls_bwd_smem(q.W, NS);
+        auto launch = [&](auto kernel) {
+            allow_smem(kernel, smem);
+            hipLaunchKernelGGL(kernel, grid, dim3(q.W * kWave), smem, stream, p, sg);
+        };
+        if (f.z) launch(ssm_ls_bwd_kernel<T, NS, true>);
+        else     launch(ssm_ls_bwd_kernel<T, NS, false>);
+    });
+    if (q.ls2) launch_ls2_bwd(p, sg, q.W, stream);
 }
 
-template <typename T, int NS>
-static bool launch_ls_fwd(const vivim_ssm_fwd_params& p, hipStream_t stream) {
-    typedef LsGeom<NS> G;
-    int S, seg_blocks;
-    ls_fwd_plan(p, S, seg_blocks);
-    const int nck = (p.seqlen + G::CK - 1) / G::CK;
-    LsSeg sg = {1, nck, nullptr, nullptr, nullptr, ls_bc_vec(p) ? 1 : 0, 0};
-    const size_t need = ls_fwd_workspace_bytes(p);
-    if (need && p.workspace && (size_t)p.workspace_bytes >= need) {
-        sg.S = S;
-        sg.seg_blocks = seg_blocks;
-        ls_seg_pointers(sg, p.workspace, p);
-    }
+void launch_ls_fwd(const vivim_ssm_fwd_params& p, const FwdPlan& q, hipStream_t stream) {
+    const LsSeg sg = ls_seg(p.workspace, p, q.S, q.seg, q.bc_vec, 0);
     const int cpg = p.dim / p.n_groups;
     const int PW = 4;
-    const int bpg = (cpg + PW * G::CPW - 1) / (PW * G::CPW);
-    const dim3 grid(bpg * p.n_groups, p.batch, sg.S), block(PW * kWave);
-    if (sg.S > 1) {
-        hipLaunchKernelGGL((ssm_ls_fwd_kernel<T, NS, 1, false>), grid, block, 0, stream, p, sg);
-        const int64_t nthr = (int64_t)p.batch * p.dim * p.dstate;
-        hipLaunchKernelGGL((ssm_ls_carry_kernel<false>), dim3((unsigned)((nthr + 255) / 256)), dim3(256), 0, stream,
-                           static_cast<const float*>(p.A), p.A_d_stride, p.A_dstate_stride, p.batch, p.dim, p.dstate, sg);
-    }
-    if (p.z) hipLaunchKernelGGL((ssm_ls_fwd_kernel<T, NS, 2, true>), grid, block, 0, stream, p, sg);
-    else     hipLaunchKernelGGL((ssm_ls_fwd_kernel<T, NS, 2, false>), grid, block, 0, stream, p, sg);
-    return true;
-}
-
-template <typename T> static bool ls_bwd_by_n(const vivim_ssm_bwd_params& p, hipStream_t s) {
-    switch (p.f.dstate) {
-        case 16: return launch_ls_bwd<T, 16>(p, s);
-        case 32: return launch_ls_bwd<T, 32>(p, s);
-        case 64: return launch_ls_bwd<T, 64>(p, s);
-    }
-    return false;
-}
-template <typename T> static bool ls_fwd_by_n(const vivim_ssm_fwd_params& p, hipStream_t s) {
-    switch (p.dstate) {
-        case 16: return launch_ls_fwd<T, 16>(p, s);
-        case 32: return launch_ls_fwd<T, 32>(p, s);
-        case 64: return launch_ls_fwd<T, 64>(p, s);
-    }
-    return false;
-}
-
-bool try_ls_bwd(const vivim_ssm_bwd_params& p, hipStream_t stream) {
-    if (!ls_shape_ok(p.f) || p.f.x == nullptr) return false;
-    {   // the tensors only the backward sees
-        const vivim_ssm_fwd_params& f = p.f;
-        const int es = f.itype == VIVIM_F32 ? 4 : 2;
-        if (!ls_span_ok(f.dim, p.dout_d_stride, f.seqlen, es) || !ls_span_ok(f.dim, p.du_d_stride, f.seqlen, es) ||
-            !ls_span_ok(f.dim, p.ddelta_d_stride, f.seqlen, es))
-            return false;
-        if (f.z && (!ls_span_ok(f.dim, f.out_d_stride, f.seqlen, es) || !ls_span_ok(f.dim, p.dz_d_stride, f.seqlen, es) ||
-                    (f.out_z && !ls_span_ok(f.dim, f.out_z_d_stride, f.seqlen, es))))
-            return false;
-    }
-    switch (p.f.itype) {
-        case VIVIM_F32: return ls_bwd_by_n<float>(p, stream);
-        case VIVIM_F16: return ls_bwd_by_n<f16_t>(p, stream);
-        case VIVIM_BF16: return ls_bwd_by_n<bf16_t>(p, stream);
-    }
-    return false;
-}
-bool try_ls_fwd(const vivim_ssm_fwd_params& p, hipStream_t stream) {
-    if (!ls_shape_ok(p)) return false;
-    {
-        const int es = p.itype == VIVIM_F32 ? 4 : 2;
-        if (!ls_span_ok(p.dim, p.out_d_stride, p.seqlen, es) || (p.z && !ls_span_ok(p.dim, p.out_z_d_stride, p.seqlen, es)))
-            return false;           // the caller reports "not implemented" (out / out_z normally inherit delta's / z's strides,
-    }                               // which ls_shape_ok has already accepted)
-    switch (p.itype) {
-        case VIVIM_F32: return ls_fwd_by_n<float>(p, stream);
-        case VIVIM_F16: return ls_fwd_by_n<f16_t>(p, stream);
-        case VIVIM_BF16: return ls_fwd_by_n<bf16_t>(p, stream);
-    }
-    return false;
+    with_itype_ns(p, [&](auto t, auto g) {
+        typedef decltype(t) T;
+        typedef decltype(g) G;
+        constexpr int NS = G::RPS * 16;
+        const int bpg = (cpg + PW * G::CPW - 1) / (PW * G::CPW);
+        const dim3 grid(bpg * p.n_groups, p.batch, sg.S), block(PW * kWave);
+        if (sg.S > 1) {
+            hipLaunchKernelGGL((ssm_ls_fwd_kernel<T, NS, 1, false>), grid, block, 0, stream, p, sg);
+            const int64_t nthr = (int64_t)p.batch * p.dim * p.dstate;
+            hipLaunchKernelGGL((ssm_ls_carry_kernel<false>), dim3((unsigned)((nthr + 255) / 256)), dim3(256), 0, stream,
+                               static_cast<const float*>(p.A), p.A_d_stride, p.A_dstate_stride, p.batch, p.dim, p.dstate, sg);
+        }
+        if (p.z) hipLaunchKernelGGL((ssm_ls_fwd_kernel<T, NS, 2, true>), grid, block, 0, stream, p, sg);
+        else     hipLaunchKernelGGL((ssm_ls_fwd_kernel<T, NS, 2, false>), grid, block, 0, stream, p, sg);
+    });
 }
 
 }  // namespace vivim

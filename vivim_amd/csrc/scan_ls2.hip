@@ -37,7 +37,7 @@
 // step loop; tools/experiments/ls2_w3.patch: +8 ... +20 % on 16-bit rows, +1 ... +2 % on fp32).  Timing
 // ablations (LS2_ABL): no LDS reads in the sweeps -11 %, no reductions -15 %, no forward rebuild -14 %, no epilogue -3 %:
 // the cost is spread over the instruction stream, which is what "VALU-bound" looks like from outside.
-#include "ls_common.cuh"
+#include "scan_plan.cuh"
 
 namespace vivim {
 
@@ -570,33 +570,15 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))
 // =========================================================================================================================
 // Host side
 // =========================================================================================================================
-size_t ls2_bwd_smem(int W, int itype) {
+static size_t ls2_bwd_smem(int W, int itype) {
     const int wb = itype == VIVIM_F32 ? Ls2Geom<float>::WB : Ls2Geom<bf16_t>::WB;
     const int es = itype == VIVIM_F32 ? 4 : 2;
-    static const size_t pad = getenv("VIVIM_LS2_SMEM_PAD") ? (size_t)atoi(getenv("VIVIM_LS2_SMEM_PAD")) : 0;   // occupancy experiments
-    return (size_t)W * wb + (size_t)W * kLsCPR * 8 * 4 + (size_t)2 * 16 * 16 * es + pad;
+    return (size_t)W * wb + (size_t)W * kLsCPR * 8 * 4 + (size_t)2 * 16 * 16 * es + scan_env().ls2_smem_pad;
 }
 
-// Vector path: every activation row 16-byte aligned and a whole number of 16-byte pieces long.
-bool ls2_bwd_ok(const vivim_ssm_bwd_params& p) {
-    const vivim_ssm_fwd_params& f = p.f;
-    if (f.dstate != 16 || !f.is_variable_B || !f.is_variable_C) return false;
-    const int64_t epv = f.itype == VIVIM_F32 ? 4 : 8;
-    auto al = [&](const void* q) { return (reinterpret_cast<uintptr_t>(q) & 15) == 0; };
-    auto st = [&](int64_t e) { return e % epv == 0; };
-    if (f.seqlen % epv != 0 || !al(f.u) || !al(f.delta) || !al(p.dout) || !al(p.du) || !al(p.ddelta) ||
-        !st(f.u_batch_stride) || !st(f.u_d_stride) || !st(f.delta_batch_stride) || !st(f.delta_d_stride) ||
-        !st(p.dout_batch_stride) || !st(p.dout_d_stride) || !st(p.du_batch_stride) || !st(p.du_d_stride) ||
-        !st(p.ddelta_batch_stride) || !st(p.ddelta_d_stride))
-        return false;
-    if (f.z && (!al(f.z) || !al(f.out) || !al(p.dz) || !st(f.z_batch_stride) || !st(f.z_d_stride) ||
-                !st(f.out_batch_stride) || !st(f.out_d_stride) || !st(p.dz_batch_stride) || !st(p.dz_d_stride) ||
-                (f.out_z && (!al(f.out_z) || !st(f.out_z_batch_stride) || !st(f.out_z_d_stride)))))
-        return false;
-    return true;
-}
-
-template <typename T> static void ls2_launch_t(const vivim_ssm_bwd_params& p, const LsSeg& sg, int W, hipStream_t stream) {
+// Same workgroup geometry as the first generation; the plan (scan_plan.hip) has checked that every activation row is
+// 16-byte aligned and a whole number of 16-byte pieces long.
+void launch_ls2_bwd(const vivim_ssm_bwd_params& p, const LsSeg& sg, int W, hipStream_t stream) {
     const vivim_ssm_fwd_params& f = p.f;
     const int cpg = f.dim / f.n_groups;
     const int cpb = W * 4 * kLsCPR;
@@ -604,36 +586,22 @@ template <typename T> static void ls2_launch_t(const vivim_ssm_bwd_params& p, co
     const dim3 grid(bpg * f.n_groups, f.batch, sg.S);
     const size_t smem = ls2_bwd_smem(W, f.itype);
     auto launch = [&](auto kernel) {
-        if (smem > 65536)
-            (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
+        allow_smem(kernel, smem);
         hipLaunchKernelGGL(kernel, grid, dim3(W * kWave), smem, stream, p, sg);
     };
-    if (f.z) launch(ssm_ls2_bwd_kernel<T, true>); else launch(ssm_ls2_bwd_kernel<T, false>);
+    with_itype(f.itype, [&](auto t) {
+        typedef decltype(t) T;
+        if (f.z) launch(ssm_ls2_bwd_kernel<T, true>); else launch(ssm_ls2_bwd_kernel<T, false>);
+    });
 }
 
-void ls2_bwd_launch(const vivim_ssm_bwd_params& p, const LsSeg& sg, int W, hipStream_t stream) {
-    switch (p.f.itype) {
-        case VIVIM_F32: ls2_launch_t<float>(p, sg, W, stream); break;
-        case VIVIM_F16: ls2_launch_t<f16_t>(p, sg, W, stream); break;
-        case VIVIM_BF16: ls2_launch_t<bf16_t>(p, sg, W, stream); break;
-    }
-}
-
-int ls2_bwd_blocks_per_cu(int itype, bool has_z, int W) {
-    int nb = 0;
-    const size_t smem = ls2_bwd_smem(W, itype);
-    hipError_t e = hipSuccess;
-    auto q = [&](auto kernel) {
-        if (smem > 65536)
-            (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
-        e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, kernel, W * kWave, smem);
-    };
-    auto by_t = [&](auto tag) {
-        typedef decltype(tag) T;
-        if (has_z) q(ssm_ls2_bwd_kernel<T, true>); else q(ssm_ls2_bwd_kernel<T, false>);
-    };
-    if (itype == VIVIM_F32) by_t(float{}); else if (itype == VIVIM_F16) by_t(f16_t{}); else by_t(bf16_t{});
-    if (e != hipSuccess || nb <= 0) { (void)hipGetLastError(); nb = 2; }
+int ls2_bwd_occupancy(const vivim_ssm_fwd_params& f, int W) {
+    int nb = 2;
+    const size_t smem = ls2_bwd_smem(W, f.itype);
+    with_itype(f.itype, [&](auto t) {
+        typedef decltype(t) T;
+        nb = f.z ? occupancy_query(ssm_ls2_bwd_kernel<T, true>, W, smem, 2) : occupancy_query(ssm_ls2_bwd_kernel<T, false>, W, smem, 2);
+    });
     return nb;
 }
 
