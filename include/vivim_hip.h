@@ -330,6 +330,43 @@ int vivim_layernorm_cm_bwd(const vivim_layernorm_params *p, void *stream);
 size_t vivim_layernorm_bwd_workspace_bytes(const vivim_layernorm_params *p);   /* from batch, seqlen, channels, itype */
 int vivim_wgrad_nt(const vivim_wgrad_nt_params *p, void *stream);
 
+/* Deterministic backward (for torch.use_deterministic_algorithms).  Same parameters, checks and results as
+ * vivim_selective_scan_bwd, and the same kernel family, but every gradient that the default call adds up across
+ * workgroups with float atomics (dA, dD, ddelta_bias, dB, dC) is a pure function of the inputs, the shapes and the
+ * vivim_set_tuning values: each contributing workgroup stores its partial sum into its own slot of `det_ws` (slot
+ * index from its coordinates, never from arrival order), and one fixed-order kernel adds the slots to the outputs.
+ * The outputs must be pre-zeroed as for the default call; the contents of `det_ws` on entry do not matter and are
+ * undefined afterwards.  A NULL, misaligned (< 16 bytes) or too small `det_ws` returns VIVIM_ERR_INVALID before
+ * anything is launched.  The dB / dC adds of the lanes = states kernels stay when a B/C group has at most two
+ * workgroups: 0 + a + b == 0 + b + a exactly.
+ *
+ * Workspace, in floats (depends on the sizes and flags in `f` and the tuning values, not on pointers): the larger of
+ * the generic family's and the family the shape's plan prefers, where for slot counts SA (dA / dD / dbias) and
+ * SB (dB / dC) a family needs  SA * dim * (dstate + 2) + 2 * SB * EB:
+ *   generic:           SA = batch;  variable B/C: SB = ceil(dim / n_groups / 2), EB = batch * n_groups * dstate * seqlen;
+ *                      constant B/C: SB = batch, EB = dim * dstate;
+ *   lanes = tokens:    SA = batch * segments;  SB = workgroups per B/C group, EB = batch * n_groups * dstate * seqlen;
+ *   lanes = states:    SA = batch * segments;  SB = workgroups per B/C group if more than two, else 0. */
+size_t vivim_scan_bwd_det_workspace_bytes(const vivim_ssm_fwd_params *f);
+/* The exact workspace of one call: the formula above for the family this call's pointers select (never more than the
+ * shape-level bound above; 0 on bad params).  vivim_selective_scan_bwd_det accepts any workspace of at least this size.
+ * The lanes = tokens kernel at 8 tokens per lane runs with 4-wave workgroups in this mode (the 8-wave build has no VGPR
+ * left for the slot stores); it re-segments for that width and runs unsegmented (S = 1) if p->workspace is too small
+ * for that segmentation (vivim_scan_bwd_workspace_bytes sizes it for the default plan). */
+size_t vivim_scan_bwd_det_call_workspace_bytes(const vivim_ssm_bwd_params *p);
+int vivim_selective_scan_bwd_det(const vivim_ssm_bwd_params *p, void *det_ws, size_t det_ws_bytes, void *stream);
+
+/* Deterministic causal conv1d backward: same parameters, checks and dx as vivim_causal_conv1d_bwd; dweight / dbias
+ * (pre-zeroed) come from per-(batch, token chunk) slots added in fixed order, no float atomics.  Workspace:
+ * slots * dim * (width + 1) floats, slots = batch * ceil(seqlen / (256 * 16 / sizeof(itype))) for channel-first x and
+ * batch * (token chunks of the channel-last kernel) for channel-last x.  Contract on det_ws as for the scan above. */
+size_t vivim_causal_conv1d_bwd_det_workspace_bytes(const vivim_conv_fwd_params *f);
+int vivim_causal_conv1d_bwd_det(const vivim_conv_bwd_params *p, void *det_ws, size_t det_ws_bytes, void *stream);
+/* Deterministic depthwise-conv weight gradient: as vivim_dwconv_wgrad, dwt / dbias (pre-zeroed) from per-(batch,
+ * token block) slots of (kd * 9 + 1) * channels floats added in fixed order.  Contract on det_ws as above. */
+size_t vivim_dwconv_wgrad_det_workspace_bytes(const vivim_dwconv_wgrad_params *p);
+int vivim_dwconv_wgrad_det(const vivim_dwconv_wgrad_params *p, void *det_ws, size_t det_ws_bytes, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -124,7 +124,10 @@ EXPORTS = ("vivim_abi_version", "vivim_last_error", "vivim_scan_chunk_len", "viv
            "vivim_selective_scan_fwd", "vivim_selective_scan_bwd",
            "vivim_causal_conv1d_fwd", "vivim_causal_conv1d_bwd", "vivim_dwconv_fwd", "vivim_dwconv_wgrad",
            "vivim_dir_scatter", "vivim_dir_gather", "vivim_causal_conv1d_update", "vivim_selective_state_update",
-           "vivim_layernorm_cm_fwd", "vivim_layernorm_cm_bwd", "vivim_layernorm_bwd_workspace_bytes", "vivim_wgrad_nt")
+           "vivim_layernorm_cm_fwd", "vivim_layernorm_cm_bwd", "vivim_layernorm_bwd_workspace_bytes", "vivim_wgrad_nt",
+           "vivim_scan_bwd_det_workspace_bytes", "vivim_scan_bwd_det_call_workspace_bytes", "vivim_selective_scan_bwd_det",
+           "vivim_causal_conv1d_bwd_det_workspace_bytes", "vivim_causal_conv1d_bwd_det",
+           "vivim_dwconv_wgrad_det_workspace_bytes", "vivim_dwconv_wgrad_det")
 
 _lib = None
 
@@ -171,6 +174,17 @@ def lib():
             fn = getattr(L, name)
             fn.argtypes = [ctypes.POINTER(st), vp]
             fn.restype = ctypes.c_int
+        L.vivim_scan_bwd_det_workspace_bytes.restype = ctypes.c_size_t
+        L.vivim_scan_bwd_det_workspace_bytes.argtypes = [ctypes.POINTER(SsmFwdParams)]
+        for name, st in (("vivim_scan_bwd_det_call_workspace_bytes", SsmBwdParams),
+                         ("vivim_causal_conv1d_bwd_det_workspace_bytes", ConvFwdParams),
+                         ("vivim_dwconv_wgrad_det_workspace_bytes", DwConvWgradParams)):
+            getattr(L, name).restype = ctypes.c_size_t
+            getattr(L, name).argtypes = [ctypes.POINTER(st)]
+        for name, st in (("vivim_selective_scan_bwd_det", SsmBwdParams), ("vivim_causal_conv1d_bwd_det", ConvBwdParams),
+                         ("vivim_dwconv_wgrad_det", DwConvWgradParams)):
+            getattr(L, name).argtypes = [ctypes.POINTER(st), vp, ctypes.c_size_t, vp]
+            getattr(L, name).restype = ctypes.c_int
         L.vivim_layernorm_bwd_workspace_bytes.argtypes = [ctypes.POINTER(LayerNormParams)]
         L.vivim_layernorm_bwd_workspace_bytes.restype = ctypes.c_size_t
         if L.vivim_abi_version() != 8:
@@ -307,6 +321,24 @@ def check_guards(what):
             raise RuntimeError(f"VIVIM_GUARD: {what} wrote outside a {buf.numel() - 2 * _GUARD_BYTES}-byte buffer "
                                f"({nlo} bytes below, {nhi} bytes above)")
     _guards.clear()
+
+
+def deterministic():
+    """True while torch.use_deterministic_algorithms is on (warn_only included): the backward entry points then take
+    their deterministic variants."""
+    import torch
+    return torch.are_deterministic_algorithms_enabled()
+
+
+def call_det(name, params, det_ws, det_ws_bytes, stream):
+    """Enqueue a deterministic-variant entry point (params, det workspace, its bytes, stream); RuntimeError on a
+    nonzero return."""
+    L = lib()
+    rc = getattr(L, name)(ctypes.byref(params), vp(det_ws), ctypes.c_size_t(det_ws_bytes), vp(stream))
+    if rc != 0:
+        raise RuntimeError(L.vivim_last_error().decode())
+    if GUARD:
+        check_guards(name)
 
 
 def call(name, params, stream):

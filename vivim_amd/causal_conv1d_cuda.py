@@ -4,6 +4,8 @@ positional signatures, checks and returns, on the gfx950 kernels behind include/
 `causal_conv1d_update` (single-token step for streaming inference) and the channel-last layout (unit stride along
 channels) are built too; neither is on Vivim's training path.
 """
+import ctypes
+
 import torch
 
 from . import _lib
@@ -105,7 +107,12 @@ def causal_conv1d_bwd(x, weight, bias_, dout, dx_, silu_activation):
     P.dx_batch_stride, P.dx_c_stride, P.dx_l_stride = dx.stride()
     P.dweight_c_stride, P.dweight_width_stride = dweight.stride()
     with torch.cuda.device(x.device):
-        _lib.call("vivim_causal_conv1d_bwd", P, torch.cuda.current_stream().cuda_stream)
+        if _lib.deterministic():                      # fixed-order slot reduction of dweight / dbias, no float atomics
+            nbytes = _lib.lib().vivim_causal_conv1d_bwd_det_workspace_bytes(ctypes.byref(P.f))
+            ws = _lib.empty((nbytes,), torch.uint8, x.device)
+            _lib.call_det("vivim_causal_conv1d_bwd_det", P, ws.data_ptr(), nbytes, torch.cuda.current_stream().cuda_stream)
+        else:
+            _lib.call("vivim_causal_conv1d_bwd", P, torch.cuda.current_stream().cuda_stream)
     return [dx, dweight.to(weight.dtype), dbias.to(bias_.dtype) if bias_ is not None else None]
 
 

@@ -5,6 +5,7 @@
 #include <stdarg.h>
 #include <stdio.h>
 #include "../../include/vivim_hip.h"
+#include "det.cuh"
 
 namespace vivim {
 bool conv_fwd_dispatch(const vivim_conv_fwd_params&, hipStream_t);
@@ -21,6 +22,15 @@ bool ssm_bwd_dispatch(const vivim_ssm_bwd_params&, hipStream_t);
 int scan_chunk_len(int itype);
 int scan_ckpt_len(const vivim_ssm_fwd_params&);
 size_t scan_bwd_workspace_bytes(const vivim_ssm_fwd_params&);
+size_t scan_bwd_det_workspace_bytes(const vivim_ssm_fwd_params&);                   // scan_plan.hip
+size_t scan_bwd_det_call_workspace_bytes(const vivim_ssm_bwd_params&);
+size_t conv_bwd_det_slots(const vivim_conv_fwd_params&);                             // conv1d.hip / conv1d_cl.hip
+bool conv_bwd_det_launch(const vivim_conv_bwd_params&, hipStream_t);
+size_t conv_cl_bwd_det_slots(const vivim_conv_fwd_params&);
+bool conv_cl_bwd_det_launch(const vivim_conv_bwd_params&, hipStream_t);
+size_t dwconv_wgrad_det_workspace_bytes(const vivim_dwconv_wgrad_params&);           // dwconv.hip
+int dwconv_wgrad_det_dispatch(const vivim_dwconv_wgrad_params&, void*, size_t, hipStream_t);
+int ssm_bwd_det_dispatch(const vivim_ssm_bwd_params&, void* det_ws, size_t det_ws_bytes, hipStream_t);
 bool layernorm_dispatch(const vivim_layernorm_params&, bool bwd, hipStream_t);   // layernorm.hip
 size_t layernorm_bwd_workspace_bytes(const vivim_layernorm_params&);
 bool wgrad_nt_dispatch(const vivim_wgrad_nt_params&, hipStream_t);                 // wgrad.hip
@@ -128,16 +138,41 @@ int vivim_selective_scan_fwd(const vivim_ssm_fwd_params* p, void* stream) {
     return after_launch("selective_scan_fwd");
 }
 
-int vivim_selective_scan_bwd(const vivim_ssm_bwd_params* p, void* stream) {
+static int check_ssm_bwd(const vivim_ssm_bwd_params* p) {
     VCHECK(p != nullptr);
     if (int rc = check_ssm_fwd(&p->f, true)) return rc;
     VCHECK(p->dout && p->du && p->ddelta && p->dA && p->dB && p->dC);
     VCHECK((p->f.D == nullptr) == (p->dD == nullptr));
     VCHECK((p->f.delta_bias == nullptr) == (p->ddelta_bias == nullptr));
     VCHECK((p->f.z == nullptr) == (p->dz == nullptr));
+    return VIVIM_OK;
+}
+
+int vivim_selective_scan_bwd(const vivim_ssm_bwd_params* p, void* stream) {
+    if (int rc = check_ssm_bwd(p)) return rc;
     if (!vivim::ssm_bwd_dispatch(*p, static_cast<hipStream_t>(stream)))
         return fail(VIVIM_ERR_UNSUPPORTED, "selective_scan_bwd not implemented for input type %d", p->f.itype);
     return after_launch("selective_scan_bwd");
+}
+
+size_t vivim_scan_bwd_det_workspace_bytes(const vivim_ssm_fwd_params* f) {
+    return f && f->batch > 0 && f->dim > 0 && f->seqlen > 0 && f->dstate > 0 && f->n_groups > 0
+               ? vivim::scan_bwd_det_workspace_bytes(*f) : 0;
+}
+
+size_t vivim_scan_bwd_det_call_workspace_bytes(const vivim_ssm_bwd_params* p) {
+    return check_ssm_bwd(p) == VIVIM_OK ? vivim::scan_bwd_det_call_workspace_bytes(*p) : 0;
+}
+
+int vivim_selective_scan_bwd_det(const vivim_ssm_bwd_params* p, void* det_ws, size_t det_ws_bytes, void* stream) {
+    if (int rc = check_ssm_bwd(p)) return rc;
+    switch (vivim::ssm_bwd_det_dispatch(*p, det_ws, det_ws_bytes, static_cast<hipStream_t>(stream))) {
+        case 0: break;
+        case 2: return fail(VIVIM_ERR_INVALID, "selective_scan_bwd_det: workspace of %zu bytes at %p: need a 16-byte aligned one of "
+                            "vivim_scan_bwd_det_call_workspace_bytes() = %zu", det_ws_bytes, det_ws, vivim::scan_bwd_det_call_workspace_bytes(*p));
+        default: return fail(VIVIM_ERR_UNSUPPORTED, "selective_scan_bwd_det not implemented for input type %d", p->f.itype);
+    }
+    return after_launch("selective_scan_bwd_det");
 }
 
 static int check_conv(const vivim_conv_fwd_params* p) {
@@ -166,6 +201,45 @@ int vivim_causal_conv1d_fwd(const vivim_conv_fwd_params* p, void* stream) {
         return fail(VIVIM_ERR_UNSUPPORTED, "causal_conv1d_fwd not implemented for input type %d / weight type %d",
                     p->itype, p->wtype);
     return after_launch("causal_conv1d_fwd");
+}
+
+static int check_conv_bwd(const vivim_conv_bwd_params* p) {
+    VCHECK(p != nullptr);
+    if (int rc = check_conv(&p->f)) return rc;
+    VCHECK(p->dout && p->dx && p->dweight);
+    const bool cl = conv_channel_last(&p->f);
+    if (cl) { VCHECK(p->dout_c_stride == 1 && p->dx_c_stride == 1); }
+    else    { VCHECK(p->dout_l_stride == 1 && p->dx_l_stride == 1); }
+    VCHECK((p->f.bias == nullptr) == (p->dbias == nullptr));
+    return VIVIM_OK;
+}
+
+size_t vivim_causal_conv1d_bwd_det_workspace_bytes(const vivim_conv_fwd_params* f) {
+    if (check_conv(f) != VIVIM_OK) return 0;
+    const size_t slots = conv_channel_last(f) ? vivim::conv_cl_bwd_det_slots(*f) : vivim::conv_bwd_det_slots(*f);
+    return sizeof(float) * slots * (size_t)f->dim * (f->width + 1);
+}
+
+int vivim_causal_conv1d_bwd_det(const vivim_conv_bwd_params* p, void* det_ws, size_t det_ws_bytes, void* stream) {
+    if (int rc = check_conv_bwd(p)) return rc;
+    const size_t need = vivim_causal_conv1d_bwd_det_workspace_bytes(&p->f);
+    if (det_ws == nullptr || det_ws_bytes < need || reinterpret_cast<uintptr_t>(det_ws) % 16 != 0)
+        return fail(VIVIM_ERR_INVALID, "causal_conv1d_bwd_det: workspace of %zu bytes at %p: need a 16-byte aligned one of "
+                    "vivim_causal_conv1d_bwd_det_workspace_bytes() = %zu", det_ws_bytes, det_ws, need);
+    const bool cl = conv_channel_last(&p->f);
+    const hipStream_t s = static_cast<hipStream_t>(stream);
+    vivim_conv_bwd_params d = *p;
+    d.dweight = det_ws;
+    d.dbias = nullptr;
+    if (!(cl ? vivim::conv_cl_bwd_det_launch(d, s) : vivim::conv_bwd_det_launch(d, s)))
+        return fail(VIVIM_ERR_UNSUPPORTED, "causal_conv1d_bwd_det not implemented for input type %d / weight type %d",
+                    p->f.itype, p->f.wtype);
+    const int slots = (int)(cl ? vivim::conv_cl_bwd_det_slots(p->f) : vivim::conv_bwd_det_slots(p->f));
+    const int64_t D = p->f.dim, W = p->f.width, sstride = D * (W + 1);
+    const float* ws = static_cast<const float*>(det_ws);
+    vivim::det_reduce(ws, slots, vivim::det_out(static_cast<float*>(p->dweight), {D, W}, {p->dweight_c_stride, p->dweight_width_stride}), s, sstride);
+    if (p->dbias) vivim::det_reduce(ws + D * W, slots, vivim::det_out(static_cast<float*>(p->dbias), {D}, {1}), s, sstride);
+    return after_launch("causal_conv1d_bwd_det");
 }
 
 int vivim_causal_conv1d_bwd(const vivim_conv_bwd_params* p, void* stream) {
@@ -206,6 +280,34 @@ int vivim_dwconv_fwd(const vivim_dwconv_params* p, void* stream) {
     if (!vivim::dwconv_fwd_dispatch(*p, static_cast<hipStream_t>(stream)))
         return fail(VIVIM_ERR_UNSUPPORTED, "dwconv_fwd not implemented for input type %d", p->itype);
     return after_launch("dwconv_fwd");
+}
+
+static int check_dw_wgrad(const vivim_dwconv_wgrad_params* p) {
+    VCHECK(p != nullptr);
+    if (int rc = check_dw_dims(p->batch, p->depth, p->height, p->width, p->channels, p->kd, p->itype)) return rc;
+    VCHECK(p->x && p->dy && p->dwt);
+    VCHECK(p->channels % 2 == 0 && p->x_token_stride % 2 == 0 && p->x_batch_stride % 2 == 0 &&
+           p->dy_token_stride % 2 == 0 && p->dy_batch_stride % 2 == 0);
+    VCHECK((reinterpret_cast<uintptr_t>(p->x) & 7) == 0 && (reinterpret_cast<uintptr_t>(p->dy) & 7) == 0);
+    return VIVIM_OK;
+}
+
+size_t vivim_dwconv_wgrad_det_workspace_bytes(const vivim_dwconv_wgrad_params* p) {
+    if (!p || p->batch <= 0 || p->depth <= 0 || p->height <= 0 || p->width <= 0 || p->channels <= 0 || (p->kd != 1 && p->kd != 3))
+        return 0;
+    return vivim::dwconv_wgrad_det_workspace_bytes(*p);
+}
+
+int vivim_dwconv_wgrad_det(const vivim_dwconv_wgrad_params* p, void* det_ws, size_t det_ws_bytes, void* stream) {
+    if (int rc = check_dw_wgrad(p)) return rc;
+    switch (vivim::dwconv_wgrad_det_dispatch(*p, det_ws, det_ws_bytes, static_cast<hipStream_t>(stream))) {
+        case 0: break;
+        case 2: return fail(VIVIM_ERR_INVALID, "dwconv_wgrad_det: workspace of %zu bytes at %p: need a 16-byte aligned one of "
+                            "vivim_dwconv_wgrad_det_workspace_bytes() = %zu", det_ws_bytes, det_ws,
+                            vivim::dwconv_wgrad_det_workspace_bytes(*p));
+        default: return fail(VIVIM_ERR_UNSUPPORTED, "dwconv_wgrad_det not implemented for input type %d", p->itype);
+    }
+    return after_launch("dwconv_wgrad_det");
 }
 
 int vivim_dwconv_wgrad(const vivim_dwconv_wgrad_params* p, void* stream) {

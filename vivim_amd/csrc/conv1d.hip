@@ -11,7 +11,7 @@
 //   * conv1d_{fwd,bwd}_kernel: everything else (ragged or unaligned rows, rows of one tile: stage 3's 320 tokens).  One
 //     tile per wave; halos move between neighbouring lanes with wave shuffles, the two lanes at the wave edges fetch
 //     theirs with guarded scalar loads.
-#include "common.cuh"
+#include "det.cuh"
 
 namespace vivim {
 
@@ -93,7 +93,9 @@ __global__ void __launch_bounds__(kConvThreads) conv1d_fwd_kernel(const vivim_co
 //   g[t]   = dout[t] * silu'(pre[t])            (pre recomputed from x, bwd.cu:163-175)
 //   dx[s]  = sum_j w4[j] * g[s + 3 - j]
 //   dw4[j] = sum_t g[t] * x[t - 3 + j],  dbias = sum_t g[t]     (own tokens only, then reduced)
-template <typename T, typename WT, int E, bool PACK>
+// DET (vivim_causal_conv1d_bwd_det, PACK false only): the workgroup stores its sums into slot (batch, tile) of p.dweight =
+// the workspace, dim * (width + 1) floats per slot: dweight (dim, width) then dbias (dim).
+template <typename T, typename WT, int E, bool PACK, bool DET = false>
 __global__ void __launch_bounds__(kConvThreads) conv1d_bwd_kernel(const vivim_conv_bwd_params p) {
     const vivim_conv_fwd_params& f = p.f;
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
@@ -193,7 +195,12 @@ __global__ void __launch_bounds__(kConvThreads) conv1d_bwd_kernel(const vivim_co
         float s = 0.f;
 #pragma unroll
         for (int w = 0; w < kConvThreads / kWave; ++w) s += part[w][threadIdx.x];
-        if (threadIdx.x < 4) {
+        if (DET) {
+            float* slot = static_cast<float*>(p.dweight) + ((int64_t)b * gridDim.x + blockIdx.x) * f.dim * (f.width + 1);
+            const int src = (int)threadIdx.x - (4 - f.width);
+            if (threadIdx.x == 4) slot[(int64_t)f.dim * f.width + c] = s;
+            else if (src >= 0) slot[(int64_t)c * f.width + src] = s;
+        } else if (threadIdx.x < 4) {
             const int src = (int)threadIdx.x - (4 - f.width);
             if (src >= 0)
                 atomicAdd(static_cast<float*>(p.dweight) + c * p.dweight_c_stride + src * p.dweight_width_stride, s);
@@ -460,6 +467,38 @@ static bool dispatch_w_fwd(const vivim_conv_fwd_params& p, hipStream_t s) {
     }
     return false;
 }
+// Deterministic: the one-tile-per-workgroup kernel for every shape, (batch, tile) slots.
+static dim3 conv_det_grid(const vivim_conv_fwd_params& f, int esize) {
+    const int E = 16 / esize;
+    return dim3((f.seqlen + kConvThreads * E - 1) / (kConvThreads * E), f.dim, f.batch);
+}
+template <typename T, typename WT>
+static void launch_conv_bwd_det(const vivim_conv_bwd_params& p, hipStream_t stream) {
+    constexpr int E = 16 / sizeof(T);
+    hipLaunchKernelGGL((conv1d_bwd_kernel<T, WT, E, false, true>), conv_det_grid(p.f, sizeof(T)), dim3(kConvThreads), 0, stream, p);
+}
+size_t conv_bwd_det_slots(const vivim_conv_fwd_params& f) {
+    const dim3 g = conv_det_grid(f, f.itype == VIVIM_F32 ? 4 : 2);
+    return (size_t)g.x * g.z;
+}
+bool conv_bwd_det_launch(const vivim_conv_bwd_params& p, hipStream_t s) {
+    auto w = [&](auto t) {
+        typedef decltype(t) T;
+        switch (p.f.wtype) {
+            case VIVIM_F32: launch_conv_bwd_det<T, float>(p, s); return true;
+            case VIVIM_F16: launch_conv_bwd_det<T, f16_t>(p, s); return true;
+            case VIVIM_BF16: launch_conv_bwd_det<T, bf16_t>(p, s); return true;
+        }
+        return false;
+    };
+    switch (p.f.itype) {
+        case VIVIM_F32: return w(float{});
+        case VIVIM_F16: return w(f16_t{});
+        case VIVIM_BF16: return w(bf16_t{});
+    }
+    return false;
+}
+
 template <typename T>
 static bool dispatch_w_bwd(const vivim_conv_bwd_params& p, hipStream_t s) {
     switch (p.f.wtype) {

@@ -7,7 +7,7 @@
 // tokens, keeps the last three rows of its channels in registers as the sliding window and walks its chunk row by row.
 // Every row access of a wave is one contiguous run of 64 * E elements; there is no shared memory and no barrier.  The halo
 // costs three extra rows per chunk (forward) or six (backward).  Not on Vivim's path (its x has unit seqlen stride).
-#include "common.cuh"
+#include "det.cuh"
 
 namespace vivim {
 
@@ -83,7 +83,9 @@ __global__ void __launch_bounds__(kClThreads) conv1d_cl_fwd_kernel(const vivim_c
 // Backward, one forward walk over [t0, t1 + 3): at row t the lane forms g[t] = dout[t] * silu'(pre[t]) from its x window
 // and emits dx[t-3] = w4[3] g[t-3] + w4[2] g[t-2] + w4[1] g[t-1] + w4[0] g[t] from its g window.  dweight / dbias sums run
 // over the lane's own rows [t0, t1) and leave through one atomic per (channel, tap) per chunk.
-template <typename T, int E>
+// DET (vivim_causal_conv1d_bwd_det): the lane stores its sums into slot (batch, chunk) of p.dweight = the workspace,
+// dim * (width + 1) floats per slot: dweight (dim, width) then dbias (dim).
+template <typename T, int E, bool DET = false>
 __global__ void __launch_bounds__(kClThreads) conv1d_cl_bwd_kernel(const vivim_conv_bwd_params p, const ClGeom g) {
     const vivim_conv_fwd_params& f = p.f;
     const int64_t gid = (int64_t)blockIdx.x * kClThreads + threadIdx.x;
@@ -151,6 +153,20 @@ __global__ void __launch_bounds__(kClThreads) conv1d_cl_bwd_kernel(const vivim_c
         const int s = t - 3;
         if (s >= t0 && s < t1) store_k<T, E>(dx + (int64_t)s * p.dx_l_stride, nv, o);
     }
+    if (DET) {
+        float* slot = static_cast<float*>(p.dweight) + ((int64_t)b * g.nchunk + chunk) * f.dim * (f.width + 1);
+#pragma unroll
+        for (int e = 0; e < E; ++e) {
+            if (e >= nv) continue;
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                const int src = j - (4 - f.width);
+                if (src >= 0) slot[(int64_t)(c0 + e) * f.width + src] = dw[j][e];
+            }
+            slot[(int64_t)f.dim * f.width + c0 + e] = db[e];
+        }
+        return;
+    }
 #pragma unroll
     for (int e = 0; e < E; ++e) {
         if (e >= nv) continue;
@@ -190,6 +206,21 @@ bool conv_cl_fwd_dispatch(const vivim_conv_fwd_params& p, hipStream_t s) {
         case VIVIM_F32:  hipLaunchKernelGGL((conv1d_cl_fwd_kernel<float, kClE>), grid, block, 0, s, p, g); return true;
         case VIVIM_F16:  hipLaunchKernelGGL((conv1d_cl_fwd_kernel<f16_t, kClE>), grid, block, 0, s, p, g); return true;
         case VIVIM_BF16: hipLaunchKernelGGL((conv1d_cl_fwd_kernel<bf16_t, kClE>), grid, block, 0, s, p, g); return true;
+    }
+    return false;
+}
+
+size_t conv_cl_bwd_det_slots(const vivim_conv_fwd_params& f) {
+    const ClGeom g = cl_geometry(f);
+    return (size_t)f.batch * g.nchunk;
+}
+bool conv_cl_bwd_det_launch(const vivim_conv_bwd_params& p, hipStream_t s) {
+    const ClGeom g = cl_geometry(p.f);
+    const dim3 grid(cl_blocks(p.f, g)), block(kClThreads);
+    switch (p.f.itype) {
+        case VIVIM_F32:  hipLaunchKernelGGL((conv1d_cl_bwd_kernel<float, kClE, true>), grid, block, 0, s, p, g); return true;
+        case VIVIM_F16:  hipLaunchKernelGGL((conv1d_cl_bwd_kernel<f16_t, kClE, true>), grid, block, 0, s, p, g); return true;
+        case VIVIM_BF16: hipLaunchKernelGGL((conv1d_cl_bwd_kernel<bf16_t, kClE, true>), grid, block, 0, s, p, g); return true;
     }
     return false;
 }

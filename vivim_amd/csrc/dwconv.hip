@@ -11,7 +11,7 @@
 // TW = 4 consecutive w positions: every load is a 16-byte vector, 8 neighbouring lanes cover 128 contiguous
 // bytes of one token, each loaded input vector feeds up to 3 of the 4 outputs, taps live in LDS as fp32.
 // Memory-bound: 2*s bytes per element forward (the 27x neighbour re-reads are L1/L2 hits).
-#include "common.cuh"
+#include "det.cuh"
 
 namespace vivim {
 
@@ -106,7 +106,9 @@ __global__ void __launch_bounds__(kDwThreads) dwconv_fwd_kernel(const vivim_dwco
 // A lane owns 2 consecutive channels (a wave: 128 contiguous channels of a token) and keeps all TAPS x 2
 // partial sums in registers while it walks its share of the (d, h, w-tile) tiles; the 4 waves of a block are
 // summed through LDS, then one fp32 atomic per (tap, channel) and block.
-template <typename T, int KD>
+// DET (vivim_dwconv_wgrad_det): the block stores its sums instead, into slot (batch, blockIdx.x) of p.dwt = the
+// workspace: a slot is (TAPS + 1) x channels floats, dbias last.
+template <typename T, int KD, bool DET = false>
 __global__ void __launch_bounds__(kDwThreads) dwconv_wgrad_kernel(const vivim_dwconv_wgrad_params p, const int tiles_per_wave) {
     constexpr int CP = 2;
     constexpr int TAPS = KD * 9;
@@ -198,7 +200,9 @@ __global__ void __launch_bounds__(kDwThreads) dwconv_wgrad_kernel(const vivim_dw
         for (int wv = 0; wv < kDwThreads / kWave; ++wv) s += red[wv * (TAPS + 1) * CP * kWave + i];
         const int ln = i & 63, cp = (i >> 6) & 1, t = i >> 7;
         const int cc = blockIdx.y * (kWave * CP) + ln * CP + cp;
-        if (cc < C) {
+        if (DET) {
+            if (cc < C) dwt[((int64_t)blockIdx.z * gridDim.x + blockIdx.x) * (TAPS + 1) * C + (int64_t)t * C + cc] = s;
+        } else if (cc < C) {
             if (t < TAPS) atomicAdd(dwt + (int64_t)t * C + cc, s);
             else if (p.dbias) atomicAdd(static_cast<float*>(p.dbias) + cc, s);
         }
@@ -230,8 +234,8 @@ static bool dw_fwd(const vivim_dwconv_params& p, hipStream_t s) {
     }
     return true;
 }
-template <typename T>
-static bool dw_wgrad(const vivim_dwconv_wgrad_params& p, hipStream_t s) {
+// Grid of the weight-gradient kernel: (blocks_x, channel groups, batch) and tiles per wave.
+static dim3 dw_wgrad_grid(const vivim_dwconv_wgrad_params& p, int& tpw_out) {
     const int wtiles = (p.width + kDwTW - 1) / kDwTW;
     const int ntiles = p.depth * p.height * wtiles;
     const int cgroups = (p.channels + 127) / 128;
@@ -240,10 +244,44 @@ static bool dw_wgrad(const vivim_dwconv_wgrad_params& p, hipStream_t s) {
     int tpw = (ntiles + blocks_x * 4 - 1) / (blocks_x * 4);
     if (tpw < 8) tpw = 8;
     blocks_x = (ntiles + tpw * 4 - 1) / (tpw * 4);
-    dim3 grid(blocks_x, cgroups, p.batch);
-    if (p.kd == 3) hipLaunchKernelGGL((dwconv_wgrad_kernel<T, 3>), grid, dim3(kDwThreads), 0, s, p, tpw);
-    else           hipLaunchKernelGGL((dwconv_wgrad_kernel<T, 1>), grid, dim3(kDwThreads), 0, s, p, tpw);
+    tpw_out = tpw;
+    return dim3(blocks_x, cgroups, p.batch);
+}
+template <typename T, bool DET>
+static bool dw_wgrad(const vivim_dwconv_wgrad_params& p, hipStream_t s) {
+    int tpw = 0;
+    const dim3 grid = dw_wgrad_grid(p, tpw);
+    if (p.kd == 3) hipLaunchKernelGGL((dwconv_wgrad_kernel<T, 3, DET>), grid, dim3(kDwThreads), 0, s, p, tpw);
+    else           hipLaunchKernelGGL((dwconv_wgrad_kernel<T, 1, DET>), grid, dim3(kDwThreads), 0, s, p, tpw);
     return true;
+}
+
+// vivim_dwconv_wgrad_det: batch * blocks_x slots of (kd * 9 + 1) * channels floats.
+size_t dwconv_wgrad_det_workspace_bytes(const vivim_dwconv_wgrad_params& p) {
+    int tpw = 0;
+    const dim3 g = dw_wgrad_grid(p, tpw);
+    return sizeof(float) * (size_t)g.x * g.z * (size_t)(p.kd * 9 + 1) * p.channels;
+}
+// 0 launched, 1 type not built, 2 workspace missing / too small / misaligned (nothing launched).
+int dwconv_wgrad_det_dispatch(const vivim_dwconv_wgrad_params& p, void* ws, size_t bytes, hipStream_t s) {
+    if (ws == nullptr || bytes < dwconv_wgrad_det_workspace_bytes(p) || reinterpret_cast<uintptr_t>(ws) % 16 != 0) return 2;
+    vivim_dwconv_wgrad_params d = p;
+    d.dwt = ws;
+    bool ok = false;
+    switch (p.itype) {
+        case VIVIM_F32: ok = dw_wgrad<float, true>(d, s); break;
+        case VIVIM_F16: ok = dw_wgrad<f16_t, true>(d, s); break;
+        case VIVIM_BF16: ok = dw_wgrad<bf16_t, true>(d, s); break;
+    }
+    if (!ok) return 1;
+    int tpw = 0;
+    const dim3 g = dw_wgrad_grid(p, tpw);
+    const int taps = p.kd * 9, C = p.channels;
+    const int64_t sstride = (int64_t)(taps + 1) * C;
+    det_reduce(static_cast<const float*>(ws), (int)(g.x * g.z), det_out(static_cast<float*>(p.dwt), {taps, C}, {C, 1}), s, sstride);
+    if (p.dbias)
+        det_reduce(static_cast<const float*>(ws) + (int64_t)taps * C, (int)(g.x * g.z), det_out(static_cast<float*>(p.dbias), {C}, {1}), s, sstride);
+    return 0;
 }
 
 bool dwconv_fwd_dispatch(const vivim_dwconv_params& p, hipStream_t s) {
@@ -256,9 +294,9 @@ bool dwconv_fwd_dispatch(const vivim_dwconv_params& p, hipStream_t s) {
 }
 bool dwconv_wgrad_dispatch(const vivim_dwconv_wgrad_params& p, hipStream_t s) {
     switch (p.itype) {
-        case VIVIM_F32: return dw_wgrad<float>(p, s);
-        case VIVIM_F16: return dw_wgrad<f16_t>(p, s);
-        case VIVIM_BF16: return dw_wgrad<bf16_t>(p, s);
+        case VIVIM_F32: return dw_wgrad<float, false>(p, s);
+        case VIVIM_F16: return dw_wgrad<f16_t, false>(p, s);
+        case VIVIM_BF16: return dw_wgrad<bf16_t, false>(p, s);
     }
     return false;
 }

@@ -20,7 +20,11 @@ namespace vivim {
 
 constexpr int kBwdWaves = 4;
 
-template <typename T, int K, int R, bool HAS_Z, bool VAR_BC>
+// DET (vivim_selective_scan_bwd_det): p's dA / dD / ddelta_bias / dB / dC point into the slot workspace (scan_plan.hip,
+// scan_det_layout); every cross-workgroup add becomes a plain store into the slot of this workgroup's coordinates: batch
+// for dA / dD / dbias and constant dB / dC (whose per-step adds are first folded in wave-private LDS), channel set within
+// the group for variable dB / dC.
+template <typename T, int K, int R, bool HAS_Z, bool VAR_BC, bool DET = false>
 __global__ void __launch_bounds__(kBwdWaves * kWave) ssm_bwd_generic_kernel(const vivim_ssm_bwd_params p, const int ck) {
     constexpr int TILE = kWave * K;
     const vivim_ssm_fwd_params& f = p.f;
@@ -37,10 +41,16 @@ __global__ void __launch_bounds__(kBwdWaves * kWave) ssm_bwd_generic_kernel(cons
     const int nvalid = min(R, (g + 1) * cpg - d0);
 
     extern __shared__ __attribute__((aligned(16))) float smem[];
-    float* gcarry = smem + wave * 3 * R * N;          // g at the first token of the step to the right
+    constexpr bool FOLD_BC = DET && !VAR_BC;          // constant dB / dC summed over the steps in LDS
+    float* gcarry = smem + wave * (FOLD_BC ? 5 : 3) * R * N;   // g at the first token of the step to the right
     float* afirst = gcarry + R * N;                   // a at the first token of the step to the right
     float* dAacc = afirst + R * N;                    // running dA[r][n] of this wave
-    for (int i = lane; i < R * N; i += kWave) { gcarry[i] = 0.0f; afirst[i] = 1.0f; dAacc[i] = 0.0f; }
+    float* dBacc = dAacc + R * N;                     // FOLD_BC: running dB[r][n], dC[r][n] of this wave
+    float* dCacc = dBacc + R * N;
+    for (int i = lane; i < R * N; i += kWave) {
+        gcarry[i] = 0.0f; afirst[i] = 1.0f; dAacc[i] = 0.0f;
+        if (FOLD_BC) { dBacc[i] = 0.0f; dCacc[i] = 0.0f; }
+    }
     wave_lds_fence();
 
     int d[R];
@@ -190,20 +200,26 @@ __global__ void __launch_bounds__(kBwdWaves * kWave) ssm_bwd_generic_kernel(cons
                     sB = wave_sum(sB);
                     sC = wave_sum(sC);
                     if (lane == 0) {
-                        atomicAdd(dBg + d[r] * p.dB_group_stride + n * p.dB_dstate_stride, sB);
-                        atomicAdd(dCg + d[r] * p.dC_group_stride + n * p.dC_dstate_stride, sC);
+                        if (FOLD_BC) {                            // wave-private, steps in order
+                            dBacc[r * N + n] += sB;
+                            dCacc[r * N + n] += sC;
+                        } else {
+                            atomicAdd(dBg + d[r] * p.dB_group_stride + n * p.dB_dstate_stride, sB);
+                            atomicAdd(dCg + d[r] * p.dC_group_stride + n * p.dC_dstate_stride, sC);
+                        }
                     }
                 }
                 if (VAR_BC && r >= nvalid - 1) break;             // shadow slots must not count twice
             }
             if (VAR_BC) {
-                float* dBp = dBg + b * p.dB_batch_stride + g * p.dB_group_stride + n * p.dB_dstate_stride + t0;
-                float* dCp = dCg + b * p.dC_batch_stride + g * p.dC_group_stride + n * p.dC_dstate_stride + t0;
+                const int64_t slot = DET ? (int64_t)(ws - g * wpg) * f.batch * f.n_groups * N * L : 0;
+                float* dBp = dBg + slot + b * p.dB_batch_stride + g * p.dB_group_stride + n * p.dB_dstate_stride + t0;
+                float* dCp = dCg + slot + b * p.dC_batch_stride + g * p.dC_group_stride + n * p.dC_dstate_stride + t0;
 #pragma unroll
                 for (int k = 0; k < K; ++k) {
                     if (k < nv) {
-                        atomicAdd(dBp + k, dBv[k]);               // fp32 sum over channel sets (bwd_kernel.cuh:312-313)
-                        atomicAdd(dCp + k, dCv[k]);
+                        det_add<DET>(dBp + k, dBv[k]);            // fp32 sum over channel sets (bwd_kernel.cuh:312-313)
+                        det_add<DET>(dCp + k, dCv[k]);
                     }
                 }
             }
@@ -232,14 +248,20 @@ __global__ void __launch_bounds__(kBwdWaves * kWave) ssm_bwd_generic_kernel(cons
         const float sD = wave_sum(dD_acc[r]);
         const float sb = wave_sum(dbias_acc[r]);
         if (lane == 0) {
-            if (p.dD) atomicAdd(static_cast<float*>(p.dD) + d[r], sD);
-            if (p.ddelta_bias) atomicAdd(static_cast<float*>(p.ddelta_bias) + d[r], sb);
+            const int64_t slot = DET ? (int64_t)b * f.dim : 0;
+            if (p.dD) det_add<DET>(static_cast<float*>(p.dD) + slot + d[r], sD);
+            if (p.ddelta_bias) det_add<DET>(static_cast<float*>(p.ddelta_bias) + slot + d[r], sb);
         }
     }
     wave_lds_fence();
+    const int64_t slotA = DET ? (int64_t)b * f.dim * N : 0;
     for (int i = lane; i < nvalid * N; i += kWave) {
         const int r = i / N, n = i - r * N;
-        atomicAdd(static_cast<float*>(p.dA) + (d0 + r) * p.dA_d_stride + n * p.dA_dstate_stride, dAacc[i]);
+        det_add<DET>(static_cast<float*>(p.dA) + slotA + (d0 + r) * p.dA_d_stride + n * p.dA_dstate_stride, dAacc[i]);
+        if (FOLD_BC) {
+            dBg[slotA + (d0 + r) * p.dB_group_stride + n * p.dB_dstate_stride] = dBacc[i];
+            dCg[slotA + (d0 + r) * p.dC_group_stride + n * p.dC_dstate_stride] = dCacc[i];
+        }
     }
 }
 
@@ -283,8 +305,11 @@ template <int CTRL> __device__ __forceinline__ f2 dpp_mov2(f2 old, f2 src) {
 // The backward of one segment of the token axis (the whole sequence when S == 1).
 // DA_LDS (N <= 16): dA partial sums stay per lane in LDS and are reduced over the lanes once per segment, instead of
 // one wave reduction per (state, channel) and step.
-template <typename T, int K, bool HAS_Z, int W, bool DA_LDS>
-__global__ void __launch_bounds__(W * kWave, (K == 4 && W == 4) ? 3 : 2) ssm_bwd_fast_kernel(const vivim_ssm_bwd_params p, const BwdSeg sg) {
+// DET (vivim_selective_scan_bwd_det): stores into the slot workspace instead of adds; the slot of dA / dD / dbias is
+// (batch, segment), the slot of dB / dC is the workgroup's index within its B/C group.
+template <typename T, int K, bool HAS_Z, int W, bool DA_LDS, bool DET = false>
+// (DET at K = 8: one 4-wave workgroup per CU -- the two-wave build sits at 256 VGPRs and the slot stores would spill)
+__global__ void __launch_bounds__(W * kWave, (K == 4 && W == 4) ? 3 : (DET && K == 8 ? 1 : 2)) ssm_bwd_fast_kernel(const vivim_ssm_bwd_params p, const BwdSeg sg) {
     constexpr int R = kBwR;
     static_assert(R == 2, "the state loop is written on channel pairs");
     constexpr int TILE = kWave * K;
@@ -366,8 +391,10 @@ __global__ void __launch_bounds__(W * kWave, (K == 4 && W == 4) ? 3 : 2) ssm_bwd
     const T* __restrict__ oB = HAS_Z ? static_cast<const T*>(f.out) + b * f.out_batch_stride : nullptr;
     const T* __restrict__ Bv = static_cast<const T*>(f.B) + b * f.B_batch_stride + g * f.B_group_stride;
     const T* __restrict__ Cv = static_cast<const T*>(f.C) + b * f.C_batch_stride + g * f.C_group_stride;
-    float* __restrict__ dBg = static_cast<float*>(p.dB) + b * p.dB_batch_stride + g * p.dB_group_stride;
-    float* __restrict__ dCg = static_cast<float*>(p.dC) + b * p.dC_batch_stride + g * p.dC_group_stride;
+    // DET: this workgroup's dB / dC slot (slots of batch * n_groups * dstate * seqlen floats)
+    const int64_t bc_slot = DET ? (int64_t)(blockIdx.x - g * bpg) * f.batch * f.n_groups * N * L : 0;
+    float* __restrict__ dBg = static_cast<float*>(p.dB) + bc_slot + b * p.dB_batch_stride + g * p.dB_group_stride;
+    float* __restrict__ dCg = static_cast<float*>(p.dC) + bc_slot + b * p.dC_batch_stride + g * p.dC_group_stride;
     const float* __restrict__ xck = static_cast<const float*>(f.x);
 
     for (int step = s_hi - 1; step >= s_lo; --step) {
@@ -544,6 +571,10 @@ __global__ void __launch_bounds__(W * kWave, (K == 4 && W == 4) ? 3 : 2) ssm_bwd
                     // carry acc == 0 (their dy and delta*u are 0) and are wrapped onto distinct valid tokens.
                     const int tq = step * TILE + e_tok;
                     const int t = tq < L ? tq : tq % L;
+                    if (DET) {                                    // one store per (slot, token); nothing past the end
+                        if (tq < L) (e_isC ? dCg + n * p.dC_dstate_stride : dBg + n * p.dB_dstate_stride)[tq] = acc;
+                        continue;
+                    }
 #if defined(BW_ABL) && BW_ABL == 1               // timing experiment (tools/abl.sh bwdbuild): no dB / dC atomics -- wrong results
                     asm volatile("" : : "v"(acc), "v"(t));
 #else
@@ -588,8 +619,9 @@ __global__ void __launch_bounds__(W * kWave, (K == 4 && W == 4) ? 3 : 2) ssm_bwd
             const float sD = wave_sum(dD_acc[r]);
             const float sb = wave_sum(dbias_acc[r]);
             if (lane == 0) {
-                if (p.dD) atomicAdd(static_cast<float*>(p.dD) + d[r], sD);
-                if (p.ddelta_bias) atomicAdd(static_cast<float*>(p.ddelta_bias) + d[r], sb);
+                const int64_t slot = DET ? (int64_t)(b * gridDim.z + seg) * f.dim : 0;
+                if (p.dD) det_add<DET>(static_cast<float*>(p.dD) + slot + d[r], sD);
+                if (p.ddelta_bias) det_add<DET>(static_cast<float*>(p.ddelta_bias) + slot + d[r], sb);
             }
         }
         wave_lds_fence();
@@ -602,7 +634,8 @@ __global__ void __launch_bounds__(W * kWave, (K == 4 && W == 4) ? 3 : 2) ssm_bwd
                 for (int j = 0; j < kWave; ++j) tot += q[j * R];
             }
             if (r < nvalid)
-                atomicAdd(static_cast<float*>(p.dA) + (d0 + r) * p.dA_d_stride + n * p.dA_dstate_stride, tot);
+                det_add<DET>(static_cast<float*>(p.dA) + (DET ? (int64_t)(b * gridDim.z + seg) * f.dim * N : 0) +
+                             (d0 + r) * p.dA_d_stride + n * p.dA_dstate_stride, tot);
         }
     }
 #undef VIVIM_REC
@@ -850,7 +883,7 @@ void launch_bwd_closed_prepass(const vivim_ssm_bwd_params& p, const LsSeg& ls, i
     });
 }
 
-template <typename T, int K, int W>
+template <typename T, int K, int W, bool DET>
 static void launch_bwd_fast_kw(const vivim_ssm_bwd_params& p, const BwdPlan& q, hipStream_t stream) {
     const vivim_ssm_fwd_params& f = p.f;
     const int ppg = (f.dim / f.n_groups + kBwR - 1) / kBwR;
@@ -873,8 +906,8 @@ static void launch_bwd_fast_kw(const vivim_ssm_bwd_params& p, const BwdPlan& q, 
         allow_smem(kernel, smem);
         hipLaunchKernelGGL(kernel, grid, block, smem, stream, p, sg);
     };
-    if (f.z) { if (q.da_lds) launch(ssm_bwd_fast_kernel<T, K, true, W, true>); else launch(ssm_bwd_fast_kernel<T, K, true, W, false>); }
-    else     { if (q.da_lds) launch(ssm_bwd_fast_kernel<T, K, false, W, true>); else launch(ssm_bwd_fast_kernel<T, K, false, W, false>); }
+    if (f.z) { if (q.da_lds) launch(ssm_bwd_fast_kernel<T, K, true, W, true, DET>); else launch(ssm_bwd_fast_kernel<T, K, true, W, false, DET>); }
+    else     { if (q.da_lds) launch(ssm_bwd_fast_kernel<T, K, false, W, true, DET>); else launch(ssm_bwd_fast_kernel<T, K, false, W, false, DET>); }
 }
 
 // Two waves per SIMD (__launch_bounds__(W * 64, 2)): registers uncapped (144-152 VGPRs at K = 4, 229-248 at K = 8; one
@@ -884,31 +917,44 @@ static void launch_bwd_fast_kw(const vivim_ssm_bwd_params& p, const BwdPlan& q, 
 // restores EXEC: the store then runs with EXEC = 0, nothing is saved, and the reload returns garbage (seen as
 // wrong gradients and a GPU memory fault in fp32 once an unrelated edit changed the allocation).  No kernel
 // of this library may use scratch: `make check-scratch` (part of the default build) enforces it.
-void launch_bwd_fast(const vivim_ssm_bwd_params& p, const BwdPlan& q, hipStream_t stream) {
+template <bool DET>
+static void launch_bwd_fast_t(const vivim_ssm_bwd_params& p, const BwdPlan& q, hipStream_t stream) {
     with_itype(p.f.itype, [&](auto t) {
         typedef decltype(t) T;
-        if (q.K == 8) { if (q.W == 4) launch_bwd_fast_kw<T, 8, 4>(p, q, stream); else launch_bwd_fast_kw<T, 8, kBwWmax>(p, q, stream); }
-        else          { if (q.W == 4) launch_bwd_fast_kw<T, 4, 4>(p, q, stream); else launch_bwd_fast_kw<T, 4, kBwWmax>(p, q, stream); }
+        // (DET at K = 8 runs 4-wave workgroups only: the 8-wave build would spill, see ssm_bwd_det_dispatch)
+        if (q.K == 8) {
+            if constexpr (DET) launch_bwd_fast_kw<T, 8, 4, DET>(p, q, stream);
+            else if (q.W == 4) launch_bwd_fast_kw<T, 8, 4, DET>(p, q, stream);
+            else               launch_bwd_fast_kw<T, 8, kBwWmax, DET>(p, q, stream);
+        }
+        else          { if (q.W == 4) launch_bwd_fast_kw<T, 4, 4, DET>(p, q, stream); else launch_bwd_fast_kw<T, 4, kBwWmax, DET>(p, q, stream); }
     });
 }
+void launch_bwd_fast(const vivim_ssm_bwd_params& p, const BwdPlan& q, hipStream_t stream, bool det) {
+    if (det) launch_bwd_fast_t<true>(p, q, stream); else launch_bwd_fast_t<false>(p, q, stream);
+}
 
-void launch_bwd_generic(const vivim_ssm_bwd_params& p, int ck, hipStream_t stream) {
-    constexpr int K = 4, R = 2;
+template <bool DET>
+static void launch_bwd_generic_t(const vivim_ssm_bwd_params& p, int ck, hipStream_t stream) {
+    constexpr int K = 4, R = kBwdGenR;
     const vivim_ssm_fwd_params& f = p.f;
     const int sets = ((f.dim / f.n_groups + R - 1) / R) * f.n_groups;
     const dim3 grid((sets + kBwdWaves - 1) / kBwdWaves, f.batch), block(kBwdWaves * kWave);
-    const size_t smem = (size_t)kBwdWaves * 3 * R * f.dstate * sizeof(float);
     const bool var = f.is_variable_B;
+    const size_t smem = (size_t)kBwdWaves * (DET && !var ? 5 : 3) * R * f.dstate * sizeof(float);
     with_itype(f.itype, [&](auto t) {
         typedef decltype(t) T;
         if (f.z) {
-            if (var) hipLaunchKernelGGL((ssm_bwd_generic_kernel<T, K, R, true, true>), grid, block, smem, stream, p, ck);
-            else     hipLaunchKernelGGL((ssm_bwd_generic_kernel<T, K, R, true, false>), grid, block, smem, stream, p, ck);
+            if (var) hipLaunchKernelGGL((ssm_bwd_generic_kernel<T, K, R, true, true, DET>), grid, block, smem, stream, p, ck);
+            else     hipLaunchKernelGGL((ssm_bwd_generic_kernel<T, K, R, true, false, DET>), grid, block, smem, stream, p, ck);
         } else {
-            if (var) hipLaunchKernelGGL((ssm_bwd_generic_kernel<T, K, R, false, true>), grid, block, smem, stream, p, ck);
-            else     hipLaunchKernelGGL((ssm_bwd_generic_kernel<T, K, R, false, false>), grid, block, smem, stream, p, ck);
+            if (var) hipLaunchKernelGGL((ssm_bwd_generic_kernel<T, K, R, false, true, DET>), grid, block, smem, stream, p, ck);
+            else     hipLaunchKernelGGL((ssm_bwd_generic_kernel<T, K, R, false, false, DET>), grid, block, smem, stream, p, ck);
         }
     });
+}
+void launch_bwd_generic(const vivim_ssm_bwd_params& p, int ck, hipStream_t stream, bool det) {
+    if (det) launch_bwd_generic_t<true>(p, ck, stream); else launch_bwd_generic_t<false>(p, ck, stream);
 }
 
 }  // namespace vivim

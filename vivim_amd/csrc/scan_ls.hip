@@ -45,7 +45,10 @@ namespace vivim {
 #define LS_ABL 0
 #endif
 constexpr int kAbl = LS_ABL;
-template <typename T, int NS, bool HAS_Z>
+// DET (vivim_selective_scan_bwd_det): dA / dD / dbias are stored into the (batch, segment) slot of the workspace p points
+// them at.  dB / dC keep their adds while a group has at most two workgroups (0 + a + b == 0 + b + a exactly); with
+// more, p's dB / dC point into the workspace too and the workgroup's index within its group is the slot.
+template <typename T, int NS, bool HAS_Z, bool DET = false>
 __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(kAbl == 8 ? 4 : (NS == 16 ? 3 : 2), kAbl == 8 ? 4 : 3))) ssm_ls_bwd_kernel(const vivim_ssm_bwd_params p, const LsSeg sg) {
     typedef LsGeom<NS> G;
     constexpr int RPS = G::RPS, SPW = G::SPW, CPW = G::CPW, CPR = kLsCPR;
@@ -337,6 +340,7 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(kAbl =
                 if (t0 + ek < L) {
                     float* dst = isC ? dCg + en * dCns : dBg + en * dBns;
                     if (single) dst[t0 + ek] = acc;                   // the only contributor: plain store, deterministic
+                    else if (DET && bpg > 2) dst[(int64_t)(blockIdx.x - g * bpg) * f.batch * f.n_groups * NS * L + t0 + ek] = acc;
                     else atomicAdd(dst + t0 + ek, acc);               // two workgroups: still order-independent (a + b)
                 }
             }
@@ -349,10 +353,11 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(kAbl =
         const float* cs = cstate + c * NF * kWave;
         const float sD = ls_row_total(cs[DDACC * kWave]), sb = ls_row_total(cs[DBIAS * kWave]);
         if (d >= d_end) continue;                             // uniform per row
-        atomicAdd(static_cast<float*>(p.dA) + d * p.dA_d_stride + n * p.dA_dstate_stride, cs[DACC * kWave]);
+        const int64_t dslot = DET ? (int64_t)(b * gridDim.z + seg) * f.dim : 0;
+        det_add<DET>(static_cast<float*>(p.dA) + dslot * NS + d * p.dA_d_stride + n * p.dA_dstate_stride, cs[DACC * kWave]);
         if (li == 0 && rs == 0) {
-            if (p.dD) atomicAdd(static_cast<float*>(p.dD) + d, sD);
-            if (p.ddelta_bias) atomicAdd(static_cast<float*>(p.ddelta_bias) + d, sb);
+            if (p.dD) det_add<DET>(static_cast<float*>(p.dD) + dslot + d, sD);
+            if (p.ddelta_bias) det_add<DET>(static_cast<float*>(p.ddelta_bias) + dslot + d, sb);
         }
     }
 }
@@ -707,7 +712,7 @@ static LsSeg ls_seg(void* ws, const vivim_ssm_fwd_params& f, int S, int seg_bloc
 
 // Segmented: the pre-pass (recurrence form, or the lanes = tokens closed form the plan picked) + carry; then the main kernel
 // of the plan's generation.
-void launch_ls_bwd(const vivim_ssm_bwd_params& p, const BwdPlan& q, hipStream_t stream) {
+void launch_ls_bwd(const vivim_ssm_bwd_params& p, const BwdPlan& q, hipStream_t stream, bool det) {
     const vivim_ssm_fwd_params& f = p.f;
     const LsSeg sg = ls_seg(p.workspace, f, q.S, q.seg, q.bc_vec, scan_env().ls_dbg);
     const int cpg = f.dim / f.n_groups;
@@ -734,10 +739,10 @@ void launch_ls_bwd(const vivim_ssm_bwd_params& p, const BwdPlan& q, hipStream_t 
             allow_smem(kernel, smem);
             hipLaunchKernelGGL(kernel, grid, dim3(q.W * kWave), smem, stream, p, sg);
         };
-        if (f.z) launch(ssm_ls_bwd_kernel<T, NS, true>);
-        else     launch(ssm_ls_bwd_kernel<T, NS, false>);
+        if (det) { if (f.z) launch(ssm_ls_bwd_kernel<T, NS, true, true>); else launch(ssm_ls_bwd_kernel<T, NS, false, true>); }
+        else     { if (f.z) launch(ssm_ls_bwd_kernel<T, NS, true>);       else launch(ssm_ls_bwd_kernel<T, NS, false>); }
     });
-    if (q.ls2) launch_ls2_bwd(p, sg, q.W, stream);
+    if (q.ls2) launch_ls2_bwd(p, sg, q.W, stream, det);
 }
 
 void launch_ls_fwd(const vivim_ssm_fwd_params& p, const FwdPlan& q, hipStream_t stream) {

@@ -146,7 +146,8 @@ constexpr int kAbl2 = LS2_ABL;       // timing experiments only (tools/abl.sh ls
 // token needs that does not depend on the scan (softplus, the z gate, dz, the sigmoid factor of ddelta) is done at SPAN
 // level, where a lane holds EPV consecutive tokens of one channel and their dependency chains interleave -- in-kernel
 // stamps of the first build had a step spend 1000 + 600 cycles of pure latency in these chains against 2700 in the sweeps.
-template <typename T, bool HAS_Z>
+// DET (vivim_selective_scan_bwd_det): as in scan_ls.hip's ssm_ls_bwd_kernel.
+template <typename T, bool HAS_Z, bool DET = false>
 __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) ssm_ls2_bwd_kernel(const vivim_ssm_bwd_params p, const LsSeg sg) {
     typedef Ls2Geom<T> G2;
     typedef Ls2Piece<T> PK;
@@ -519,7 +520,8 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))
                     if (t0 + ek < L) {
                         float* dst = isC ? dCg + en * dCns : dBg + en * dBns;
                         if (single) dst[t0 + ek] = acc;                   // the only contributor: plain store, deterministic
-                        else atomicAdd(dst + t0 + ek, acc);
+                        else if (DET && bpg > 2) dst[(int64_t)(blockIdx.x - g * bpg) * f.batch * f.n_groups * NS * L + t0 + ek] = acc;
+                        else atomicAdd(dst + t0 + ek, acc);           // two workgroups: 0 + a + b == 0 + b + a
                     }
                 };
                 if (W == 4) {                                 // two outputs per thread, their eight slot reads in flight together
@@ -551,7 +553,8 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))
     for (int c = 0; c < CPR; ++c) {
         const int d = dwave + rowch + c;
         if (d >= d_end) continue;                             // uniform per row
-        atomicAdd(static_cast<float*>(p.dA) + d * p.dA_d_stride + n * p.dA_dstate_stride, dacc[c]);
+        det_add<DET>(static_cast<float*>(p.dA) + (DET ? (int64_t)(b * gridDim.z + seg) * f.dim * NS : 0) +
+                     d * p.dA_d_stride + n * p.dA_dstate_stride, dacc[c]);
     }
 #pragma unroll
     for (int i = 0; i < 2; ++i) {                             // dD, dbias: the eight lanes that share a channel at span level
@@ -561,8 +564,9 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))
         sD += dpp_mov<0x141>(0.0f, sD);  sBs += dpp_mov<0x141>(0.0f, sBs);     // lane ^ 7 (row_half_mirror): the other quad
         const int d = dwave + (lane >> 3) + 8 * i;
         if ((lane & 7) == 0 && d < d_end) {
-            if (p.dD) atomicAdd(static_cast<float*>(p.dD) + d, sD);
-            if (p.ddelta_bias) atomicAdd(static_cast<float*>(p.ddelta_bias) + d, sBs);
+            const int64_t dslot = DET ? (int64_t)(b * gridDim.z + seg) * f.dim : 0;
+            if (p.dD) det_add<DET>(static_cast<float*>(p.dD) + dslot + d, sD);
+            if (p.ddelta_bias) det_add<DET>(static_cast<float*>(p.ddelta_bias) + dslot + d, sBs);
         }
     }
 }
@@ -578,7 +582,7 @@ static size_t ls2_bwd_smem(int W, int itype) {
 
 // Same workgroup geometry as the first generation; the plan (scan_plan.hip) has checked that every activation row is
 // 16-byte aligned and a whole number of 16-byte pieces long.
-void launch_ls2_bwd(const vivim_ssm_bwd_params& p, const LsSeg& sg, int W, hipStream_t stream) {
+void launch_ls2_bwd(const vivim_ssm_bwd_params& p, const LsSeg& sg, int W, hipStream_t stream, bool det) {
     const vivim_ssm_fwd_params& f = p.f;
     const int cpg = f.dim / f.n_groups;
     const int cpb = W * 4 * kLsCPR;
@@ -591,7 +595,8 @@ void launch_ls2_bwd(const vivim_ssm_bwd_params& p, const LsSeg& sg, int W, hipSt
     };
     with_itype(f.itype, [&](auto t) {
         typedef decltype(t) T;
-        if (f.z) launch(ssm_ls2_bwd_kernel<T, true>); else launch(ssm_ls2_bwd_kernel<T, false>);
+        if (det) { if (f.z) launch(ssm_ls2_bwd_kernel<T, true, true>); else launch(ssm_ls2_bwd_kernel<T, false, true>); }
+        else     { if (f.z) launch(ssm_ls2_bwd_kernel<T, true>);       else launch(ssm_ls2_bwd_kernel<T, false>); }
     });
 }
 

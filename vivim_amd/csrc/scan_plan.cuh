@@ -7,6 +7,7 @@
 #pragma once
 #include <initializer_list>
 #include "ls_common.cuh"
+#include "det.cuh"
 
 namespace vivim {
 
@@ -21,6 +22,7 @@ constexpr int kNsR = 2;            // n-split forward: channels per workgroup
 constexpr int kChWaves = 2;        // lanes = channels forward: independent waves per workgroup
 constexpr int kBwWmax = 8;         // lanes = tokens backward: waves per workgroup, 8 or 4 (template parameter W of the fast kernel)
 constexpr int kBwR = 2;            // lanes = tokens backward: channels per wave
+constexpr int kBwdGenR = 2;        // generic backward: channels per wave
 
 // Lanes = channels forward, tokens per tile: a tile row is ONE 128-byte line for every I/O type (32 fp32 / 64 16-bit tokens).
 // With 32-byte pieces (16 tokens of bf16, the first version) a line of a row was fetched for four separate tiles,
@@ -95,10 +97,11 @@ void launch_fwd_nsplit(const vivim_ssm_fwd_params&, const FwdPlan&, hipStream_t)
 void launch_fwd_generic(const vivim_ssm_fwd_params&, hipStream_t);
 void launch_fwd_chan(const vivim_ssm_fwd_params&, const FwdPlan&, hipStream_t);       // scan_fwd_chan.hip
 void launch_ls_fwd(const vivim_ssm_fwd_params&, const FwdPlan&, hipStream_t);         // scan_ls.hip
-void launch_ls_bwd(const vivim_ssm_bwd_params&, const BwdPlan&, hipStream_t);
-void launch_ls2_bwd(const vivim_ssm_bwd_params&, const LsSeg&, int W, hipStream_t);   // scan_ls2.hip
-void launch_bwd_fast(const vivim_ssm_bwd_params&, const BwdPlan&, hipStream_t);       // scan_bwd.hip
-void launch_bwd_generic(const vivim_ssm_bwd_params&, int ck, hipStream_t);
+// `det`: the deterministic variant (scan_det_layout in scan_plan.hip), with p's reduced outputs pointing into the slot workspace.
+void launch_ls_bwd(const vivim_ssm_bwd_params&, const BwdPlan&, hipStream_t, bool det = false);
+void launch_ls2_bwd(const vivim_ssm_bwd_params&, const LsSeg&, int W, hipStream_t, bool det = false);   // scan_ls2.hip
+void launch_bwd_fast(const vivim_ssm_bwd_params&, const BwdPlan&, hipStream_t, bool det = false);       // scan_bwd.hip
+void launch_bwd_generic(const vivim_ssm_bwd_params&, int ck, hipStream_t, bool det = false);
 void launch_bwd_closed_prepass(const vivim_ssm_bwd_params&, const LsSeg&, int K, hipStream_t);
 // Raw occupancy of the lanes = states backward main kernel `f` selects (first / second generation); cached by the planner.
 int ls_bwd_occupancy(const vivim_ssm_fwd_params& f, int W);                            // scan_ls.hip

@@ -1,5 +1,6 @@
 // scan_plan.hip -- which selective-scan kernels run, on what cut of the token axis, with how much workspace (scan_plan.cuh).
 #include <stdlib.h>
+#include <algorithm>
 #include <atomic>
 #include "scan_plan.cuh"
 
@@ -414,6 +415,120 @@ static BwdPlan plan_scan_bwd(const vivim_ssm_fwd_params& f, const vivim_ssm_bwd_
 }
 
 size_t scan_bwd_workspace_bytes(const vivim_ssm_fwd_params& f) { return plan_scan_bwd(f, nullptr).ws; }
+
+// ---- deterministic backward (vivim_selective_scan_bwd_det; slot scheme in det.cuh) ----
+// Slots per family: dA / dD / dbias one per (batch, segment) -- the generic kernel has no segments; dB / dC one per
+// workgroup (lanes = tokens) or channel set (generic) of a B/C group, in a (batch, group, dstate, seqlen) slot.  Constant
+// dB / dC (generic only) take one (dim, dstate) slot per batch.  The lanes = states kernels keep their dB / dC adds while
+// a group has at most two workgroups.
+// The lanes = tokens kernel at 8 tokens per lane has no VGPR left for the slot stores with two waves per SIMD: the
+// deterministic call runs it with 4-wave workgroups (one per CU), re-segmented for that width.
+static void det_tokens_width(const vivim_ssm_fwd_params& f, const vivim_ssm_bwd_params* p, BwdPlan& q) {
+    if (q.K != 8 || q.W != kBwWmax) return;
+    q.W = 4;
+    bwd_segmentation(f, q.K, q.W, q.S, q.seg);
+    q.ws = seg_ws_bytes(f, q.S);
+    if (p && q.family == BwdFamily::tokens) {
+        if (!ws_ok(p->workspace, p->workspace_bytes, q.ws)) {
+            q.S = 1;
+            q.seg = (f.seqlen + kWave * q.K - 1) / (kWave * q.K);
+        }
+        q.da_lds = f.dstate <= 16 && q.seg >= 2;
+    }
+}
+
+struct ScanDetLayout {
+    int64_t nA, nB, eB;            // slots of dA / dD / dbias; slots of dB / dC and floats per slot (nB 0: not slotted)
+    size_t bytes;
+};
+static ScanDetLayout scan_det_layout(const vivim_ssm_fwd_params& f, BwdFamily fam, int S, int W) {
+    const int64_t cpg = f.dim / f.n_groups, bgnl = (int64_t)f.batch * f.n_groups * f.dstate * f.seqlen;
+    ScanDetLayout l{(int64_t)f.batch, 0, 0, 0};
+    if (fam == BwdFamily::generic) {
+        l.nB = f.is_variable_B ? (cpg + kBwdGenR - 1) / kBwdGenR : f.batch;
+        l.eB = f.is_variable_B ? bgnl : (int64_t)f.dim * f.dstate;
+    } else if (fam == BwdFamily::tokens) {
+        l.nA = (int64_t)f.batch * S;
+        l.nB = ((cpg + kBwR - 1) / kBwR + W - 1) / W;
+        l.eB = bgnl;
+    } else {
+        const int64_t cpb = (int64_t)W * (4 / (f.dstate / 16)) * kLsCPR, bpg = (cpg + cpb - 1) / cpb;
+        l.nA = (int64_t)f.batch * S;
+        l.nB = bpg > 2 ? bpg : 0;
+        l.eB = bpg > 2 ? bgnl : 0;
+    }
+    l.bytes = sizeof(float) * (size_t)(l.nA * f.dim * (f.dstate + 2) + 2 * l.nB * l.eB);
+    return l;
+}
+
+// The shape level does not know which family the call's pointers allow: the larger of the shape's family (at its
+// segmentation; fewer segments only shrink it) and the generic fallback.
+size_t scan_bwd_det_workspace_bytes(const vivim_ssm_fwd_params& f) {
+    BwdPlan q = plan_scan_bwd(f, nullptr);
+    det_tokens_width(f, nullptr, q);
+    const size_t gen = scan_det_layout(f, BwdFamily::generic, 1, 0).bytes;
+    if (!q.W) return gen;
+    const BwdFamily fam = q.K ? BwdFamily::tokens : BwdFamily::states;     // (the shape level sets K for lanes = tokens only)
+    return std::max(gen, scan_det_layout(f, fam, q.S, q.W).bytes);
+}
+
+// The slots of the family this call's pointers select (never more than the shape-level size above).
+size_t scan_bwd_det_call_workspace_bytes(const vivim_ssm_bwd_params& p) {
+    BwdPlan q = plan_scan_bwd(p.f, &p);
+    if (q.family == BwdFamily::none) return 0;
+    det_tokens_width(p.f, &p, q);
+    return scan_det_layout(p.f, q.family, q.S, q.W).bytes;
+}
+
+// 0: launched; 1: the family is not built; 2: workspace missing or too small (nothing launched).
+int ssm_bwd_det_dispatch(const vivim_ssm_bwd_params& p, void* det_ws, size_t det_ws_bytes, hipStream_t s) {
+    const vivim_ssm_fwd_params& f = p.f;
+    BwdPlan q = plan_scan_bwd(f, &p);
+    if (q.family == BwdFamily::none) return 1;
+    det_tokens_width(f, &p, q);
+    const ScanDetLayout l = scan_det_layout(f, q.family, q.S, q.W);
+    if (det_ws == nullptr || det_ws_bytes < l.bytes || reinterpret_cast<uintptr_t>(det_ws) % 16 != 0) return 2;
+    float* wA = static_cast<float*>(det_ws);
+    float* wD = wA + l.nA * f.dim * f.dstate;
+    float* wb = wD + l.nA * f.dim;
+    float* wB = wb + l.nA * f.dim;
+    float* wC = wB + l.nB * l.eB;
+    vivim_ssm_bwd_params d = p;
+    d.dA = wA; d.dA_d_stride = f.dstate; d.dA_dstate_stride = 1;
+    if (p.dD) d.dD = wD;
+    if (p.ddelta_bias) d.ddelta_bias = wb;
+    const bool varBC = f.is_variable_B;
+    if (l.nB) {
+        d.dB = wB; d.dC = wC;
+        if (varBC) {
+            d.dB_batch_stride = d.dC_batch_stride = (int64_t)f.n_groups * f.dstate * f.seqlen;
+            d.dB_group_stride = d.dC_group_stride = (int64_t)f.dstate * f.seqlen;
+            d.dB_dstate_stride = d.dC_dstate_stride = f.seqlen;
+        } else {                   // constant B / C: (dim, dstate), the channel on the group stride
+            d.dB_batch_stride = d.dC_batch_stride = 0;
+            d.dB_group_stride = d.dC_group_stride = f.dstate;
+            d.dB_dstate_stride = d.dC_dstate_stride = 1;
+        }
+    }
+    switch (q.family) {
+        case BwdFamily::states: launch_ls_bwd(d, q, s, true); break;
+        case BwdFamily::tokens: launch_bwd_fast(d, q, s, true); break;
+        case BwdFamily::generic: launch_bwd_generic(d, q.ck, s, true); break;
+        case BwdFamily::none: return 1;
+    }
+    det_reduce(wA, (int)l.nA, det_out(static_cast<float*>(p.dA), {f.dim, f.dstate}, {p.dA_d_stride, p.dA_dstate_stride}), s);
+    if (p.dD) det_reduce(wD, (int)l.nA, det_out(static_cast<float*>(p.dD), {f.dim}, {1}), s);
+    if (p.ddelta_bias) det_reduce(wb, (int)l.nA, det_out(static_cast<float*>(p.ddelta_bias), {f.dim}, {1}), s);
+    if (l.nB) {
+        auto bc = [&](float* w, void* out, int64_t bs, int64_t gs, int64_t ns) {
+            if (varBC) det_reduce(w, (int)l.nB, det_out(static_cast<float*>(out), {f.batch, f.n_groups, f.dstate, f.seqlen}, {bs, gs, ns, 1}), s);
+            else       det_reduce(w, (int)l.nB, det_out(static_cast<float*>(out), {f.dim, f.dstate}, {gs, ns}), s);
+        };
+        bc(wB, p.dB, p.dB_batch_stride, p.dB_group_stride, p.dB_dstate_stride);
+        bc(wC, p.dC, p.dC_batch_stride, p.dC_group_stride, p.dC_dstate_stride);
+    }
+    return 0;
+}
 
 bool ssm_bwd_dispatch(const vivim_ssm_bwd_params& p, hipStream_t s) {
     const BwdPlan q = plan_scan_bwd(p.f, &p);

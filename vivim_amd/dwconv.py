@@ -2,6 +2,7 @@
 MambaLayer's Mlp (`DWConv`, modeling/vivim.py:57-68 -- nn.Conv3d(dim, dim, 3, 1, 1, groups=dim) applied to
 x.transpose(1, 2).view(B, C, nf, H, W)) without the transposes, on the gfx950 kernels of csrc/dwconv.hip.
 SURVEY.md section 8f row 4.  Same parameters as the nn.Conv3d / nn.Conv2d it replaces (weight (C,1,[kd,]3,3))."""
+import ctypes
 import os
 
 import torch
@@ -67,7 +68,12 @@ def _run_wgrad(x, dy, wt, dims, has_bias):
     P.x, P.dy, P.dwt = x.data_ptr(), dy.data_ptr(), acc.data_ptr()
     P.dbias = acc.data_ptr() + 4 * wt.shape[0] * C if has_bias else None
     with torch.cuda.device(x.device):
-        _lib.call("vivim_dwconv_wgrad", P, torch.cuda.current_stream().cuda_stream)
+        if _lib.deterministic():                      # fixed-order slot reduction of dwt / dbias, no float atomics
+            nbytes = _lib.lib().vivim_dwconv_wgrad_det_workspace_bytes(ctypes.byref(P))
+            ws = _lib.empty((nbytes,), torch.uint8, x.device)
+            _lib.call_det("vivim_dwconv_wgrad_det", P, ws.data_ptr(), nbytes, torch.cuda.current_stream().cuda_stream)
+        else:
+            _lib.call("vivim_dwconv_wgrad", P, torch.cuda.current_stream().cuda_stream)
     return acc
 
 

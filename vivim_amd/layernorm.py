@@ -16,6 +16,10 @@ _ITYPE = {torch.float32: _lib.F32, torch.float16: _lib.F16, torch.bfloat16: _lib
 
 
 def supported(x, weight):
+    # under torch.use_deterministic_algorithms the caller's ATen path runs instead: the backward kernel adds its row
+    # groups into dweight / dbias with float atomics
+    if _lib.deterministic():
+        return False
     if not (x.is_cuda and x.dim() == 3 and x.dtype in _ITYPE and weight is not None and weight.dtype == torch.float32):
         return False
     B, L, C = x.shape

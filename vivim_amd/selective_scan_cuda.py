@@ -3,6 +3,8 @@ mamba/csrc/selective_scan/selective_scan.cpp:494-497): `fwd` and `bwd` with the 
 signatures, argument checks and return lists, running the gfx950 kernels through the C ABI
 (include/vivim_hip.h).  Tensor allocation is the only thing PyTorch does here.
 """
+import ctypes
+
 import torch
 
 from . import _lib
@@ -187,7 +189,14 @@ def bwd(u, delta, A, B, C, D_, z_, delta_bias_, dout, x_, out_, dz_, delta_softp
         workspace = _lib.empty((ws_bytes,), torch.uint8, u.device)   # torch caching allocator: no sync
         P.workspace, P.workspace_bytes = workspace.data_ptr(), ws_bytes
     with torch.cuda.device(u.device):
-        _lib.call("vivim_selective_scan_bwd", P, torch.cuda.current_stream().cuda_stream)
+        if _lib.deterministic():                                     # fixed-order slot reduction, no float atomics
+            det_bytes = _lib.lib().vivim_scan_bwd_det_call_workspace_bytes(ctypes.byref(P))
+            last_workspace_bytes["bwd_det"] = det_bytes
+            det_ws = _lib.empty((det_bytes,), torch.uint8, u.device)
+            _lib.call_det("vivim_selective_scan_bwd_det", P, det_ws.data_ptr(), det_bytes,
+                          torch.cuda.current_stream().cuda_stream)
+        else:
+            _lib.call("vivim_selective_scan_bwd", P, torch.cuda.current_stream().cuda_stream)
     if var_B and var_C and B.dtype != torch.float32:
         dBC = acc[:nB + nC].to(B.dtype)
         dB_out, dC_out = dBC[:nB].view(B.shape), dBC[nB:].view(C.shape)
