@@ -191,3 +191,47 @@ def test_graft_entry_build_is_consistent():
     assertion is derived from the header, not hard-coded."""
     import __graft_entry__ as g
     g.build()
+
+
+def _read(*parts):
+    with open(os.path.join(ROOT, *parts)) as fh:
+        return fh.read()
+
+
+def test_no_experiment_scaffolding_in_kernel_sources():
+    """Timing-ablation switches (FOO_ABL) and in-kernel stamp hooks (VIVIM_STAMP*) are retired: the product build is the
+    only build of the kernel sources."""
+    bad = []
+    for top in (os.path.join("vivim_amd", "csrc"), "include"):
+        for dp, _, files in os.walk(os.path.join(ROOT, top)):
+            for f in files:
+                if f.endswith((".hip", ".cuh", ".h", ".hpp", ".cpp")) or f == "Makefile":
+                    src = open(os.path.join(dp, f)).read()
+                    bad += ["%s: %s" % (f, m) for m in re.findall(r"\b[A-Z0-9]+_ABL\b|VIVIM_STAMP", src)]
+    assert not bad, bad
+
+
+def test_env_switches_match_integration_table():
+    """The VIVIM_* variables the library, its Python wrappers and bench.py read are exactly the rows of INTEGRATION.md §4."""
+    read = set()
+    csrc = os.path.join(ROOT, "vivim_amd", "csrc")
+    for f in sorted(os.listdir(csrc)):
+        if f.endswith((".hip", ".cuh", ".h")):
+            src = _read("vivim_amd", "csrc", f)
+            read |= set(re.findall(r'\b(?:getenv|num)\(\s*"(VIVIM_\w+)"', src))
+            read |= set(re.findall(r'\btuning_get\([^,()]*,\s*"(VIVIM_\w+)"', src))
+    py = [os.path.join("vivim_amd", f) for f in sorted(os.listdir(os.path.join(ROOT, "vivim_amd"))) if f.endswith(".py")]
+    for f in py + ["bench.py"]:
+        src = _read(f)
+        for m in re.findall(r'os\.(?:environ\.get|getenv)\(\s*["\'](VIVIM_\w+)|os\.environ\[\s*["\'](VIVIM_\w+)|'
+                            r'["\'](VIVIM_\w+)["\']\s+(?:not\s+)?in\s+os\.environ', src):
+            read |= {n for n in m if n}
+    doc = _read("INTEGRATION.md")
+    section = re.search(r"^## 4\..*?$(.*?)^## ", doc, flags=re.S | re.M).group(1)
+    documented = set()
+    for line in section.splitlines():
+        if line.startswith("| `"):
+            documented |= set(re.findall(r"`(VIVIM_\w+)", line.split("|")[1]))
+    assert read, "no environment reads found: the patterns above no longer match the code"
+    assert read == documented, {"read but not in INTEGRATION.md §4": sorted(read - documented),
+                                "in INTEGRATION.md §4 but not read": sorted(documented - read)}

@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Times the two direction-map kernels (vivim_dir_scatter / vivim_dir_gather) and, for scale, the grouped conv1d + scan
 forward and backward that consume their output, at the four stage shapes of BASELINE configs[1] (bf16, B 3, 5 frames).
-With VIVIM_LIB pointing at the -DDIR_ABL=1 build (tools/abl.sh dirbuild) the maps move the frame interleave only: the
+profiles/r03_dirmap_ablation.log has these times against a build whose maps moved the frame interleave only: the
 difference is the most a `direction` argument on conv + scan (directions 0 and 1) could save."""
 import os
 import sys

@@ -183,23 +183,6 @@ __device__ __forceinline__ void lds_barrier() {
     asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
 }
 
-// ---- in-kernel stamps: DIAGNOSTIC builds only (tools/scan_lab.hip defines VIVIM_STAMPS) ----
-#ifdef VIVIM_STAMPS
-__device__ unsigned long long* g_stamp_buf = nullptr;   // [block][wave][step][slot]
-constexpr int kStampSlots = 16, kStampSteps = 8, kStampWaves = 8;
-__device__ __forceinline__ void stamp(int step, int slot, int wave, int lane) {
-    __builtin_amdgcn_sched_barrier(0);
-    unsigned long long t;
-    asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(t) :: "memory");
-    __builtin_amdgcn_sched_barrier(0);
-    if (g_stamp_buf && lane == 0 && step < kStampSteps && blockIdx.x < 2 && blockIdx.y == 0 && blockIdx.z == 0)
-        g_stamp_buf[((blockIdx.x * kStampWaves + wave) * kStampSteps + step) * kStampSlots + slot] = t;
-}
-#define VIVIM_STAMP(step, slot, wave, lane) stamp(step, slot, wave, lane)
-#else
-#define VIVIM_STAMP(step, slot, wave, lane) ((void)0)
-#endif
-
 // ---- wave64 scans of affine maps  x -> P*x + H  ----
 // Forward: lane l ends up with the composition of lanes 0..l (lane 0 applied first).
 __device__ __forceinline__ void wave_scan_affine_fwd(float& P, float& H, int lane) {

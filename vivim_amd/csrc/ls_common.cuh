@@ -359,7 +359,6 @@ struct LsSeg {
     float* dsum;                   // [batch][dim][S]           pre-pass: the segment's sum of delta (see the kernels)
     float* gin;                    // [batch][dim][S][dstate]   carry kernel: inflow of segment s
     int bc_vec;                    // B / C rows may be read with 16-byte vectors
-    int dbg;                       // DIAGNOSTIC (VIVIM_LS_DBG): 1 skips the backward's tile epilogue, 2 its B / C loads -- wrong results
 };
 
 template <int NS> struct LsGeom {

@@ -400,7 +400,6 @@ __global__ void __launch_bounds__(W * kWave, (K == 4 && W == 4) ? 3 : (DET && K 
     for (int step = s_hi - 1; step >= s_lo; --step) {
         const int t0 = step * TILE + lane * K;
         const bool in = t0 < L;                         // host guarantees L % K == 0: all-in or all-out
-        VIVIM_STAMP(nsteps - 1 - step, 0, wave, lane);
         // forward checkpoints entering this step, one float per (state, channel)
         for (int i = lane; i < N * R; i += kWave) {
             const int n = i / R, r = i - n * R;
@@ -449,7 +448,6 @@ __global__ void __launch_bounds__(W * kWave, (K == 4 && W == 4) ? 3 : (DET && K 
 #pragma unroll
         for (int k = 0; k < K; ++k) { S1[k] = f2{0.0f, 0.0f}; S2[k] = f2{0.0f, 0.0f}; }
         wave_lds_fence();
-        VIVIM_STAMP(nsteps - 1 - step, 1, wave, lane);
         {
             RawK<T, K> Braw = load_vec_always<T, K>(Bv + t0, in, Bv);
             RawK<T, K> Craw = load_vec_always<T, K>(Cv + t0, in, Cv);
@@ -464,7 +462,6 @@ __global__ void __launch_bounds__(W * kWave, (K == 4 && W == 4) ? 3 : (DET && K 
                     Braw = load_vec_always<T, K>(Bv + (n + 1) * f.B_dstate_stride + t0, nx, Bv);
                     Craw = load_vec_always<T, K>(Cv + (n + 1) * f.C_dstate_stride + t0, nx, Cv);
                 }
-                if (n == 1) VIVIM_STAMP(nsteps - 1 - step, 2, wave, lane);
                 // the state's record: checkpoint, g carry, first decay of the step to the right, A * log2e (pairs)
                 const f2* q2 = reinterpret_cast<const f2*>(rec + n * kRec * R);
                 const f2 hck = q2[HCK], gcar = q2[GCAR], afirst = q2[AFIRST], a2v = q2[A2VAL];
@@ -477,7 +474,6 @@ __global__ void __launch_bounds__(W * kWave, (K == 4 && W == 4) ? 3 : (DET && K 
                     wB[k] = w[k] * Bn[k];
                     H = fma2(a[k], H, wB[k]);
                 }
-                if (n == 1) VIVIM_STAMP(nsteps - 1 - step, 3, wave, lane);
                 {
                     float P0 = P.x, H0 = H.x, P1 = P.y, H1 = H.y;
                     wave_scan2_affine_fwd(P0, H0, P1, H1);
@@ -493,7 +489,6 @@ __global__ void __launch_bounds__(W * kWave, (K == 4 && W == 4) ? 3 : (DET && K 
                         hs[k] = h;
                     }
                 }
-                if (n == 1) VIVIM_STAMP(nsteps - 1 - step, 4, wave, lane);
                 // ---- reverse scan of g_t = a_{t+1} g_{t+1} + C_t dy_t ----
                 const f2 an = dpp_mov2<kDppWaveShl1>(afirst, a[0]);          // decay of the token right of this lane
                 f2 cdy[K], Pr = an, G = {0.0f, 0.0f};
@@ -512,7 +507,6 @@ __global__ void __launch_bounds__(W * kWave, (K == 4 && W == 4) ? 3 : (DET && K 
                     wave_scan_rev_join(P1, G1, lane);
                     gfirst = fma2(f2{P0, P1}, gcar, f2{G0, G1});             // g at this lane's first token
                 }
-                if (n == 1) VIVIM_STAMP(nsteps - 1 - step, 5, wave, lane);
                 f2 gc = dpp_mov2<kDppWaveShl1>(gcar, gfirst);                // g at the token right of this lane
                 f2 dA_part = {0.0f, 0.0f};
                 float dBv[K], dCv[K];
@@ -528,7 +522,6 @@ __global__ void __launch_bounds__(W * kWave, (K == 4 && W == 4) ? 3 : (DET && K 
                     dBv[k] = db.x + db.y;                                    // the pair's sum
                     dCv[k] = dc.x + dc.y;
                 }
-                if (n == 1) VIVIM_STAMP(nsteps - 1 - step, 6, wave, lane);
                 if (DA_LDS) {
                     dAl[n * kWave + lane] += dA_part;                        // wave-private: no barrier
                     if (lane == 0) {                                         // lane 0 already holds both values
@@ -554,9 +547,7 @@ __global__ void __launch_bounds__(W * kWave, (K == 4 && W == 4) ? 3 : (DET && K 
                         sl[(K + k) * kWave] = dCv[k];
                     }
                 }
-                if (n == 1) VIVIM_STAMP(nsteps - 1 - step, 7, wave, lane);
                 lds_barrier();
-                if (n == 1) VIVIM_STAMP(nsteps - 1 - step, 8, wave, lane);
 #pragma unroll
                 for (int j = 0; j < EPT; ++j) {
                     // fixed-order sum over the workgroup's 8 channel pairs, then one fp32 atomic per element
@@ -575,16 +566,10 @@ __global__ void __launch_bounds__(W * kWave, (K == 4 && W == 4) ? 3 : (DET && K 
                         if (tq < L) (e_isC ? dCg + n * p.dC_dstate_stride : dBg + n * p.dB_dstate_stride)[tq] = acc;
                         continue;
                     }
-#if defined(BW_ABL) && BW_ABL == 1               // timing experiment (tools/abl.sh bwdbuild): no dB / dC atomics -- wrong results
-                    asm volatile("" : : "v"(acc), "v"(t));
-#else
                     atomicAdd((e_isC ? dCg + n * p.dC_dstate_stride : dBg + n * p.dB_dstate_stride) + t, acc);
-#endif
                 }
-                if (n == 1) VIVIM_STAMP(nsteps - 1 - step, 9, wave, lane);
             }
         }
-        VIVIM_STAMP(nsteps - 1 - step, 11, wave, lane);
         // ---- per-channel outputs of the step ----
 #pragma unroll
         for (int r = 0; r < R; ++r) {
@@ -610,7 +595,6 @@ __global__ void __launch_bounds__(W * kWave, (K == 4 && W == 4) ? 3 : (DET && K 
             store_vec<T, K>(static_cast<T*>(p.du) + b * p.du_batch_stride + d[r] * p.du_d_stride + t0, in && active && r < nvalid, duv);
             store_vec<T, K>(static_cast<T*>(p.ddelta) + b * p.ddelta_batch_stride + d[r] * p.ddelta_d_stride + t0, in && active && r < nvalid, ddv);
         }
-        VIVIM_STAMP(nsteps - 1 - step, 10, wave, lane);
     }
     if (active) {
 #pragma unroll

@@ -242,7 +242,6 @@ __global__ void __launch_bounds__(NS * kWave, MINW) ssm_fwd_nsplit_kernel(const 
     lds_barrier();
     for (int step = 0; step < nsteps; ++step) {
         const int t0 = step * TILE + lane * K;
-        VIVIM_STAMP(step, 0, wave, lane);
         // ---- issue every global load of this step up front; they are consumed after LDS/VALU work ----
         const int tp = step * TILE + ptok;             // this thread's epilogue tokens
         const int tn = tp + TILE;                      // ... and next step's prologue tokens
@@ -274,7 +273,6 @@ __global__ void __launch_bounds__(NS * kWave, MINW) ssm_fwd_nsplit_kernel(const 
             Bq[i] = load_vec<T, K>(Bv + (n0 + i) * p.B_dstate_stride + t0 + TILE, ok);
             Cq[i] = load_vec<T, K>(Cv + (n0 + i) * p.C_dstate_stride + t0 + TILE, ok);
         }
-        VIVIM_STAMP(step, 1, wave, lane);
         // one state for the wave's R channels: lane maps, DPP scan, apply, checkpoint
         auto do_state = [&](int n, const RawK<T, K>& Braw, const RawK<T, K>& Craw) {
             float A2[R], cin[R];
@@ -323,7 +321,6 @@ __global__ void __launch_bounds__(NS * kWave, MINW) ssm_fwd_nsplit_kernel(const 
             }
         };
         do_state(n0, Bc[0], Cc[0]);
-        VIVIM_STAMP(step, 2, wave, lane);
         if (SPW > 1) {
             RawK<T, K> Bx = load_vec<T, K>(Bv + (n0 + 2) * p.B_dstate_stride + t0, in && SPW > 2);
             RawK<T, K> Cx = load_vec<T, K>(Cv + (n0 + 2) * p.C_dstate_stride + t0, in && SPW > 2);
@@ -337,14 +334,11 @@ __global__ void __launch_bounds__(NS * kWave, MINW) ssm_fwd_nsplit_kernel(const 
                 do_state(n, Bn_, Cn_);
             }
         }
-        VIVIM_STAMP(step, 3, wave, lane);
 #pragma unroll
         for (int r = 0; r < R; ++r)
 #pragma unroll
             for (int k = 0; k < K; ++k) s_part[wave * TSZ + (r * K + k) * kLdsRow + lane] = yp[r][k];
-        VIVIM_STAMP(step, 4, wave, lane);
         lds_barrier();
-        VIVIM_STAMP(step, 5, wave, lane);
         // ---- epilogue of this step + prologue of the next, same token slice per thread ----
         {
             float y[IPT];
@@ -366,11 +360,8 @@ __global__ void __launch_bounds__(NS * kWave, MINW) ssm_fwd_nsplit_kernel(const 
                 }
             }
         }
-        VIVIM_STAMP(step, 6, wave, lane);
         if (more) prologue(step + 1, unx, dnx);
-        VIVIM_STAMP(step, 7, wave, lane);
         lds_barrier();
-        VIVIM_STAMP(step, 8, wave, lane);
     }
 }
 

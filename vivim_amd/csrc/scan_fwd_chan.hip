@@ -24,12 +24,6 @@
 
 namespace vivim {
 
-// CH_ABL: timing experiments (tools/abl.sh chan): 1 no scalar B / C loads, 2 no tile loads, 3 no tile stores, 4 no exp -- results
-// are wrong for any value but 0; never set in the product build.
-#ifndef CH_ABL
-#define CH_ABL 0
-#endif
-constexpr int kChAbl = CH_ABL;
 constexpr int kChN = 16;           // states (compile time: they live in registers)
 
 struct FwdSeg {
@@ -113,7 +107,7 @@ typedef float cf2 __attribute__((ext_vector_type(2)));
 #define CHP_PAIR(j, BP, CP)                                                                        \
     {                                                                                              \
         cf2 t = dlp * ap[j];                                                                       \
-        if (kChAbl != 4) { t.x = fast_exp2(t.x); t.y = fast_exp2(t.y); }                           \
+        t.x = fast_exp2(t.x); t.y = fast_exp2(t.y);                                                \
         cf2 u;                                                                                     \
         asm volatile("v_pk_mul_f32 %0, " BP ", %1" : "=v"(u) : "v"(wp));                           \
         hp[j] = __builtin_elementwise_fma(t, hp[j], u);                                            \
@@ -131,8 +125,7 @@ typedef float cf2 __attribute__((ext_vector_type(2)));
 template <int PASS>
 __device__ __forceinline__ void chan_token_x(cf2* hp, const cf2* ap, float dl, float w, cf2& y2, const float* next) {
     const cf2 dlp = {dl, dl}, wp = {w, w};
-    if (kChAbl == 1) asm volatile("; CHAN lo_x\n\t" : : [ptr] "s"(next) : CH_CLOB_Y);
-    else if (PASS == 2) asm volatile("; CHAN lo_x\n\t" CH_LOAD_Y2 : : [ptr] "s"(next) : CH_CLOB_Y);
+    if (PASS == 2) asm volatile("; CHAN lo_x\n\t" CH_LOAD_Y2 : : [ptr] "s"(next) : CH_CLOB_Y);
     else           asm volatile("; CHAN lo_x\n\t" CH_LOAD_Y1 : : [ptr] "s"(next) : CH_CLOB_Y);
     CHP_PAIR(0, "s[68:69]", "s[76:77]") CHP_PAIR(1, "s[70:71]", "s[78:79]")
     CHP_PAIR(2, "s[72:73]", "s[80:81]") CHP_PAIR(3, "s[74:75]", "s[82:83]")
@@ -144,8 +137,7 @@ __device__ __forceinline__ void chan_token_x(cf2* hp, const cf2* ap, float dl, f
 template <int PASS>
 __device__ __forceinline__ void chan_token_y(cf2* hp, const cf2* ap, float dl, float w, cf2& y2, const float* next) {
     const cf2 dlp = {dl, dl}, wp = {w, w};
-    if (kChAbl == 1) asm volatile("; CHAN lo_y\n\t" : : [ptr] "s"(next) : CH_CLOB_X);
-    else if (PASS == 2) asm volatile("; CHAN lo_y\n\t" CH_LOAD_X2 : : [ptr] "s"(next) : CH_CLOB_X);
+    if (PASS == 2) asm volatile("; CHAN lo_y\n\t" CH_LOAD_X2 : : [ptr] "s"(next) : CH_CLOB_X);
     else           asm volatile("; CHAN lo_y\n\t" CH_LOAD_X1 : : [ptr] "s"(next) : CH_CLOB_X);
     CHP_PAIR(0, "s[36:37]", "s[44:45]") CHP_PAIR(1, "s[38:39]", "s[46:47]")
     CHP_PAIR(2, "s[40:41]", "s[48:49]") CHP_PAIR(3, "s[42:43]", "s[50:51]")
@@ -257,7 +249,6 @@ ssm_fwd_chan_kernel(const vivim_ssm_fwd_params p, const FwdSeg sg) {
     union tile_regs { RawK<T, EPV> r; v4 v; };
     tile_regs nu[NIO], nd[NIO];
     auto issue_tile_loads = [&](int tile) {
-        if (kChAbl == 2 && tile > tile_lo) return;
         kparams_t q = fresh_params();
         // Unconditional loads (countable vmcnt: a load under a branch would make the next wait a full drain); columns past
         // the end are clamped onto the row's last vector -- their tokens are never processed (blocks stop at L, the
@@ -286,7 +277,7 @@ ssm_fwd_chan_kernel(const vivim_ssm_fwd_params p, const FwdSeg sg) {
     // (Registers are free for it: two resident tile streams already cap the kernel at two waves per SIMD.)
     tile_regs gz[NIO];
     auto issue_z_loads = [&](int tile) {
-        if (!(PASS == 2 && HAS_Z) || kChAbl == 2) return;
+        if (!(PASS == 2 && HAS_Z)) return;
         kparams_t q = fresh_params();
         const int t = min(__builtin_amdgcn_readfirstlane(tile * TT) + io_col * EPV, L - EPV);
         const int64_t sz = q->z_d_stride;
@@ -371,7 +362,7 @@ ssm_fwd_chan_kernel(const vivim_ssm_fwd_params p, const FwdSeg sg) {
             }
         }
         wave_lds_fence();
-        if (PASS == 2 && kChAbl != 3) {                // LDS -> global, coalesced; the gate is applied here
+        if (PASS == 2) {                               // LDS -> global, coalesced; the gate is applied here
             kparams_t q = fresh_params();
             const int t = t0 + io_col * EPV;
             if (t < L) {

@@ -40,16 +40,11 @@ namespace vivim {
 // (the unrolled first version: 4 x the code, its scalar state spilled to VGPR lanes).  The activations of step i + 1 are
 // requested before step i is computed.
 // =========================================================================================================================
-// LS_ABL: timing experiments of tools/abl.sh (results are WRONG for any value but 0; never set in the product build).
-#ifndef LS_ABL
-#define LS_ABL 0
-#endif
-constexpr int kAbl = LS_ABL;
 // DET (vivim_selective_scan_bwd_det): dA / dD / dbias are stored into the (batch, segment) slot of the workspace p points
 // them at.  dB / dC keep their adds while a group has at most two workgroups (0 + a + b == 0 + b + a exactly); with
 // more, p's dB / dC point into the workspace too and the workgroup's index within its group is the slot.
 template <typename T, int NS, bool HAS_Z, bool DET = false>
-__global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(kAbl == 8 ? 4 : (NS == 16 ? 3 : 2), kAbl == 8 ? 4 : 3))) ssm_ls_bwd_kernel(const vivim_ssm_bwd_params p, const LsSeg sg) {
+__global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(NS == 16 ? 3 : 2, 3))) ssm_ls_bwd_kernel(const vivim_ssm_bwd_params p, const LsSeg sg) {
     typedef LsGeom<NS> G;
     constexpr int RPS = G::RPS, SPW = G::SPW, CPW = G::CPW, CPR = kLsCPR;
     const vivim_ssm_fwd_params& f = p.f;
@@ -145,14 +140,14 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(kAbl =
         const int d = dwave + rowch + c;
         const bool cv = d < d_end;
         const int chu = min(dwave + c, d_end - 1);
-        const bool ok = kAbl != 4 && cv && t < L && tile >= tile_lo;   // past the segment's last step: nothing is used
+        const bool ok = cv && t < L && tile >= tile_lo;   // past the segment's last step: nothing is used
         r.uu = tu.ld_raw(chu, t, ok);
         r.raw = tdl.ld_raw(chu, t, ok);
         r.dy = tdo.ld_raw(chu, t, ok);
         r.zf = 0.0f; r.of = 0.0f;
         if (HAS_Z) { r.zf = tz.ld_raw(q, chu, t, ok); r.of = to.ld_raw(q, chu, t, ok); }
         const int blk = tile / RPS;
-        r.hin = tx.ld_raw(q, chu, (blk - 1) * NS + n, kAbl != 4 && blk > 0 && cv && tile >= tile_lo);
+        r.hin = tx.ld_raw(q, chu, (blk - 1) * NS + n, blk > 0 && cv && tile >= tile_lo);
         return r;
     };
 
@@ -167,7 +162,6 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(kAbl =
     int p_chu = min(dwave, d_end - 1), p_t = 0;
     bool p_st = false;
     auto flush = [&]() __attribute__((always_inline)) {
-        if constexpr (kAbl == 3) return;
         const ls_kargs qs = ls_fresh_kargs();
         if (HAS_Z) {
             tdz.st(qs, p_chu, p_t, p_st, p_dz);
@@ -202,7 +196,7 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(kAbl =
         for (int k = 0; k < 16; ++k) { dBv[k] = 0.0f; dCv[k] = 0.0f; }
         ls_arrive(Bv);
         ls_arrive(Cv);
-        const bool stage_next = kAbl != 1 && W == 4 && bc_vec && tile - 1 >= tile_lo;   // (a tile left of another one is whole)
+        const bool stage_next = W == 4 && bc_vec && tile - 1 >= tile_lo;   // (a tile left of another one is whole)
         u32x4 sb = {0u, 0u, 0u, 0u}, sc = {0u, 0u, 0u, 0u};
 #pragma unroll 1
         for (int c = 0; c < CPR; ++c) {
@@ -277,7 +271,6 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(kAbl =
                 float hp = h_in;
                 sfor<0, 16>([&](auto kc) {
                     constexpr int k = decltype(kc)::value;
-                    if constexpr (kAbl == 6) { a[k] = A2; h[k] = hp + Bv[k]; return; }
                     a[k] = fast_exp2(tok<k>(dl) * A2);
                     hp = tok_fma<k>(a[k] * hp, w, Bv[k]);                                  // h_t = a_t h_{t-1} + d_t u_t B_t
                     h[k] = hp;
@@ -297,7 +290,6 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(kAbl =
                     if constexpr (k & 1) dA1 = tok_fma<k>(dA1, dl, x); else dA0 = tok_fma<k>(dA0, dl, x);   // two chains
                     dBv[k] = tok_fma<k>(dBv[k], w, gk);
                     dCv[k] = tok_fma<k>(dCv[k], dy, h[k]);
-                    if constexpr (kAbl == 7) { if (k == 0) { S1 = s1[0] + s1[5] + s1[15]; S2 = s2[0] + s2[7] + s2[15]; } return; }
                     ls_reduce_down<k>(s1, z1, w1, v1, S1, li);
                     ls_reduce_down<k>(s2, z2, w2, v2, S2, li);
                 });
@@ -317,8 +309,7 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(kAbl =
         // Both barriers sit around the slot writes: the first says "everybody is done reading the previous tile's slots and
         // this tile's staged rows", the second "slots and the next tile's rows are written".  Back to back, the second
         // finds the waves already aligned; spaced (one before, one after the reduction) they cost two synchronisations.
-        if constexpr (kAbl == 1) continue;
-        if constexpr (kAbl != 2) lds_barrier();
+        lds_barrier();
         if (stage_next && tid < PT) {
             *reinterpret_cast<u32x4*>(stage + tid * 16) = sb;
             *reinterpret_cast<u32x4*>(stage + (PT + tid) * 16) = sc;
@@ -329,7 +320,7 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(kAbl =
             *reinterpret_cast<float4*>(slot + q * 4) = float4{dBv[q * 4], dBv[q * 4 + 1], dBv[q * 4 + 2], dBv[q * 4 + 3]};
             *reinterpret_cast<float4*>(slot + NS * 16 + q * 4) = float4{dCv[q * 4], dCv[q * 4 + 1], dCv[q * 4 + 2], dCv[q * 4 + 3]};
         }
-        if constexpr (kAbl != 2) lds_barrier();
+        lds_barrier();
         {
             const int nsrc = W * SPW;
             for (int e = tid; e < 2 * NS * 16; e += blockDim.x) {
@@ -674,7 +665,7 @@ static size_t ls_bwd_smem(int W, int NS) {
     // states at the inner tile boundaries of a checkpoint block) + the D / bias table: 50.1 KB for 4 waves at dstate 16
     const int RPS = NS / 16, SPW = 4 / RPS;
     return ((size_t)W * SPW * 2 * NS * 16 + (size_t)W * kLsCPR * (4 + RPS - 1) * kWave + (size_t)W * kLsCPR * 8) * sizeof(float) +
-           (size_t)2 * NS * 16 * 4 + scan_env().ls_smem_pad;   // + the staged B / C rows of one tile (sized for fp32)
+           (size_t)2 * NS * 16 * 4;   // + the staged B / C rows of one tile (sized for fp32)
 }
 
 // Calls fn(T{}, LsGeom<NS>{}) for the element type and state count of `f`.
@@ -699,8 +690,8 @@ int ls_bwd_occupancy(const vivim_ssm_fwd_params& f, int W) {
     return nb;
 }
 
-static LsSeg ls_seg(void* ws, const vivim_ssm_fwd_params& f, int S, int seg_blocks, bool bc_vec, int dbg) {
-    LsSeg sg = {S, seg_blocks, nullptr, nullptr, nullptr, bc_vec ? 1 : 0, dbg};
+static LsSeg ls_seg(void* ws, const vivim_ssm_fwd_params& f, int S, int seg_blocks, bool bc_vec) {
+    LsSeg sg = {S, seg_blocks, nullptr, nullptr, nullptr, bc_vec ? 1 : 0};
     if (S > 1) {
         const size_t nbd = (size_t)f.batch * f.dim * S;
         sg.agg = static_cast<float*>(ws);
@@ -714,7 +705,7 @@ static LsSeg ls_seg(void* ws, const vivim_ssm_fwd_params& f, int S, int seg_bloc
 // of the plan's generation.
 void launch_ls_bwd(const vivim_ssm_bwd_params& p, const BwdPlan& q, hipStream_t stream, bool det) {
     const vivim_ssm_fwd_params& f = p.f;
-    const LsSeg sg = ls_seg(p.workspace, f, q.S, q.seg, q.bc_vec, scan_env().ls_dbg);
+    const LsSeg sg = ls_seg(p.workspace, f, q.S, q.seg, q.bc_vec);
     const int cpg = f.dim / f.n_groups;
     if (q.closed_prepass) launch_bwd_closed_prepass(p, sg, q.K, stream);
     with_itype_ns(f, [&](auto t, auto g) {
@@ -746,7 +737,7 @@ void launch_ls_bwd(const vivim_ssm_bwd_params& p, const BwdPlan& q, hipStream_t 
 }
 
 void launch_ls_fwd(const vivim_ssm_fwd_params& p, const FwdPlan& q, hipStream_t stream) {
-    const LsSeg sg = ls_seg(p.workspace, p, q.S, q.seg, q.bc_vec, 0);
+    const LsSeg sg = ls_seg(p.workspace, p, q.S, q.seg, q.bc_vec);
     const int cpg = p.dim / p.n_groups;
     const int PW = 4;
     with_itype_ns(p, [&](auto t, auto g) {

@@ -35,7 +35,7 @@
 // staged LDS copy instead of 32 registers (+6 %), the reductions as one block behind the sweep (+1 %), 8-wave workgroups
 // with plain dB / dC stores (+5 ... +18 %), three waves per SIMD (32-token spans, B / C from LDS, 168 VGPRs with spills outside the
 // step loop; tools/experiments/ls2_w3.patch: +8 ... +20 % on 16-bit rows, +1 ... +2 % on fp32).  Timing
-// ablations (LS2_ABL): no LDS reads in the sweeps -11 %, no reductions -15 %, no forward rebuild -14 %, no epilogue -3 %:
+// ablations (same log): no LDS reads in the sweeps -11 %, no reductions -15 %, no forward rebuild -14 %, no epilogue -3 %:
 // the cost is spread over the instruction stream, which is what "VALU-bound" looks like from outside.
 #include "scan_plan.cuh"
 
@@ -137,15 +137,11 @@ __device__ __forceinline__ float ls2_rows32(float P, float Q) {
 // otherwise: 48 more live registers, spilled)
 __device__ __forceinline__ void ls2_sched_fence() { asm volatile("" ::: "memory"); }
 
-#ifndef LS2_ABL
-#define LS2_ABL 0
-#endif
-constexpr int kAbl2 = LS2_ABL;       // timing experiments only (tools/abl.sh ls2build): results are WRONG for any value but 0
-
 // One (tile, channel) step is the forward sweep, the reverse sweep and four instructions of output arithmetic: everything a
 // token needs that does not depend on the scan (softplus, the z gate, dz, the sigmoid factor of ddelta) is done at SPAN
 // level, where a lane holds EPV consecutive tokens of one channel and their dependency chains interleave -- in-kernel
-// stamps of the first build had a step spend 1000 + 600 cycles of pure latency in these chains against 2700 in the sweeps.
+// stamps of the first build had a step spend 1000 + 600 cycles of pure latency in these chains against 2700 in the sweeps
+// (profiles/r03_ls2_stamps.log).
 // DET (vivim_selective_scan_bwd_det): as in scan_ls.hip's ssm_ls_bwd_kernel.
 template <typename T, bool HAS_Z, bool DET = false>
 __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) ssm_ls2_bwd_kernel(const vivim_ssm_bwd_params p, const LsSeg sg) {
@@ -293,7 +289,6 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))
         wave_lds_fence();
     };
     auto store_span = [&](int sp) __attribute__((always_inline)) {
-        if constexpr (kAbl2 == 3) return;
         wave_lds_fence();
         const ls_kargs q = ls_fresh_kargs();
         int ln = lane;
@@ -350,12 +345,6 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))
     bool staged = false;
     float hcur[CPR], hnxt[CPR];
     fetch_h(tile_hi - 1, hcur);
-#ifdef VIVIM_STAMPS
-    int stamp_step = 0;                                       // DIAGNOSTIC builds only (tools/ls2_lab.hip)
-#define LS2_STAMP(slot) VIVIM_STAMP(stamp_step, slot, wave, lane)
-#else
-#define LS2_STAMP(slot) ((void)0)
-#endif
 
     const int sp_hi = (tile_hi - 1) / TPS, sp_lo = tile_lo / TPS;
 #pragma unroll 1
@@ -401,7 +390,6 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))
                     sb = rB.piece(q, (tile - 1) * kLsT, mine ? pn : 0u, mine ? pq : 0u);
                     sc = rC.piece(q, (tile - 1) * kLsT, mine ? pn : 0u, mine ? pq : 0u);
                 }
-                LS2_STAMP(0);
                 const float* dlr = dlb + cw * TS + tokb;      // the 16 tokens of this step: the same address in all lanes of a row
                 float* wur = wub + cw * TS + tokb;
                 float* dyr = dyb + cw * TS + tokb;
@@ -409,7 +397,6 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))
                 const float dl_t = dlr[tk], dy_t = dyr[tk];
                 const float uu = to_f32<T>(*reinterpret_cast<const T*>(raw_u + cw * 128 + (tokb + tk) * (int)sizeof(T)));
                 const float A2 = A2r[0];
-                LS2_STAMP(1);
                 // ---- forward states of the tile, from the checkpoint ----
                 float a[16], h[16];
                 {
@@ -418,20 +405,17 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))
                     for (int m = 0; m < 4; ++m) {
                         ls2_sched_fence();
                         float4 d4, w4;
-                        if constexpr (kAbl2 == 9) { d4 = float4{dl_t, dl_t, dl_t, dl_t}; w4 = float4{dy_t, dy_t, uu, uu}; }   // timing only: no LDS reads in the sweeps
-                        else { d4 = *reinterpret_cast<const float4*>(dlr + 4 * m); w4 = *reinterpret_cast<const float4*>(wur + 4 * m); }
+                        d4 = *reinterpret_cast<const float4*>(dlr + 4 * m); w4 = *reinterpret_cast<const float4*>(wur + 4 * m);
                         const float dd[4] = {d4.x, d4.y, d4.z, d4.w}, ww[4] = {w4.x, w4.y, w4.z, w4.w};
 #pragma unroll
                         for (int j = 0; j < 4; ++j) {
                             const int k = 4 * m + j;
-                            if constexpr (kAbl2 == 6) { a[k] = A2; h[k] = hp + Bv[k]; continue; }
                             a[k] = fast_exp2(dd[j] * A2);
                             hp = fmaf(a[k], hp, ww[j] * Bv[k]);                          // h_t = a_t h_{t-1} + d_t u_t B_t
                             h[k] = hp;
                         }
                     }
                 }
-                LS2_STAMP(2);
                 // ---- reverse sweep: g_t = a_{t+1} g_{t+1} + C_t dy_t; ag = a_t g_t is the carry to the left ----
                 float s1[16], s2[16], z1[8], z2[8], w1[4], w2[4], v1[2], v2[2], S1 = 0.0f, S2 = 0.0f;
                 {
@@ -440,9 +424,8 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))
                         constexpr int m = decltype(mc)::value;
                         ls2_sched_fence();
                         float4 d4, w4, y4;
-                        if constexpr (kAbl2 == 9) { d4 = float4{dl_t, dl_t, dl_t, dl_t}; w4 = float4{dy_t, dy_t, uu, uu}; y4 = float4{uu, dy_t, dl_t, uu}; }
-                        else { d4 = *reinterpret_cast<const float4*>(dlr + 4 * m); w4 = *reinterpret_cast<const float4*>(wur + 4 * m);
-                               y4 = *reinterpret_cast<const float4*>(dyr + 4 * m); }
+                        d4 = *reinterpret_cast<const float4*>(dlr + 4 * m); w4 = *reinterpret_cast<const float4*>(wur + 4 * m);
+                        y4 = *reinterpret_cast<const float4*>(dyr + 4 * m);
                         const float dd[4] = {d4.x, d4.y, d4.z, d4.w}, ww[4] = {w4.x, w4.y, w4.z, w4.w}, yy[4] = {y4.x, y4.y, y4.z, y4.w};
                         sfor_down<4>([&](auto jc) {
                             constexpr int j = decltype(jc)::value;
@@ -455,7 +438,6 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))
                             if constexpr (k & 1) dA1 = fmaf(dd[j], x, dA1); else dA0 = fmaf(dd[j], x, dA0);   // two chains
                             dBv[k] = fmaf(ww[j], gk, dBv[k]);
                             dCv[k] = fmaf(yy[j], h[k], dCv[k]);
-                            if constexpr (kAbl2 == 7) { if (k == 0) { S1 = s1[0] + s1[5] + s1[15]; S2 = s2[0] + s2[7] + s2[15]; } return; }
                             ls2_reduce_down<k>(s1, z1, w1, v1, S1, li);
                             ls2_reduce_down<k>(s2, z2, w2, v2, S2, li);
                         });
@@ -465,21 +447,14 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))
                     dacc[0] = dacc[1]; dacc[1] = dacc[2]; dacc[2] = dacc[3]; dacc[3] = dA0 + dA1;
                     A2r[0] = A2r[1]; A2r[1] = A2r[2]; A2r[2] = A2r[3]; A2r[3] = A2;
                 }
-                LS2_STAMP(3);
                 // ---- this lane's token: du, and ddelta up to the sigmoid factor (applied at span level), into the delta u / dy
                 // slots of the token (all sixteen were consumed by the sweeps above) ----
                 wave_lds_fence();
                 wur[tk] = fmaf(dl_t, S1, ctab[c * 8 + 0] * dy_t);
                 dyr[tk] = fmaf(uu, S1, S2 * kLn2);                                        // S2 carries A * log2e
-                LS2_STAMP(4);
-#ifdef VIVIM_STAMPS
-                if (c < CPR - 1) ++stamp_step;
-#endif
             }
             // ---- dB / dC of the tile: the row's channels are summed in dBv / dCv; add the four rows in registers, then the
             // waves of the workgroup through LDS.  R[k], row r = the wave's total of vector 4 k + r (0-15 dB, 16-31 dC by token).
-            if constexpr (kAbl2 == 1) continue;
-            LS2_STAMP(5);
             // (the dB / dC bases: scalar loads from the argument block, requested here so that they are in when the barriers are)
             const ls_kargs qe = ls_fresh_kargs();
             float* __restrict__ dBg = ls_karg<float*>(qe, LS_OFF(BP, dB)) + b * ls_karg<int64_t>(qe, LS_OFF(BP, dB_batch_stride)) + g * ls_karg<int64_t>(qe, LS_OFF(BP, dB_group_stride));
@@ -493,9 +468,7 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))
             }
             // Both barriers sit around the slot writes: "everybody is done reading the previous tile's slots and this tile's
             // staged rows", then "slots and the next tile's rows are written".
-            LS2_STAMP(6);
             lds_barrier();
-            LS2_STAMP(7);
             if (stage_next && tid < PT) {
                 *reinterpret_cast<u32x4*>(stage + tid * 16) = sb;
                 *reinterpret_cast<u32x4*>(stage + (PT + tid) * 16) = sc;
@@ -504,7 +477,6 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))
             *reinterpret_cast<float4*>(slot + lane * 4) = float4{R[0], R[1], R[2], R[3]};
             *reinterpret_cast<float4*>(slot + (kWave + lane) * 4) = float4{R[4], R[5], R[6], R[7]};
             lds_barrier();
-            LS2_STAMP(8);
             // the next tile's checkpoints: out of the memory queue before this tile's atomics go in
             asm volatile("" : "+v"(hnxt[0]), "+v"(hnxt[1]), "+v"(hnxt[2]), "+v"(hnxt[3]));
 #pragma unroll
@@ -541,10 +513,6 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))
                     }
                 }
             }
-            LS2_STAMP(9);
-#ifdef VIVIM_STAMPS
-            ++stamp_step;
-#endif
         }
         store_span(sp);
     }
@@ -577,7 +545,7 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))
 static size_t ls2_bwd_smem(int W, int itype) {
     const int wb = itype == VIVIM_F32 ? Ls2Geom<float>::WB : Ls2Geom<bf16_t>::WB;
     const int es = itype == VIVIM_F32 ? 4 : 2;
-    return (size_t)W * wb + (size_t)W * kLsCPR * 8 * 4 + (size_t)2 * 16 * 16 * es + scan_env().ls2_smem_pad;
+    return (size_t)W * wb + (size_t)W * kLsCPR * 8 * 4 + (size_t)2 * 16 * 16 * es;
 }
 
 // Same workgroup geometry as the first generation; the plan (scan_plan.hip) has checked that every activation row is

@@ -62,8 +62,6 @@ struct BwdPlan {
 struct ScanEnv {
     int chan_waves;                // VIVIM_CHAN_WAVES: target waves of the lanes = channels segmentation
     int chan_xcd;                  // VIVIM_CHAN_XCD: force the XCD re-numbering on (1) / off (0)
-    size_t ls_smem_pad, ls2_smem_pad;   // VIVIM_LS_SMEM_PAD / VIVIM_LS2_SMEM_PAD: occupancy experiments
-    int ls_dbg;                    // VIVIM_LS_DBG: LsSeg::dbg
 };
 const ScanEnv& scan_env();
 

@@ -12,8 +12,7 @@ const ScanEnv& scan_env() {
         // VIVIM_CHAN_WAVES default 2048: swept 512 ... 8192 on the grouped cfg-2 shapes (309/144/106/64 us at 2048;
         // 377/198/130/68 at 1024; 320/167/125/70 at 4096); again with the packed token update: 293/146/101/69 at 1536,
         // 283/141/104/70 at 2048, 300/164/115/70 at 3072, 304/165/124/70 at 4096
-        return ScanEnv{num("VIVIM_CHAN_WAVES", 2048), num("VIVIM_CHAN_XCD", -1), (size_t)num("VIVIM_LS_SMEM_PAD", 0),
-                       (size_t)num("VIVIM_LS2_SMEM_PAD", 0), num("VIVIM_LS_DBG", 0)};
+        return ScanEnv{num("VIVIM_CHAN_WAVES", 2048), num("VIVIM_CHAN_XCD", -1)};
     }();
     return e;
 }
