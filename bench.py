@@ -3,7 +3,8 @@
 256x256, clip_length 5, 3 classes, per-GPU batch 3, bf16 autocast (BASELINE.json configs[1]); weak scaling
 over N GPUs (one process per GPU, RCCL gradient all-reduce overlapped with the backward by DDP buckets).
 
-    python bench.py --gpus 1 --steps 30 --warmup 5
+    python bench.py --gpus 1 --steps 30 --warmup 5            # the headline line alone
+    python bench.py --gpus 1 --steps 30 --warmup 5 --full     # + the measurements listed below
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
         bench.py --gpus N --steps K --warmup W
 
@@ -12,17 +13,25 @@ their gradients) as float32 DIR/<name>.npy; with the same arguments the inputs a
 be compared output for output.  The GPU train step is not bitwise reproducible: two runs of the same build agree to about
 1e-2 relative on logits and gradients after the default 35 bf16 steps (1e-4 on parameters), so compare with a tolerance.
 
-Rank 0 prints ONE JSON line.  Besides the contract fields it carries
+Rank 0 prints ONE JSON line.  A plain run sets up, warms up, times the steps, dumps (--dump-outputs) and prints; besides
+the contract fields its line carries what the timed region itself recorded:
   roofline      -- the dominant hot-path kernel (largest total time among the four C-ABI kernels), its
                    algorithmic bytes (vivim_amd/_lib.py:algorithmic_bytes) divided by its
                    HIP-event time, both summed over every launch inside the timed region;
                    `traffic` is the HBM bytes per launch from committed rocprofv3 --pmc passes over this command
                    (profiles/r*_bench_pmc_traffic.json), null when none is committed;
-  cpu_baseline  -- the pure-PyTorch selective_scan_ref port (oracle/ref_torch.py) timed on this host's cores
-                   on a bounded sample (N = 1 only).
+  kernels       -- launches and HIP-event time of each hot-path kernel inside the timed region.
+--full adds the measurements that take runs of their own, after the timed region (they never change the headline):
+  roofline.measured_copy_GBps -- device-to-device copy rate of this GPU, beside the nominal HBM peak;
+  comm                        -- gradient all-reduce cost and its overlap with the backward (N > 1 only);
+  roofline_by_config          -- the scan kernels alone at the stage-0 shapes of configs 2 / 3 / 5 (N = 1 only;
+                                 --no-by-config skips it);
+  cpu_baseline                -- the pure-PyTorch selective_scan_ref port (oracle/ref_torch.py) timed on this host's
+                                 cores on a bounded sample (N = 1 only; --no-cpu-baseline skips it).
 Synthetic data, random-init weights (SegFormer-b3 architecture from a local config): there is no network.
 """
 import argparse
+import functools
 import json
 import os
 import sys
@@ -50,8 +59,12 @@ def parse():
     ap.add_argument("--dtype", default="bf16", choices=["bf16", "fp16", "fp32"])
     ap.add_argument("--d-state", type=int, default=16)
     ap.add_argument("--expand", type=int, default=2)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-by-config", action="store_true", help="skip the per-config kernel timings after the timed region")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps, also measure what takes runs of its own: the device copy rate, the "
+                         "gradient exchange (N > 1), the per-config kernel timings and the CPU baseline (N = 1)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
+    ap.add_argument("--no-by-config", action="store_true",
+                    help="with --full: skip the per-config kernel timings after the timed region")
     ap.add_argument("--stock-backbone-dwconv", action="store_true",
                     help="leave the SegFormer blocks stock: Mix-FFN depthwise convs on MIOpen instead of csrc/dwconv.hip, "
                          "transformers' own DropPath")
@@ -70,13 +83,19 @@ DUMP_SEED = 1234                  # fixed: the same elements are sampled in ever
 DUMP_MAX_ELEMS = {"logits": 8 << 20, "params_sample": 1 << 20, "grads_sample": 1 << 20}   # float32: <= 40 MB in all
 
 
+@functools.lru_cache(maxsize=None)
+def _sample_index(n, k, seed):
+    """k of n positions, ascending, fixed by seed.  Drawn once per (n, k, seed): a CPU randperm of the ~60 M parameters
+    takes seconds, and the parameters and their gradients are sampled at the same positions."""
+    g = torch.Generator().manual_seed(seed)
+    return torch.randperm(n, generator=g)[:k].sort().values
+
+
 def _sample(flat, k, seed):
     """flat (1-D) whole when it has at most k elements, else k elements at fixed seeded positions (ascending)."""
     if flat.numel() <= k:
         return flat
-    g = torch.Generator().manual_seed(seed)
-    idx = torch.randperm(flat.numel(), generator=g)[:k].sort().values
-    return flat[idx.to(flat.device)]
+    return flat[_sample_index(flat.numel(), k, seed).to(flat.device)]
 
 
 def dump_outputs(out_dir, loss, logits, model):
@@ -366,11 +385,12 @@ def main():
             dump_outputs(a.dump_outputs, loss, last_out[-1], model)
         del last_out
     comm = {}
-    try:                                                       # every rank takes part; rank 0 reports
-        comm = dp.comm_probe(step_model, lambda: train_step(step_model, opt, clip, onehot, a.num_classes, amp),
-                             elapsed / a.steps * 1e3, dev)
-    except Exception as ex:
-        comm = {"error": repr(ex)[:200]}
+    if a.full:
+        try:                                                   # every rank takes part; rank 0 reports
+            comm = dp.comm_probe(step_model, lambda: train_step(step_model, opt, clip, onehot, a.num_classes, amp),
+                                 elapsed / a.steps * 1e3, dev)
+        except Exception as ex:
+            comm = {"error": repr(ex)[:200]}
 
     if rank == 0:
         frames = world * a.train_bs * a.clip_length * a.steps
@@ -427,22 +447,23 @@ def main():
                          "traffic_source": traffic_src, "traffic_stale": bool(stale), "co_limit": co, "valu_ceiling": ceiling,
                          "algorithmic_bytes_per_launch": int(per[dom][0] / per[dom][2]),
                          "launches": per[dom][2],
-                         "avg_launch_us": round(per[dom][1] / per[dom][2] * 1e6, 2),
-                         "measured_copy_GBps": measured_copy_ceiling(dev)},
+                         "avg_launch_us": round(per[dom][1] / per[dom][2] * 1e6, 2)},
             "kernels": kernels,
             # what the step holds in HBM (caching allocator peak since process start; the lanes = states family keeps 4 bytes of
             # scan checkpoints per token and channel from forward to backward -- ADVICE round 2: compare VIVIM_FWD_VARIANT=1)
             "max_memory_allocated_MB": round(torch.cuda.max_memory_allocated(dev) / 1e6, 1),
             "loss": round(float(loss), 5),
         }
+        if a.full:
+            out["roofline"]["measured_copy_GBps"] = measured_copy_ceiling(dev)
         if comm:
             out["comm"] = comm                                 # allreduce_ms, overlap_frac, n_ranks_seen (N > 1)
-        if world == 1 and not a.no_by_config:
+        if a.full and world == 1 and not a.no_by_config:
             try:
                 out["roofline_by_config"] = roofline_by_config(dev)
             except Exception as ex:                            # never lose the headline line to the extras
                 out["roofline_by_config"] = {"error": repr(ex)[:200]}
-        if world == 1 and not a.no_cpu_baseline:
+        if a.full and world == 1 and not a.no_cpu_baseline:
             out["cpu_baseline"] = cpu_baseline()
         sys.stdout.flush()
         os.write(result_fd, (json.dumps(out) + "\n").encode())

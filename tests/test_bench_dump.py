@@ -70,6 +70,13 @@ def test_bench_rejects_bad_step_counts(args, monkeypatch):
         bench.parse()
 
 
+def test_bench_full_is_opt_in(monkeypatch):
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--gpus", "1", "--steps", "3", "--warmup", "1"])
+    assert bench.parse().full is False                  # a plain run measures the headline alone
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--full"])
+    assert bench.parse().full is True
+
+
 def _run_bench(out_dir, steps):
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", str(steps), "--warmup", "1",
            "--no-cpu-baseline", "--no-by-config", "--dump-outputs", str(out_dir)]

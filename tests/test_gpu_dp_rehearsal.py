@@ -18,7 +18,7 @@ def test_bench_two_ranks_on_one_gpu():
     for port in ("29517", "29641"):                               # a second port if the first one is taken on the box
         cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr",
                "127.0.0.1", "--master-port", port, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "2",
-               "--warmup", "1", "--no-cpu-baseline", "--no-by-config"]
+               "--warmup", "1", "--full", "--no-cpu-baseline", "--no-by-config"]     # --full: the comm probe
         r = subprocess.run(cmd, cwd=ROOT, env=env, capture_output=True, text=True, timeout=600)
         if r.returncode == 0 or "in use" not in r.stderr.lower():
             break
