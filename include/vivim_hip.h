@@ -268,6 +268,42 @@ typedef struct {
     void *workspace;                         /* backward scratch (see above), 16-byte aligned; contents undefined afterwards */
 } vivim_layernorm_params;
 
+/* ---- residual add fused with the LayerNorm above (MambaLayer's `x + drop_path(branch)` followed by norm2; opt-in) ----------
+ * Write s[b] for scale[b], 1 when `scale` is NULL (the per-sample DropPath factor mask / keep).
+ *   forward : x_new[b][c][t] = x[b][c][t] + s[b] * branch[b][t][c]   (one f32 fma, rounded once to itype; channel-major like x)
+ *             y = LayerNorm over c of x_new AS STORED, token-major like `branch`; mean / rstd saved
+ *   backward: dx[b][c][t] = LNbwd(dy; x_new, mean, rstd, weight) + dres[b][c][t]   (dres: the gradient reaching x_new from later in
+ *             the network, channel-major; dy or dres may be NULL, not both), dbranch[b][t][c] = s[b] * dx (NULL: not wanted),
+ *             dweight / dbias through `workspace` exactly as vivim_layernorm_cm_bwd
+ * Add-only mode, weight == NULL: the forward writes x_new alone (y, mean, rstd are not touched); the backward writes
+ * dbranch = s * dres transposed and nothing else (dx IS dres: the caller passes it on).
+ * x, x_new, dres, dx: itype, unit token stride, 16-byte aligned rows, seqlen a whole number of 16-byte pieces.  branch, dbranch:
+ * btype, unit channel stride; btype == itype, or itype f32 with an f16 / bf16 branch (what autocast produces).  y, dy: otype =
+ * VIVIM_F32 or itype, unit channel stride.  channels <= 512; anything else returns VIVIM_ERR_UNSUPPORTED. */
+typedef struct {
+    int32_t batch, seqlen, channels;
+    int32_t itype, btype, otype;
+    float eps;
+    int32_t _pad0;
+    int64_t x_batch_stride, x_c_stride;              /* x: (batch, channels, seqlen) memory, token stride 1 */
+    int64_t x_new_batch_stride, x_new_c_stride;      /* x_new: laid out like x (forward output, backward input) */
+    int64_t branch_batch_stride, branch_token_stride;   /* branch: (batch, seqlen, channels), channel stride 1 */
+    int64_t y_batch_stride, y_token_stride;          /* y and dy: (batch, seqlen, channels), channel stride 1 */
+    int64_t dres_batch_stride, dres_c_stride;        /* dres, dx: laid out like x */
+    int64_t dx_batch_stride, dx_c_stride;
+    int64_t dbranch_batch_stride, dbranch_token_stride;
+    const void *x, *branch;                          /* forward inputs */
+    const void *scale;                               /* (batch) f32, or NULL (1) */
+    const void *weight, *bias;                       /* (channels) f32; weight NULL selects the add-only mode, bias NULL is 0 */
+    void *x_new;                                     /* written by the forward, read by the backward */
+    void *y;                                         /* forward output */
+    void *mean, *rstd;                               /* (batch, seqlen) f32: written by the forward, read by the backward */
+    const void *dy, *dres;                           /* backward inputs */
+    void *dx, *dbranch;                              /* backward outputs */
+    void *dweight, *dbias;                           /* (channels) f32 pre-zeroed, or NULL */
+    void *workspace;                                 /* vivim_add_layernorm_bwd_workspace_bytes() of scratch, 16-byte aligned */
+} vivim_add_layernorm_params;
+
 /* ---- weight-gradient products of the fused inner op's backward (mamba_ssm/ops/selective_scan_interface.py:273, 276) ------------
  * out[g][i][j] += sum_t a[g][i][t] * b[g][j][t]: both operands with unit stride along t (the grouped op keeps everything
  * channel-major), t = every token of every clip.  Replaces the two einsum calls there (ddelta_proj_weight: a = ddelta (d, B*l),
@@ -289,7 +325,7 @@ const char *vivim_last_error(void);
 
 /* sizeof() of a params struct as this library was compiled, so a foreign-language binding can assert
  * its own layout: which = 0 ssm_fwd, 1 ssm_bwd, 2 conv_fwd, 3 conv_bwd, 4 dwconv, 5 dwconv_wgrad, 6 dir, 7 conv_update,
- * 8 state_update, 9 layernorm, 10 wgrad_nt; 0 for anything else. */
+ * 8 state_update, 9 layernorm, 10 wgrad_nt, 11 add_layernorm; 0 for anything else. */
 size_t vivim_sizeof(int which);
 
 /* Tokens per checkpoint row of `x`: n_chunks = ceil(seqlen / vivim_scan_ckpt_len(f)).  Depends on the sizes and flags in
@@ -329,6 +365,9 @@ int vivim_layernorm_cm_fwd(const vivim_layernorm_params *p, void *stream);
 int vivim_layernorm_cm_bwd(const vivim_layernorm_params *p, void *stream);
 size_t vivim_layernorm_bwd_workspace_bytes(const vivim_layernorm_params *p);   /* from batch, seqlen, channels, itype */
 int vivim_wgrad_nt(const vivim_wgrad_nt_params *p, void *stream);
+int vivim_add_layernorm_cm_fwd(const vivim_add_layernorm_params *p, void *stream);
+int vivim_add_layernorm_cm_bwd(const vivim_add_layernorm_params *p, void *stream);
+size_t vivim_add_layernorm_bwd_workspace_bytes(const vivim_add_layernorm_params *p);   /* from batch, seqlen, channels, itype */
 
 /* Deterministic backward (for torch.use_deterministic_algorithms).  Same parameters, checks and results as
  * vivim_selective_scan_bwd, and the same kernel family, but every gradient that the default call adds up across

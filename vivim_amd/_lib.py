@@ -119,6 +119,17 @@ class WgradNtParams(ctypes.Structure):
                 + [(n, vp) for n in ("a", "b", "out")])
 
 
+class AddLayerNormParams(ctypes.Structure):
+    _fields_ = ([(n, i32) for n in ("batch", "seqlen", "channels", "itype", "btype", "otype")]
+                + [("eps", ctypes.c_float), ("_pad0", i32)]
+                + [(n, i64) for n in ("x_batch_stride", "x_c_stride", "x_new_batch_stride", "x_new_c_stride",
+                                      "branch_batch_stride", "branch_token_stride", "y_batch_stride", "y_token_stride",
+                                      "dres_batch_stride", "dres_c_stride", "dx_batch_stride", "dx_c_stride",
+                                      "dbranch_batch_stride", "dbranch_token_stride")]
+                + [(n, vp) for n in ("x", "branch", "scale", "weight", "bias", "x_new", "y", "mean", "rstd", "dy", "dres",
+                                     "dx", "dbranch", "dweight", "dbias", "workspace")])
+
+
 EXPORTS = ("vivim_abi_version", "vivim_last_error", "vivim_scan_chunk_len", "vivim_scan_ckpt_len", "vivim_sizeof",
            "vivim_scan_bwd_workspace_bytes", "vivim_scan_fwd_workspace_bytes", "vivim_set_tuning",
            "vivim_selective_scan_fwd", "vivim_selective_scan_bwd",
@@ -127,7 +138,8 @@ EXPORTS = ("vivim_abi_version", "vivim_last_error", "vivim_scan_chunk_len", "viv
            "vivim_layernorm_cm_fwd", "vivim_layernorm_cm_bwd", "vivim_layernorm_bwd_workspace_bytes", "vivim_wgrad_nt",
            "vivim_scan_bwd_det_workspace_bytes", "vivim_scan_bwd_det_call_workspace_bytes", "vivim_selective_scan_bwd_det",
            "vivim_causal_conv1d_bwd_det_workspace_bytes", "vivim_causal_conv1d_bwd_det",
-           "vivim_dwconv_wgrad_det_workspace_bytes", "vivim_dwconv_wgrad_det")
+           "vivim_dwconv_wgrad_det_workspace_bytes", "vivim_dwconv_wgrad_det",
+           "vivim_add_layernorm_cm_fwd", "vivim_add_layernorm_cm_bwd", "vivim_add_layernorm_bwd_workspace_bytes")
 
 _lib = None
 
@@ -170,7 +182,9 @@ def lib():
                          ("vivim_causal_conv1d_update", ConvUpdateParams),
                          ("vivim_selective_state_update", StateUpdateParams),
                          ("vivim_layernorm_cm_fwd", LayerNormParams), ("vivim_layernorm_cm_bwd", LayerNormParams),
-                         ("vivim_wgrad_nt", WgradNtParams)):
+                         ("vivim_wgrad_nt", WgradNtParams),
+                         ("vivim_add_layernorm_cm_fwd", AddLayerNormParams),
+                         ("vivim_add_layernorm_cm_bwd", AddLayerNormParams)):
             fn = getattr(L, name)
             fn.argtypes = [ctypes.POINTER(st), vp]
             fn.restype = ctypes.c_int
@@ -187,11 +201,13 @@ def lib():
             getattr(L, name).restype = ctypes.c_int
         L.vivim_layernorm_bwd_workspace_bytes.argtypes = [ctypes.POINTER(LayerNormParams)]
         L.vivim_layernorm_bwd_workspace_bytes.restype = ctypes.c_size_t
+        L.vivim_add_layernorm_bwd_workspace_bytes.argtypes = [ctypes.POINTER(AddLayerNormParams)]
+        L.vivim_add_layernorm_bwd_workspace_bytes.restype = ctypes.c_size_t
         if L.vivim_abi_version() != 8:
             raise ImportError("libvivim_hip.so ABI version mismatch")
         for which, st in enumerate((SsmFwdParams, SsmBwdParams, ConvFwdParams, ConvBwdParams, DwConvParams,
                                     DwConvWgradParams, DirParams, ConvUpdateParams, StateUpdateParams, LayerNormParams,
-                                    WgradNtParams)):
+                                    WgradNtParams, AddLayerNormParams)):
             if L.vivim_sizeof(which) != ctypes.sizeof(st):
                 raise ImportError(f"struct layout mismatch for {st.__name__}: "
                                   f"C {L.vivim_sizeof(which)} vs ctypes {ctypes.sizeof(st)}")
@@ -205,6 +221,14 @@ _ISIZE = {F32: 4, F16: 2, BF16: 2}
 def algorithmic_bytes(name, P):
     """Compulsory HBM traffic of one launch: every tensor of the op read or written once
     (the checkpoint tensor x is an implementation choice and is excluded)."""
+    if name.startswith("vivim_add_layernorm"):
+        n = P.batch * P.seqlen * P.channels
+        if not P.weight:                                               # add-only: x, branch, x_new / dres, dbranch
+            return n * ((2 if name.endswith("fwd") else 1) * _ISIZE[P.itype] + _ISIZE[P.btype])
+        if name.endswith("fwd"):                                       # x, branch, x_new, y + mean, rstd
+            return n * (2 * _ISIZE[P.itype] + _ISIZE[P.btype] + _ISIZE[P.otype]) + 8 * P.batch * P.seqlen + 8 * P.channels
+        res = (_ISIZE[P.itype] if P.dres else 0) + (_ISIZE[P.otype] if P.dy else 0) + (_ISIZE[P.btype] if P.dbranch else 0)
+        return n * (2 * _ISIZE[P.itype] + res) + 8 * P.batch * P.seqlen + 12 * P.channels   # x_new, dx + what is present
     if name.startswith("vivim_selective_scan"):
         f = P.f if name.endswith("bwd") else P
         s = _ISIZE[f.itype]

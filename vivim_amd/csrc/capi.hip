@@ -34,6 +34,8 @@ int ssm_bwd_det_dispatch(const vivim_ssm_bwd_params&, void* det_ws, size_t det_w
 bool layernorm_dispatch(const vivim_layernorm_params&, bool bwd, hipStream_t);   // layernorm.hip
 size_t layernorm_bwd_workspace_bytes(const vivim_layernorm_params&);
 bool wgrad_nt_dispatch(const vivim_wgrad_nt_params&, hipStream_t);                 // wgrad.hip
+bool add_layernorm_dispatch(const vivim_add_layernorm_params&, bool bwd, hipStream_t);   // add_layernorm.hip
+size_t add_layernorm_bwd_workspace_bytes(const vivim_add_layernorm_params&);
 size_t scan_fwd_workspace_bytes(const vivim_ssm_fwd_params&);
 }  // namespace vivim
 
@@ -127,6 +129,7 @@ size_t vivim_sizeof(int which) {
         case 8: return sizeof(vivim_state_update_params);
         case 9: return sizeof(vivim_layernorm_params);
         case 10: return sizeof(vivim_wgrad_nt_params);
+        case 11: return sizeof(vivim_add_layernorm_params);
     }
     return 0;
 }
@@ -418,6 +421,61 @@ int vivim_wgrad_nt(const vivim_wgrad_nt_params* p, void* stream) {
     if (!vivim::wgrad_nt_dispatch(*p, static_cast<hipStream_t>(stream)))
         return fail(VIVIM_ERR_UNSUPPORTED, "wgrad_nt not implemented for type %d", p->itype);
     return after_launch("wgrad_nt");
+}
+
+static bool aligned16(const void* q) { return (reinterpret_cast<uintptr_t>(q) & 15) == 0; }
+
+// what the forward and the backward of the residual-add LayerNorm share; `e` <- elements per 16-byte vector of x / x_new / dres / dx
+static int check_add_layernorm(const vivim_add_layernorm_params* p, int64_t* e) {
+    VCHECK(p != nullptr);
+    VCHECK(dtype_ok(p->itype) && dtype_ok(p->btype) && (p->weight == nullptr || dtype_ok(p->otype)));
+    VCHECK(p->batch > 0 && p->seqlen > 0 && p->channels > 0 && p->batch <= 65535);
+    if (p->channels > 512)
+        return fail(VIVIM_ERR_UNSUPPORTED, "add_layernorm_cm: more than 512 channels do not fit the backward's two LDS tiles");
+    if (p->btype != p->itype && p->itype != VIVIM_F32)
+        return fail(VIVIM_ERR_UNSUPPORTED, "add_layernorm_cm: branch type %d with x type %d is not built (the branch has x's type, or x is f32)",
+                    p->btype, p->itype);
+    if (p->weight && p->otype != VIVIM_F32 && p->otype != p->itype)
+        return fail(VIVIM_ERR_UNSUPPORTED, "add_layernorm_cm: output type %d with x type %d is not built (f32 or x's type)", p->otype, p->itype);
+    *e = p->itype == VIVIM_F32 ? 4 : 8;
+    VCHECK(p->seqlen % *e == 0);
+    return VIVIM_OK;
+}
+
+int vivim_add_layernorm_cm_fwd(const vivim_add_layernorm_params* p, void* stream) {
+    int64_t e = 0;
+    if (int rc = check_add_layernorm(p, &e)) return rc;
+    VCHECK(p->x && p->branch && p->x_new && aligned16(p->x) && aligned16(p->x_new));
+    VCHECK(p->x_batch_stride % e == 0 && p->x_c_stride % e == 0 && p->x_new_batch_stride % e == 0 && p->x_new_c_stride % e == 0);
+    if (p->weight) VCHECK(p->y && p->mean && p->rstd);
+    if (!vivim::add_layernorm_dispatch(*p, false, static_cast<hipStream_t>(stream)))
+        return fail(VIVIM_ERR_UNSUPPORTED, "add_layernorm_cm_fwd not implemented for x type %d / branch type %d / output type %d", p->itype,
+                    p->btype, p->otype);
+    return after_launch("add_layernorm_cm_fwd");
+}
+
+size_t vivim_add_layernorm_bwd_workspace_bytes(const vivim_add_layernorm_params* p) {
+    return p && p->batch > 0 && p->seqlen > 0 && p->channels > 0 ? vivim::add_layernorm_bwd_workspace_bytes(*p) : 0;
+}
+
+int vivim_add_layernorm_cm_bwd(const vivim_add_layernorm_params* p, void* stream) {
+    int64_t e = 0;
+    if (int rc = check_add_layernorm(p, &e)) return rc;
+    if (p->dres) VCHECK(aligned16(p->dres) && p->dres_batch_stride % e == 0 && p->dres_c_stride % e == 0);
+    if (p->weight) {
+        VCHECK(p->x_new && aligned16(p->x_new) && p->mean && p->rstd && (p->dy || p->dres));
+        VCHECK(p->x_new_batch_stride % e == 0 && p->x_new_c_stride % e == 0);
+        VCHECK(p->dx && aligned16(p->dx) && p->dx_batch_stride % e == 0 && p->dx_c_stride % e == 0);
+        if ((p->dweight || p->dbias) && !p->workspace)
+            return fail(VIVIM_ERR_INVALID,
+                        "add_layernorm_cm_bwd: dweight / dbias need the workspace (vivim_add_layernorm_bwd_workspace_bytes)");
+    } else {
+        VCHECK(p->dres && p->dbranch);                 // add-only: dbranch = scale * dres, dx is dres itself
+    }
+    if (!vivim::add_layernorm_dispatch(*p, true, static_cast<hipStream_t>(stream)))
+        return fail(VIVIM_ERR_UNSUPPORTED, "add_layernorm_cm_bwd not implemented for x type %d / branch type %d / output type %d", p->itype,
+                    p->btype, p->otype);
+    return after_launch("add_layernorm_cm_bwd");
 }
 
 }  // extern "C"

@@ -5,7 +5,17 @@ vivim_layernorm_params) -- the two norms around the Mamba call of MambaLayer (mo
                                             -> (B, L, C) contiguous, the dtype F.layer_norm would return (f32 under autocast)
 The transpose the ATen path does with a copy kernel in front of its row kernel is the kernel's own read pattern here.
 `supported(x, weight)` says whether the fast path applies; the caller falls back to F.layer_norm otherwise (other layouts:
-the ATen kernel is already the right one for token-major rows)."""
+the ATen kernel is already the right one for token-major rows).
+
+The residual add in front of the norm, fused with it (csrc/add_layernorm.hip; vivim_add_layernorm_params) -- MambaLayer's
+`x + drop_path(branch)` followed by norm2, and the layer's last add (MambaLayer(fused_add_norm=True)):
+
+    add_layer_norm_cm(x, branch, weight, bias, eps, scale=None) -> (x_new, y)
+                                            x as above; branch: (B, L, C) with unit channel stride, x's dtype (or f16 / bf16 with an
+                                            f32 x: the autocast case); scale: (B,) f32 per-sample DropPath factor or None
+                                            x_new = x + scale[b] * branch in x's dtype and layout, y = layer_norm(x_new)
+    add_cm(x, branch, scale=None) -> x_new  the add alone
+`add_norm_supported(x, branch, weight)` says whether they apply; the caller keeps its composition of torch ops otherwise."""
 import ctypes
 
 import torch
@@ -98,3 +108,160 @@ def layer_norm_cm(x, weight, bias, eps=1e-5):
     """F.layer_norm(x, (C,), weight, bias, eps) for a channel-major x; output dtype as ATen's under the ambient autocast state."""
     out_dtype = torch.float32 if torch.is_autocast_enabled() else x.dtype
     return _LayerNormCM.apply(x, weight, bias, eps, out_dtype)
+
+
+def _cm_ok(t, e):
+    """t: (B, L, C) view of channel-major memory the kernels can move in 16-byte vectors along the tokens."""
+    return (t.stride(1) == 1 and t.shape[1] % e == 0 and t.stride(0) % e == 0 and t.stride(2) % e == 0
+            and t.data_ptr() % 16 == 0 and t.stride(2) >= t.shape[1])
+
+
+def add_norm_supported(x, branch, weight=None):
+    """Whether add_layer_norm_cm (weight given) / add_cm (weight None) take these tensors.  False under
+    torch.use_deterministic_algorithms, as `supported`: the reduce kernel adds into dweight / dbias with float atomics."""
+    if _lib.deterministic():
+        return False
+    if not (x.is_cuda and x.dim() == 3 and x.dtype in _ITYPE and branch.device == x.device and branch.shape == x.shape):
+        return False
+    if weight is not None and weight.dtype != torch.float32:
+        return False
+    if not (branch.dtype == x.dtype or (x.dtype == torch.float32 and branch.dtype in (torch.float16, torch.bfloat16))):
+        return False
+    C = x.shape[2]
+    return C <= 512 and _cm_ok(x, 16 // x.element_size()) and branch.stride(2) == 1 and branch.stride(1) >= C
+
+
+def _add_params(x, branch, scale):
+    B, L, C = x.shape
+    P = _lib.AddLayerNormParams()
+    P.batch, P.seqlen, P.channels, P.itype, P.btype, P.otype = B, L, C, _ITYPE[x.dtype], _ITYPE[branch.dtype], _ITYPE[x.dtype]
+    P.scale = scale.data_ptr() if scale is not None else None
+    return P
+
+
+def _check_scale(scale, x):
+    if scale is not None and not (scale.dtype == torch.float32 and scale.shape == (x.shape[0],) and scale.is_contiguous()
+                                  and scale.device == x.device):
+        raise ValueError("scale must be a contiguous (batch,) float32 tensor on x's device")
+
+
+def _as_cm(g, like):
+    """The gradient of a channel-major tensor, in that layout and dtype (it usually arrives so: a view of the next layer's
+    contiguous (B, C, ...) gradient)."""
+    if g.dtype != like.dtype:
+        g = g.to(like.dtype)
+    if not _cm_ok(g, 16 // g.element_size()):
+        g = g.transpose(1, 2).contiguous().transpose(1, 2)
+    return g
+
+
+def _add_forward(x, branch, scale, P):
+    """The part of the forward call both ops share: x, branch and a fresh x_new in x's layout."""
+    B, L, C = x.shape
+    x_new = _lib.empty((B, C, L), x.dtype, x.device).transpose(1, 2)
+    P.x_batch_stride, P.x_c_stride = x.stride(0), x.stride(2)
+    P.x_new_batch_stride, P.x_new_c_stride = C * L, L
+    P.branch_batch_stride, P.branch_token_stride = branch.stride(0), branch.stride(1)
+    P.x, P.branch, P.x_new = x.data_ptr(), branch.data_ptr(), x_new.data_ptr()
+    return x_new
+
+
+class _AddLayerNormCM(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x, branch, weight, bias, scale, eps, out_dtype):
+        B, L, C = x.shape
+        P = _add_params(x, branch, scale)
+        P.otype, P.eps = _ITYPE[out_dtype], eps
+        x_new = _add_forward(x, branch, scale, P)
+        y = _lib.empty((B, L, C), out_dtype, x.device)
+        stats = _lib.empty((2, B, L), torch.float32, x.device)              # mean, rstd
+        P.y_batch_stride, P.y_token_stride = L * C, C
+        P.weight, P.bias = weight.data_ptr(), (bias.data_ptr() if bias is not None else None)
+        P.y, P.mean = y.data_ptr(), stats.data_ptr()
+        P.rstd = P.mean + 4 * B * L
+        _launch("vivim_add_layernorm_cm_fwd", P, x.device)
+        ctx.save_for_backward(x_new, weight, stats, scale)
+        ctx.eps, ctx.has_bias, ctx.out_dtype, ctx.branch_dtype = eps, bias is not None, out_dtype, branch.dtype
+        ctx.set_materialize_grads(False)                                    # an unused output's gradient stays None: the kernel skips it
+        return x_new, y
+
+    @staticmethod
+    def backward(ctx, dres, dy):
+        if dres is None and dy is None:
+            return (None,) * 7
+        x_new, weight, stats, scale = ctx.saved_tensors
+        B, L, C = x_new.shape
+        P = _lib.AddLayerNormParams()
+        P.batch, P.seqlen, P.channels, P.eps = B, L, C, ctx.eps
+        P.itype, P.btype, P.otype = _ITYPE[x_new.dtype], _ITYPE[ctx.branch_dtype], _ITYPE[ctx.out_dtype]
+        P.scale = scale.data_ptr() if scale is not None else None
+        P.x_new_batch_stride, P.x_new_c_stride = x_new.stride(0), x_new.stride(2)
+        P.x_new, P.weight, P.mean = x_new.data_ptr(), weight.data_ptr(), stats.data_ptr()
+        P.rstd = P.mean + 4 * B * L
+        dwb = None
+        if dy is not None:
+            if dy.dtype != ctx.out_dtype:
+                dy = dy.to(ctx.out_dtype)
+            if dy.stride(2) != 1 or dy.stride(1) < C:
+                dy = dy.contiguous()
+            P.dy, P.y_batch_stride, P.y_token_stride = dy.data_ptr(), dy.stride(0), dy.stride(1)
+            dwb = _lib.zeros(2 * C, x_new.device)                            # dweight, dbias: one zero fill
+            P.dweight = dwb.data_ptr()
+            P.dbias = P.dweight + 4 * C if ctx.has_bias else None
+            ws = _lib.empty((_lib.lib().vivim_add_layernorm_bwd_workspace_bytes(ctypes.byref(P)) // 4,), torch.float32, x_new.device)
+            P.workspace = ws.data_ptr()                                      # per-tile dweight / dbias partial sums
+        if dres is not None:
+            dres = _as_cm(dres, x_new)
+            P.dres, P.dres_batch_stride, P.dres_c_stride = dres.data_ptr(), dres.stride(0), dres.stride(2)
+        # dx in x's own layout, dbranch token-major
+        dx = _lib.empty((B, C, L), x_new.dtype, x_new.device).transpose(1, 2)
+        P.dx, P.dx_batch_stride, P.dx_c_stride = dx.data_ptr(), C * L, L
+        dbranch = None
+        if ctx.needs_input_grad[1]:
+            dbranch = _lib.empty((B, L, C), ctx.branch_dtype, x_new.device)
+            P.dbranch, P.dbranch_batch_stride, P.dbranch_token_stride = dbranch.data_ptr(), L * C, C
+        _launch("vivim_add_layernorm_cm_bwd", P, x_new.device)
+        return (dx, dbranch, (dwb[:C] if dwb is not None else None),
+                (dwb[C:] if dwb is not None and ctx.has_bias else None), None, None, None)
+
+
+class _AddCM(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x, branch, scale):
+        P = _add_params(x, branch, scale)
+        x_new = _add_forward(x, branch, scale, P)
+        _launch("vivim_add_layernorm_cm_fwd", P, x.device)
+        ctx.save_for_backward(scale)
+        ctx.branch_dtype = branch.dtype
+        return x_new
+
+    @staticmethod
+    def backward(ctx, dres):
+        scale, = ctx.saved_tensors
+        if not ctx.needs_input_grad[1]:
+            return dres, None, None
+        dres = _as_cm(dres, dres)
+        B, L, C = dres.shape
+        dbranch = _lib.empty((B, L, C), ctx.branch_dtype, dres.device)
+        P = _lib.AddLayerNormParams()
+        P.batch, P.seqlen, P.channels = B, L, C
+        P.itype, P.btype, P.otype = _ITYPE[dres.dtype], _ITYPE[ctx.branch_dtype], _ITYPE[dres.dtype]
+        P.scale = scale.data_ptr() if scale is not None else None
+        P.dres, P.dres_batch_stride, P.dres_c_stride = dres.data_ptr(), dres.stride(0), dres.stride(2)
+        P.dbranch, P.dbranch_batch_stride, P.dbranch_token_stride = dbranch.data_ptr(), L * C, C
+        _launch("vivim_add_layernorm_cm_bwd", P, dres.device)
+        return dres, dbranch, None                                           # dx is dres itself: no kernel
+
+
+def add_layer_norm_cm(x, branch, weight, bias, eps=1e-5, scale=None):
+    """(x + scale[:, None, None] * branch, F.layer_norm of that sum as stored) for a channel-major x and a token-major branch;
+    the sum in x's dtype and layout, the norm's dtype as layer_norm_cm's."""
+    _check_scale(scale, x)
+    out_dtype = torch.float32 if torch.is_autocast_enabled() else x.dtype
+    return _AddLayerNormCM.apply(x, branch, weight, bias, scale, eps, out_dtype)
+
+
+def add_cm(x, branch, scale=None):
+    """x + scale[:, None, None] * branch in x's dtype and (channel-major) layout."""
+    _check_scale(scale, x)
+    return _AddCM.apply(x, branch, scale)

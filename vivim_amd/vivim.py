@@ -47,6 +47,14 @@ class DropPath(nn.Module):
         mask = x.new_empty((x.shape[0],) + (1,) * (x.dim() - 1)).bernoulli_(keep).div_(keep)
         return x * mask
 
+    def sample_scale(self, x):
+        """The per-sample factor mask / keep that forward would multiply x by, as a (B,) f32 tensor for a kernel that applies
+        it itself (layernorm.add_layer_norm_cm / add_cm); None when this module is the identity (eval, or drop_prob 0)."""
+        if self.drop_prob == 0.0 or not self.training:
+            return None
+        keep = 1.0 - self.drop_prob
+        return torch.empty(x.shape[0], dtype=torch.float32, device=x.device).bernoulli_(keep).div_(keep)
+
 
 def _init_weights(m):
     # modeling/vivim.py:83-96 / 132-145
@@ -131,9 +139,10 @@ class MambaLayer(nn.Module):
     (modeling/vivim.py:111-159)."""
 
     def __init__(self, dim, d_state=16, d_conv=4, expand=2, mlp_ratio=4, drop=0.0, drop_path=0.0,
-                 act_layer=nn.GELU):
+                 act_layer=nn.GELU, fused_add_norm=False):
         super().__init__()
         self.dim = dim
+        self.fused_add_norm = fused_add_norm
         self.norm1 = nn.LayerNorm(dim)
         self.mamba = Mamba(d_model=dim, d_state=d_state, d_conv=d_conv, expand=expand, bimamba_type="v3")
         self.drop_path = DropPath(drop_path) if drop_path > 0.0 else nn.Identity()
@@ -155,9 +164,31 @@ class MambaLayer(nn.Module):
         B, C, nf, H, W = x.shape
         assert C == self.dim
         x_flat = x.reshape(B, C, nf * H * W).transpose(-1, -2)          # frame-major tokens (vivim.py:151-153)
-        x_flat = x_flat + self.drop_path(self.mamba(self._norm(self.norm1, x_flat), nframes=nf))
+        branch = self.mamba(self._norm(self.norm1, x_flat), nframes=nf)
+        if self.fused_add_norm and self._add_norm_applies(x_flat, branch, self.norm2.weight):
+            # residual add + norm2 as one kernel (csrc/add_layernorm.hip): the channel-major stream and the token-major branch
+            # meet in the kernel's LDS tile, DropPath is a per-sample factor inside it, and the sum is normalised before it
+            # leaves the chip; the layer's last add is the same kernel without the norm, and its result is (B, C, L) memory
+            # again, so the final reshape is a view
+            x_flat, h = _ln.add_layer_norm_cm(x_flat, branch, self.norm2.weight, self.norm2.bias, self.norm2.eps,
+                                              self._drop_scale(x_flat))
+            branch = self.mlp(h, nf, H, W)
+            if self._add_norm_applies(x_flat, branch, None):
+                x_flat = _ln.add_cm(x_flat, branch, self._drop_scale(x_flat))
+            else:
+                x_flat = x_flat + self.drop_path(branch)
+            return x_flat.transpose(-1, -2).reshape(B, C, nf, H, W)
+        x_flat = x_flat + self.drop_path(branch)
         x_flat = x_flat + self.drop_path(self.mlp(self._norm(self.norm2, x_flat), nf, H, W))
         return x_flat.transpose(-1, -2).reshape(B, C, nf, H, W)
+
+    @staticmethod
+    def _add_norm_applies(x_flat, branch, weight):
+        return (_ln.add_norm_supported(x_flat, branch, weight) and _ln.worthwhile(x_flat)
+                and not os.environ.get("VIVIM_NO_FUSED_LAYERNORM"))
+
+    def _drop_scale(self, x_flat):
+        return self.drop_path.sample_scale(x_flat) if isinstance(self.drop_path, DropPath) else None
 
 
 def _encoder_parts(backbone):
