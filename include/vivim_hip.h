@@ -352,6 +352,13 @@ size_t vivim_scan_fwd_workspace_bytes(const vivim_ssm_fwd_params *f);
 int vivim_set_tuning(int which, int value);
 
 int vivim_selective_scan_fwd(const vivim_ssm_fwd_params *p, void *stream);
+/* The forward for a call no backward follows (inference, torch.no_grad): the same kernels, family choice and token-axis
+ * cut as vivim_selective_scan_fwd on the same tensors with an `out` laid out like `delta`, hence bit-identical results,
+ * but no checkpoint tensor is written and, when z is given, no `out`: p->x must be NULL; with z, p->out_z is required and
+ * p->out must be NULL; without z, p->out is required.  `last_state` is NULL or a contiguous fp32 (batch, dim, dstate)
+ * buffer that receives the state after the last token (what the full call leaves in the last row of x).  Same workspace
+ * contract and query (vivim_scan_fwd_workspace_bytes), same vivim_set_tuning(0, ...) override. */
+int vivim_selective_scan_fwd_lean(const vivim_ssm_fwd_params *p, void *last_state, void *stream);
 int vivim_selective_scan_bwd(const vivim_ssm_bwd_params *p, void *stream);
 int vivim_causal_conv1d_fwd(const vivim_conv_fwd_params *p, void *stream);
 int vivim_causal_conv1d_bwd(const vivim_conv_bwd_params *p, void *stream);

@@ -1,6 +1,7 @@
 #!/usr/bin/env python3
 """Inference frames/s of the Vivim model (the reference's inference.py:294-325, 414 times a
 no_grad forward per clip without a device sync; here the timed region is bracketed by torch.cuda.synchronize()).
+Also prints the allocator's peak over the timed loop (VIVIM_NO_LEAN_FWD=1: the same run on the full scan forward).
     python tools/infer_fps.py [--batch 1] [--clip-length 5] [--image-size 256] [--dtype bf16] [--iters 30]"""
 import argparse, json, os, sys, time
 import torch
@@ -23,6 +24,7 @@ with torch.no_grad(), torch.autocast("cuda", dtype=amp, enabled=amp != torch.flo
     for _ in range(5):
         model(clip)
     torch.cuda.synchronize()
+    torch.cuda.reset_peak_memory_stats()
     t0 = time.perf_counter()
     for _ in range(a.iters):
         out = model(clip)
@@ -30,4 +32,6 @@ with torch.no_grad(), torch.autocast("cuda", dtype=amp, enabled=amp != torch.flo
 dt = (time.perf_counter() - t0) / a.iters
 print(json.dumps({"metric": "inference frames/sec (no_grad forward, eval)", "value": round(a.batch * a.clip_length / dt, 2),
                   "ms_per_clip_batch": round(dt * 1e3, 3), "batch": a.batch, "clip_length": a.clip_length,
-                  "image_size": a.image_size, "dtype": a.dtype, "finite": bool(torch.isfinite(out).all())}))
+                  "image_size": a.image_size, "dtype": a.dtype, "finite": bool(torch.isfinite(out).all()),
+                  "max_memory_allocated_MiB": round(torch.cuda.max_memory_allocated() / 2 ** 20, 1),
+                  "lean_fwd": os.environ.get("VIVIM_NO_LEAN_FWD", "0") != "1"}))

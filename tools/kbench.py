@@ -4,7 +4,9 @@ BASELINE.json config and prints achieved algorithmic GB/s (SURVEY.md section 8d 
 Usage: python tools/kbench.py [--config 2|3|5] [--iters 20] [--stages 0,1,2,3] [--kernels sf,sb,cf,cb] [--groups 3]
 --groups 3: the grouped v3 shapes (three directions side by side: dim = 3 * d_inner, n_groups = 3, contiguous rows).
 --cold S: cycle S independent input sets (S >= 3 and S * set size > the 256 MB Infinity Cache: no launch finds its inputs
-in a cache).  --ceiling: also print the device-to-device copy rate (the practical HBM ceiling)."""
+in a cache).  --ceiling: also print the device-to-device copy rate (the practical HBM ceiling).
+--lean: for kernel key sf, time the lean forward (selective_scan_cuda.fwd_lean: no checkpoints, out_z only) beside the full
+one in the same process -- full, lean, then full again, so that the two full lines show the run-to-run spread."""
 import argparse
 import os
 import sys
@@ -24,6 +26,8 @@ DIMS, STRIDES = [64, 128, 320, 512], [4, 8, 16, 32]
 
 
 def alg_bytes(kind, B, D, L, N, s, G=1, W=4):
+    if kind == "sf_lean":   # u, delta, z, out_z
+        return 4 * B * D * L * s + 2 * B * G * N * L * s + 4 * (D * N + 2 * D)
     if kind == "sf":
         return 5 * B * D * L * s + 2 * B * G * N * L * s + 4 * (D * N + 2 * D)
     if kind == "sb":   # out_z not requested: 8 activation streams
@@ -55,6 +59,7 @@ def main():
     ap.add_argument("--groups", type=int, default=1)
     ap.add_argument("--cold", type=int, default=1)
     ap.add_argument("--ceiling", action="store_true")
+    ap.add_argument("--lean", action="store_true", help="sf: also time the lean forward (full, lean, full again)")
     ap.add_argument("--pad", type=int, default=0, help="extra elements between the rows of the inputs (row stride L + pad)")
     a = ap.parse_args()
     B, nf, img, N, expand, dt = CONFIGS[a.config]
@@ -94,6 +99,10 @@ def main():
             u, delta, z, dout, Bm, Cm, out, x, dz = nxt()
             return ss.fwd(u, delta, A, Bm, Cm, Dv, z, bias, True)
 
+        def sf_lean():
+            u, delta, z, dout, Bm, Cm, out, x, dz = nxt()
+            return ss.fwd_lean(u, delta, A, Bm, Cm, Dv, z, bias, True)
+
         def sb():
             u, delta, z, dout, Bm, Cm, out, x, dz = nxt()
             return ss.bwd(u, delta, A, Bm, Cm, Dv, z, bias, dout, x, out, dz, True, False)
@@ -105,8 +114,11 @@ def main():
             s_ = nxt()
             return cc.causal_conv1d_bwd(s_[0], w, cb, s_[3], None, True)
 
-        runs = {"sf": sf, "sb": sb, "cf": cf, "cb": cbw}
+        runs = {"sf": sf, "sf_lean": sf_lean, "sb": sb, "cf": cf, "cb": cbw}
+        keys = []
         for k in a.kernels.split(","):
+            keys += ["sf", "sf_lean", "sf"] if (k == "sf" and a.lean) else [k]
+        for k in keys:
             t = timeit(runs[k], a.iters)
             nb = alg_bytes(k, B, D, L, N, s, G)
             cut = ""

@@ -6,3 +6,4 @@ There is no CPU or PyTorch fallback: importing the op modules without the built
 vivim_amd/csrc/libvivim_hip.so raises ImportError on first use.
 """
 __version__ = "0.1.0"
+from .generation import InferenceParams  # noqa: E402,F401  (a plain dataclass: importing it loads neither torch nor the library)

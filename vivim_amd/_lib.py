@@ -132,7 +132,7 @@ class AddLayerNormParams(ctypes.Structure):
 
 EXPORTS = ("vivim_abi_version", "vivim_last_error", "vivim_scan_chunk_len", "vivim_scan_ckpt_len", "vivim_sizeof",
            "vivim_scan_bwd_workspace_bytes", "vivim_scan_fwd_workspace_bytes", "vivim_set_tuning",
-           "vivim_selective_scan_fwd", "vivim_selective_scan_bwd",
+           "vivim_selective_scan_fwd", "vivim_selective_scan_bwd", "vivim_selective_scan_fwd_lean",
            "vivim_causal_conv1d_fwd", "vivim_causal_conv1d_bwd", "vivim_dwconv_fwd", "vivim_dwconv_wgrad",
            "vivim_dir_scatter", "vivim_dir_gather", "vivim_causal_conv1d_update", "vivim_selective_state_update",
            "vivim_layernorm_cm_fwd", "vivim_layernorm_cm_bwd", "vivim_layernorm_bwd_workspace_bytes", "vivim_wgrad_nt",
@@ -188,6 +188,8 @@ def lib():
             fn = getattr(L, name)
             fn.argtypes = [ctypes.POINTER(st), vp]
             fn.restype = ctypes.c_int
+        L.vivim_selective_scan_fwd_lean.argtypes = [ctypes.POINTER(SsmFwdParams), vp, vp]
+        L.vivim_selective_scan_fwd_lean.restype = ctypes.c_int
         L.vivim_scan_bwd_det_workspace_bytes.restype = ctypes.c_size_t
         L.vivim_scan_bwd_det_workspace_bytes.argtypes = [ctypes.POINTER(SsmFwdParams)]
         for name, st in (("vivim_scan_bwd_det_call_workspace_bytes", SsmBwdParams),
@@ -235,6 +237,8 @@ def algorithmic_bytes(name, P):
         act = f.batch * f.dim * f.seqlen * s
         bc = (f.batch * f.n_groups * f.dstate * f.seqlen) if f.is_variable_B else f.dim * f.dstate
         has_z = bool(f.z)
+        if name.endswith("fwd_lean"):                             # u, delta, out | u, delta, z, out_z
+            return (4 if has_z else 3) * act + 2 * bc * (s if f.is_variable_B else 4) + 4 * (f.dim * f.dstate + 2 * f.dim)
         if name.endswith("fwd"):
             n_act = 3 + (2 if has_z else 0)                       # u, delta, out (+ z, out_z)
             return n_act * act + 2 * bc * (s if f.is_variable_B else 4) + 4 * (f.dim * f.dstate + 2 * f.dim)
@@ -359,6 +363,24 @@ def call_det(name, params, det_ws, det_ws_bytes, stream):
     nonzero return."""
     L = lib()
     rc = getattr(L, name)(ctypes.byref(params), vp(det_ws), ctypes.c_size_t(det_ws_bytes), vp(stream))
+    if rc != 0:
+        raise RuntimeError(L.vivim_last_error().decode())
+    if GUARD:
+        check_guards(name)
+
+
+def call_lean_fwd(params, last_state, stream):
+    """Enqueue vivim_selective_scan_fwd_lean (params, last_state pointer or None, stream); profiled and guarded like `call`."""
+    L = lib()
+    name = "vivim_selective_scan_fwd_lean"
+    if _profile is not None and _profile[1]:
+        e0, e1 = _event(), _event()
+        e0.record()
+        rc = L.vivim_selective_scan_fwd_lean(ctypes.byref(params), vp(last_state), vp(stream))
+        e1.record()
+        _profile[0].append((name, algorithmic_bytes(name, params), e0, e1))
+    else:
+        rc = L.vivim_selective_scan_fwd_lean(ctypes.byref(params), vp(last_state), vp(stream))
     if rc != 0:
         raise RuntimeError(L.vivim_last_error().decode())
     if GUARD:

@@ -13,6 +13,7 @@ bool conv_bwd_dispatch(const vivim_conv_bwd_params&, hipStream_t);
 bool conv_cl_fwd_dispatch(const vivim_conv_fwd_params&, hipStream_t);                // conv1d_cl.hip (channel-last)
 bool conv_cl_bwd_dispatch(const vivim_conv_bwd_params&, hipStream_t);
 bool ssm_fwd_dispatch(const vivim_ssm_fwd_params&, hipStream_t);
+bool ssm_fwd_lean_dispatch(const vivim_ssm_fwd_params&, void* last_state, hipStream_t);   // scan_plan.hip
 bool dwconv_fwd_dispatch(const vivim_dwconv_params&, hipStream_t);
 bool dwconv_wgrad_dispatch(const vivim_dwconv_wgrad_params&, hipStream_t);
 template <bool GATHER> bool dir_dispatch(const vivim_dir_params&, hipStream_t);     // dirmap.hip
@@ -62,18 +63,34 @@ static int after_launch(const char* what) {
 
 static bool dtype_ok(int t) { return t == VIVIM_F32 || t == VIVIM_F16 || t == VIVIM_BF16; }
 
-static int check_ssm_fwd(const vivim_ssm_fwd_params* p, bool is_bwd) {
+// mode: the full forward, the backward (its `f` half), or the lean forward (no checkpoints; out_z alone when z is given)
+enum SsmCheck { kSsmFwd, kSsmBwd, kSsmFwdLean };
+static int check_ssm_fwd(const vivim_ssm_fwd_params* p, SsmCheck mode) {
+    const bool is_bwd = mode == kSsmBwd;
     VCHECK(p != nullptr);
     VCHECK(dtype_ok(p->itype));
     VCHECK(p->batch > 0 && p->dim > 0 && p->seqlen > 0 && p->dstate > 0 && p->n_groups > 0);
     VCHECK(p->dstate <= 256);                       // selective_scan.cpp:262
     VCHECK(p->dim % p->n_groups == 0);
     VCHECK(p->u && p->delta && p->A && p->B && p->C);
-    VCHECK(p->x != nullptr || (is_bwd && p->seqlen <= vivim::scan_ckpt_len(*p)));
-    if (!is_bwd) VCHECK(p->out != nullptr);
-    if (p->z) {
-        if (!is_bwd) VCHECK(p->out_z != nullptr);
-        else VCHECK(p->out != nullptr);             // selective_scan.cpp:423 (saved out needed for dz)
+    if (mode == kSsmFwdLean) {
+        if (p->x != nullptr)
+            return fail(VIVIM_ERR_INVALID, "selective_scan_fwd_lean: x must be NULL (this entry point writes no checkpoints; "
+                        "vivim_selective_scan_fwd is the call that fills x)");
+        if (p->z) {
+            VCHECK(p->out_z != nullptr);
+            if (p->out != nullptr)
+                return fail(VIVIM_ERR_INVALID, "selective_scan_fwd_lean: with z only out_z is written, out must be NULL");
+        } else {
+            VCHECK(p->out != nullptr);
+        }
+    } else {
+        VCHECK(p->x != nullptr || (is_bwd && p->seqlen <= vivim::scan_ckpt_len(*p)));
+        if (!is_bwd) VCHECK(p->out != nullptr);
+        if (p->z) {
+            if (!is_bwd) VCHECK(p->out_z != nullptr);
+            else VCHECK(p->out != nullptr);             // selective_scan.cpp:423 (saved out needed for dz)
+        }
     }
     if (p->is_variable_B != p->is_variable_C)
         return fail(VIVIM_ERR_UNSUPPORTED,
@@ -135,15 +152,22 @@ size_t vivim_sizeof(int which) {
 }
 
 int vivim_selective_scan_fwd(const vivim_ssm_fwd_params* p, void* stream) {
-    if (int rc = check_ssm_fwd(p, false)) return rc;
+    if (int rc = check_ssm_fwd(p, kSsmFwd)) return rc;
     if (!vivim::ssm_fwd_dispatch(*p, static_cast<hipStream_t>(stream)))
         return fail(VIVIM_ERR_UNSUPPORTED, "selective_scan_fwd not implemented for input type %d", p->itype);
     return after_launch("selective_scan_fwd");
 }
 
+int vivim_selective_scan_fwd_lean(const vivim_ssm_fwd_params* p, void* last_state, void* stream) {
+    if (int rc = check_ssm_fwd(p, kSsmFwdLean)) return rc;
+    if (!vivim::ssm_fwd_lean_dispatch(*p, last_state, static_cast<hipStream_t>(stream)))
+        return fail(VIVIM_ERR_UNSUPPORTED, "selective_scan_fwd_lean not implemented for input type %d", p->itype);
+    return after_launch("selective_scan_fwd_lean");
+}
+
 static int check_ssm_bwd(const vivim_ssm_bwd_params* p) {
     VCHECK(p != nullptr);
-    if (int rc = check_ssm_fwd(&p->f, true)) return rc;
+    if (int rc = check_ssm_fwd(&p->f, kSsmBwd)) return rc;
     VCHECK(p->dout && p->du && p->ddelta && p->dA && p->dB && p->dC);
     VCHECK((p->f.D == nullptr) == (p->dD == nullptr));
     VCHECK((p->f.delta_bias == nullptr) == (p->ddelta_bias == nullptr));

@@ -23,13 +23,18 @@
 //
 // ssm_fwd_generic_kernel -- any dstate, constant B/C: a wave owns R channels and ALL states (carry in a
 //   per-wave LDS row, shuffle-based scan); slower, used only off Vivim's path.
+//
+// LEAN (vivim_selective_scan_fwd_lean: a forward no backward follows) is a compile-time twin of both kernels with the
+// same arithmetic and no checkpoint store; with z it has no `out` store either.  `p.x` is then NOT the checkpoint
+// tensor: it is null or a (batch, dim, dstate) fp32 buffer that receives the state after the last token -- the value
+// the full kernel puts into the last checkpoint row.
 #include "scan_plan.cuh"
 
 namespace vivim {
 
 constexpr int kScanWaves = 4;   // waves per workgroup (independent of each other)
 
-template <typename T, int K, int R, bool HAS_Z, bool VAR_BC>
+template <typename T, int K, int R, bool HAS_Z, bool VAR_BC, bool LEAN = false>
 __global__ void __launch_bounds__(kScanWaves * kWave) ssm_fwd_generic_kernel(const vivim_ssm_fwd_params p) {
     constexpr int TILE = kWave * K;
     const int lane = threadIdx.x & 63;
@@ -125,7 +130,7 @@ __global__ void __launch_bounds__(kScanWaves * kWave) ssm_fwd_generic_kernel(con
                 if (lane == kWave - 1) {
                     const float cnew = fmaf(Pi, cin, Hi);     // state after the step's last token
                     carry[r * N + n] = cnew;
-                    if (r < nvalid)
+                    if (!LEAN && r < nvalid)
                         xck[(((int64_t)b * p.dim + d[r]) * nsteps + step) * N + n] = cnew;
                 }
                 wave_lds_fence();
@@ -134,8 +139,10 @@ __global__ void __launch_bounds__(kScanWaves * kWave) ssm_fwd_generic_kernel(con
 #pragma unroll
         for (int r = 0; r < R; ++r) {
             if (r >= nvalid) break;
-            T* out = static_cast<T*>(p.out) + b * p.out_batch_stride + d[r] * p.out_d_stride + t0;
-            store_k<T, K>(out, nv, y[r]);
+            if (!(LEAN && HAS_Z)) {
+                T* out = static_cast<T*>(p.out) + b * p.out_batch_stride + d[r] * p.out_d_stride + t0;
+                store_k<T, K>(out, nv, y[r]);
+            }
             if (HAS_Z) {
                 float zf[K], oz[K];
                 load_k<T, K>(static_cast<const T*>(p.z) + b * p.z_batch_stride + d[r] * p.z_d_stride + t0, nv, zf);
@@ -146,13 +153,17 @@ __global__ void __launch_bounds__(kScanWaves * kWave) ssm_fwd_generic_kernel(con
             }
         }
     }
+    if (LEAN && xck) {                                // the carry row holds the state after the last step: the last checkpoint
+        for (int i = lane; i < nvalid * N; i += kWave)
+            xck[((int64_t)b * p.dim + d0) * N + i] = carry[i];
+    }
 }
 
 
 // ------------------------------------------------------------------------------------------------
 constexpr int kLdsRow = 65;        // [slot][k][lane] tiles, rows padded to 65 floats: conflict-free both ways
 
-template <typename T, int K, int NS, bool HAS_Z, int MINW>
+template <typename T, int K, int NS, bool HAS_Z, int MINW, bool LEAN = false>
 __global__ void __launch_bounds__(NS * kWave, MINW) ssm_fwd_nsplit_kernel(const vivim_ssm_fwd_params p) {
     constexpr int R = kNsR;
     constexpr int TILE = kWave * K;
@@ -251,6 +262,9 @@ __global__ void __launch_bounds__(NS * kWave, MINW) ssm_fwd_nsplit_kernel(const 
         unx = load_vec<T, IPT>(pu + tn, tn < L);
         dnx = load_vec<T, IPT>(pdl + tn, tn < L);
         const bool in = t0 < L;
+        // LEAN: the lane that holds the state after token L - 1 during the last step (the last checkpoint row's lane)
+        const bool last_step = LEAN && !more;
+        const int last_lane = (nck - step * CPS) * LPC - 1;
 
         float dl[R][K], w[R][K], yp[R][K], dsum[R];
 #pragma unroll
@@ -310,13 +324,17 @@ __global__ void __launch_bounds__(NS * kWave, MINW) ssm_fwd_nsplit_kernel(const 
                 for (int q = 0; q < CPS; ++q) {                              // state after every kChunk tokens
                     const float v = read_lane(hend, (q + 1) * LPC - 1);
                     const int row = step * CPS + q;
-                    if (lane == 0 && r < nvalid && row < nck)
+                    if (!LEAN && lane == 0 && r < nvalid && row < nck)
                         xck[(((int64_t)b * p.dim + d[r]) * nck + row) * N + n] = v;
                     if (q == CPS - 1) {                                      // state after the step
                         wave_lds_fence();
                         if (lane == 0) s_carry[n * R + r] = v;
                         wave_lds_fence();
                     }
+                }
+                if (last_step) {                                             // uniform: once per (state, channel) and launch
+                    const float v = read_lane(hend, last_lane);
+                    if (lane == 0 && r < nvalid && xck) xck[((int64_t)b * p.dim + d[r]) * N + n] = v;
                 }
             }
         };
@@ -350,7 +368,7 @@ __global__ void __launch_bounds__(NS * kWave, MINW) ssm_fwd_nsplit_kernel(const 
                 y[i] = acc;
             }
             if (pr < nvalid) {
-                store_vec<T, IPT>(pout + tp, tp < L, y);
+                if (!(LEAN && HAS_Z)) store_vec<T, IPT>(pout + tp, tp < L, y);
                 if (HAS_Z) {
                     float zf[IPT];
                     unpack(zr, zf);
@@ -366,23 +384,24 @@ __global__ void __launch_bounds__(NS * kWave, MINW) ssm_fwd_nsplit_kernel(const 
 }
 
 // 8 waves per workgroup, dstate / 8 states per wave, K tokens per lane (the plan: scan_plan.hip).
-void launch_fwd_nsplit(const vivim_ssm_fwd_params& p, const FwdPlan& q, hipStream_t stream) {
+void launch_fwd_nsplit(const vivim_ssm_fwd_params& p, const FwdPlan& q, hipStream_t stream, bool lean) {
     const int cpg = p.dim / p.n_groups;
     const dim3 grid(((cpg + kNsR - 1) / kNsR) * p.n_groups, p.batch), block(8 * kWave);
     with_itype(p.itype, [&](auto t) {
         typedef decltype(t) T;
-        if (q.K == 4) {
-            if (p.z) hipLaunchKernelGGL((ssm_fwd_nsplit_kernel<T, 4, 8, true, 2>), grid, block, 0, stream, p);
-            else     hipLaunchKernelGGL((ssm_fwd_nsplit_kernel<T, 4, 8, false, 2>), grid, block, 0, stream, p);
+        auto launch = [&](auto kernel) { hipLaunchKernelGGL(kernel, grid, block, 0, stream, p); };
+        if (lean) {
+            if (q.K == 4) { if (p.z) launch(ssm_fwd_nsplit_kernel<T, 4, 8, true, 2, true>); else launch(ssm_fwd_nsplit_kernel<T, 4, 8, false, 2, true>); }
+            else          { if (p.z) launch(ssm_fwd_nsplit_kernel<T, 8, 8, true, 2, true>); else launch(ssm_fwd_nsplit_kernel<T, 8, 8, false, 2, true>); }
         } else {
-            if (p.z) hipLaunchKernelGGL((ssm_fwd_nsplit_kernel<T, 8, 8, true, 2>), grid, block, 0, stream, p);
-            else     hipLaunchKernelGGL((ssm_fwd_nsplit_kernel<T, 8, 8, false, 2>), grid, block, 0, stream, p);
+            if (q.K == 4) { if (p.z) launch(ssm_fwd_nsplit_kernel<T, 4, 8, true, 2>); else launch(ssm_fwd_nsplit_kernel<T, 4, 8, false, 2>); }
+            else          { if (p.z) launch(ssm_fwd_nsplit_kernel<T, 8, 8, true, 2>); else launch(ssm_fwd_nsplit_kernel<T, 8, 8, false, 2>); }
         }
     });
 }
 
 static_assert(kWave * 4 == kChunk, "generic kernel step must equal the checkpoint chunk");
-void launch_fwd_generic(const vivim_ssm_fwd_params& p, hipStream_t stream) {
+void launch_fwd_generic(const vivim_ssm_fwd_params& p, hipStream_t stream, bool lean) {
     constexpr int K = 4, R = 2;
     const int cpg = p.dim / p.n_groups;
     const int sets = ((cpg + R - 1) / R) * p.n_groups;
@@ -391,12 +410,13 @@ void launch_fwd_generic(const vivim_ssm_fwd_params& p, hipStream_t stream) {
     const bool var = p.is_variable_B;   // capi enforces is_variable_B == is_variable_C
     with_itype(p.itype, [&](auto t) {
         typedef decltype(t) T;
-        if (p.z) {
-            if (var) hipLaunchKernelGGL((ssm_fwd_generic_kernel<T, K, R, true, true>), grid, block, smem, stream, p);
-            else     hipLaunchKernelGGL((ssm_fwd_generic_kernel<T, K, R, true, false>), grid, block, smem, stream, p);
+        auto launch = [&](auto kernel) { hipLaunchKernelGGL(kernel, grid, block, smem, stream, p); };
+        if (lean) {
+            if (p.z) { if (var) launch(ssm_fwd_generic_kernel<T, K, R, true, true, true>); else launch(ssm_fwd_generic_kernel<T, K, R, true, false, true>); }
+            else     { if (var) launch(ssm_fwd_generic_kernel<T, K, R, false, true, true>); else launch(ssm_fwd_generic_kernel<T, K, R, false, false, true>); }
         } else {
-            if (var) hipLaunchKernelGGL((ssm_fwd_generic_kernel<T, K, R, false, true>), grid, block, smem, stream, p);
-            else     hipLaunchKernelGGL((ssm_fwd_generic_kernel<T, K, R, false, false>), grid, block, smem, stream, p);
+            if (p.z) { if (var) launch(ssm_fwd_generic_kernel<T, K, R, true, true>); else launch(ssm_fwd_generic_kernel<T, K, R, true, false>); }
+            else     { if (var) launch(ssm_fwd_generic_kernel<T, K, R, false, true>); else launch(ssm_fwd_generic_kernel<T, K, R, false, false>); }
         }
     });
 }

@@ -20,6 +20,10 @@
 //     inflow plus sum(delta); a carry kernel chains them (h_in[s+1] = exp2(A*log2e*sum_s) * h_in[s] + H_s); PASS 2
 //     recomputes the recurrence from the true inflow and produces out / out_z and the checkpoints x.  The state
 //     is re-derived instead of stored: 2 exp per state update instead of a 16-float-per-token round trip.
+//   * LEAN (vivim_selective_scan_fwd_lean: a forward no backward follows) is a compile-time twin of PASS 2: the same
+//     token update, no checkpoint stores in the block loop, no `out` store when z is given.  `p.x` is then null or a
+//     (batch, dim, dstate) fp32 buffer: the last segment's waves store their registers there after the tile loop --
+//     the state after token L - 1, which the full kernel puts into the last checkpoint row.
 #include "scan_plan.cuh"
 
 namespace vivim {
@@ -166,7 +170,7 @@ __device__ __forceinline__ kparams_t fresh_params() {
 
 // (amdgpu_waves_per_eu(2): the f32 / z / 64-state PASS 2 otherwise takes 255 VGPRs + 4 AGPRs = one wave per SIMD; with the
 // bound it fits 253 and the other 22 instantiations compile as before, the 16-state ones register for register)
-template <typename T, int PASS, bool HAS_Z, int NST = kChN>
+template <typename T, int PASS, bool HAS_Z, int NST = kChN, bool LEAN = false>
 __global__ void __launch_bounds__(kChWaves * kWave) __attribute__((amdgpu_num_sgpr(kChSgprLimit), amdgpu_waves_per_eu(2)))
 ssm_fwd_chan_kernel(const vivim_ssm_fwd_params p, const FwdSeg sg) {
     constexpr int N = NST;                            // 16, or 64 as four chunks of 16 per token (the scalar sets hold one chunk)
@@ -228,7 +232,7 @@ ssm_fwd_chan_kernel(const vivim_ssm_fwd_params p, const FwdSeg sg) {
     const float* __restrict__ bc = sg.BC + (int64_t)(b * p.n_groups + g) * (sg.Lpad + 1) * 32 * NCH;
     const int ck = sg.ck;
     const int nck = (L + ck - 1) / ck;
-    float* __restrict__ xlane = static_cast<float*>(p.x) + ((int64_t)b * p.dim + d) * nck * N;   // per-lane (VGPRs)
+    float* __restrict__ xlane = LEAN ? nullptr : static_cast<float*>(p.x) + ((int64_t)b * p.dim + d) * nck * N;   // per-lane (VGPRs)
 
     // cooperative tile I/O: instruction i moves rows i*16 + lane/4, 16-byte column lane%4
     const int io_col = lane % LPR;
@@ -345,7 +349,7 @@ ssm_fwd_chan_kernel(const vivim_ssm_fwd_params p, const FwdSeg sg) {
             if (PASS == 2) {
                 // state after every ck tokens and after the last one: always the last token of a block
                 const int tl = tb + TB - 1;
-                if (((tl + 1) & (ck - 1)) == 0 || tl == L - 1) {
+                if (!LEAN && (((tl + 1) & (ck - 1)) == 0 || tl == L - 1)) {
                     float* xr = xlane + (tl / ck) * N;
 #pragma unroll
                     for (int n = 0; n < N; ++n) xr[n] = (n & 1) ? hp[n / 2].y : hp[n / 2].x;
@@ -367,14 +371,18 @@ ssm_fwd_chan_kernel(const vivim_ssm_fwd_params p, const FwdSeg sg) {
             const int t = t0 + io_col * EPV;
             if (t < L) {
                 if (NCH != 1) issue_z_loads(tile);
-                const int64_t so = q->out_d_stride;
-                T* go = static_cast<T*>(q->out) + b * q->out_batch_stride + (c0 + io_row0) * so + t;
+                constexpr bool ST_OUT = !(LEAN && HAS_Z);
+                const int64_t so = ST_OUT ? q->out_d_stride : 0;
+                T* go = ST_OUT ? static_cast<T*>(q->out) + b * q->out_batch_stride + (c0 + io_row0) * so + t : nullptr;
                 const int64_t soz = HAS_Z ? q->out_z_d_stride : 0;
                 T* goz = HAS_Z ? static_cast<T*>(q->out_z) + b * q->out_z_batch_stride + (c0 + io_row0) * soz + t : nullptr;
 #pragma unroll
                 for (int i = 0; i < NIO; ++i) {
                     const int off = (i * RPI + io_row0) * ROWB + io_col * 16;
                     float y[EPV];
+                    // 64 states, lean, 16-bit z: without the `out` stores between the rows hipcc unpacks several rows of z at once
+                    // and runs out of registers (f16: 2 VGPRs spilled); a row's z becomes visible to it only here
+                    if (LEAN && HAS_Z && NCH != 1 && sizeof(T) == 2) asm volatile("" : "+v"(gz[i].v));
                     if (sizeof(T) == 4) {
                         const float4 a = *reinterpret_cast<const float4*>(tile_u + off);
                         y[0] = a.x; y[1] = a.y; y[2] = a.z; y[3] = a.w;
@@ -387,7 +395,7 @@ ssm_fwd_chan_kernel(const vivim_ssm_fwd_params p, const FwdSeg sg) {
                     union { T e[EPV]; v4 v; } co;
 #pragma unroll
                     for (int k = 0; k < EPV; ++k) co.e[k] = from_f32<T>(y[k]);
-                    *reinterpret_cast<v4*>(go + i * RPI * so) = co.v;
+                    if (ST_OUT) *reinterpret_cast<v4*>(go + i * RPI * so) = co.v;
                     if (HAS_Z) {
                         float zf[EPV];
                         unpack(gz[i].r, zf);
@@ -395,6 +403,8 @@ ssm_fwd_chan_kernel(const vivim_ssm_fwd_params p, const FwdSeg sg) {
                         for (int k = 0; k < EPV; ++k) co.e[k] = from_f32<T>(y[k] * zf[k] * sigmoidf_fast(zf[k]));   // fwd_kernel.cuh:290
                         *reinterpret_cast<v4*>(goz + i * RPI * soz) = co.v;
                     }
+                    // 64 states, lean, z: without the `out` stores between them hipcc converts several rows at once and runs out
+                    // of registers (f16: 2 VGPRs spilled); one row at a time, as the full kernel ends up doing
                 }
             }
             wave_lds_fence();
@@ -402,6 +412,16 @@ ssm_fwd_chan_kernel(const vivim_ssm_fwd_params p, const FwdSeg sg) {
         asm volatile("" : : "v"(l2_touch));              // the touch load must not be optimised away (consumed only now)
         tile_regs_to_lds();                              // tile + 1: its loads had a whole tile to land
         wave_lds_fence();
+    }
+    if (PASS == 2 && LEAN && tile_hi == ntiles) {          // the last segment: its registers hold the state after token L - 1
+        kparams_t q = fresh_params();
+        float* __restrict__ xl = static_cast<float*>(q->x);
+        if (xl) {
+            xl += ((int64_t)b * q->dim + d) * N;
+#pragma unroll
+            for (int n = 0; n < N; n += 4)                 // (the row is 64-byte aligned: N * 4 bytes per channel)
+                *reinterpret_cast<float4*>(xl + n) = float4{hp[n / 2].x, hp[n / 2].y, hp[n / 2 + 1].x, hp[n / 2 + 1].y};
+        }
     }
     if (PASS == 1) {
         float* Hs = sg.H + (((int64_t)b * p.dim + d) * sg.S + seg) * N;
@@ -489,7 +509,7 @@ __global__ void __launch_bounds__(kWave) ssm_fwd_carry64_kernel(const vivim_ssm_
 }
 
 // The B / C repack, then (segmented) PASS 1 + carry, then PASS 2, on the plan's cut of the token axis (scan_plan.hip).
-void launch_fwd_chan(const vivim_ssm_fwd_params& p, const FwdPlan& q, hipStream_t stream) {
+void launch_fwd_chan(const vivim_ssm_fwd_params& p, const FwdPlan& q, hipStream_t stream, bool lean) {
     FwdSeg sg = {q.S, q.seg, nullptr, nullptr, static_cast<const float*>(p.workspace), q.Lpad, q.ck, q.xcd};
     if (q.S > 1) {
         sg.H = static_cast<float*>(p.workspace) + q.bc_floats;
@@ -507,8 +527,13 @@ void launch_fwd_chan(const vivim_ssm_fwd_params& p, const FwdPlan& q, hipStream_
                 hipLaunchKernelGGL((ssm_fwd_chan_kernel<T, 1, false, 64>), grid, block, 0, stream, p, sg);
                 hipLaunchKernelGGL(ssm_fwd_carry64_kernel, dim3((unsigned)(p.batch * p.dim)), dim3(kWave), 0, stream, p, sg);
             }
-            if (p.z) hipLaunchKernelGGL((ssm_fwd_chan_kernel<T, 2, true, 64>), grid, block, 0, stream, p, sg);
-            else     hipLaunchKernelGGL((ssm_fwd_chan_kernel<T, 2, false, 64>), grid, block, 0, stream, p, sg);
+            if (lean) {
+                if (p.z) hipLaunchKernelGGL((ssm_fwd_chan_kernel<T, 2, true, 64, true>), grid, block, 0, stream, p, sg);
+                else     hipLaunchKernelGGL((ssm_fwd_chan_kernel<T, 2, false, 64, true>), grid, block, 0, stream, p, sg);
+            } else {
+                if (p.z) hipLaunchKernelGGL((ssm_fwd_chan_kernel<T, 2, true, 64>), grid, block, 0, stream, p, sg);
+                else     hipLaunchKernelGGL((ssm_fwd_chan_kernel<T, 2, false, 64>), grid, block, 0, stream, p, sg);
+            }
             return;
         }
         if (sg.S > 1) {
@@ -516,8 +541,13 @@ void launch_fwd_chan(const vivim_ssm_fwd_params& p, const FwdPlan& q, hipStream_
             const size_t carry_lds = (size_t)sg.S * (kChN + 1) * sizeof(float);      // <= 34 KB (S <= 512)
             hipLaunchKernelGGL(ssm_fwd_carry_kernel, dim3((unsigned)(p.batch * p.dim)), dim3(kWave), carry_lds, stream, p, sg);
         }
-        if (p.z) hipLaunchKernelGGL((ssm_fwd_chan_kernel<T, 2, true>), grid, block, 0, stream, p, sg);
-        else     hipLaunchKernelGGL((ssm_fwd_chan_kernel<T, 2, false>), grid, block, 0, stream, p, sg);
+        if (lean) {
+            if (p.z) hipLaunchKernelGGL((ssm_fwd_chan_kernel<T, 2, true, kChN, true>), grid, block, 0, stream, p, sg);
+            else     hipLaunchKernelGGL((ssm_fwd_chan_kernel<T, 2, false, kChN, true>), grid, block, 0, stream, p, sg);
+        } else {
+            if (p.z) hipLaunchKernelGGL((ssm_fwd_chan_kernel<T, 2, true>), grid, block, 0, stream, p, sg);
+            else     hipLaunchKernelGGL((ssm_fwd_chan_kernel<T, 2, false>), grid, block, 0, stream, p, sg);
+        }
     });
 }
 

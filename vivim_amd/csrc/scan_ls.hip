@@ -496,8 +496,12 @@ __global__ void __launch_bounds__(256) ssm_ls_carry_kernel(const float* __restri
 // One loop over (tile, channel) steps like the backward: the running state of the row's kLsCPR channels lives in
 // wave-private LDS (one float per lane and channel), a step's inputs are requested one step ahead, its outputs are stored at
 // the start of the next step.  No barrier: waves are independent.
+// LEAN (vivim_selective_scan_fwd_lean: a forward no backward follows) is a compile-time twin of PASS 2 without the
+// checkpoint store, and without the `out` store when z is given.  `p.x` is then null or a (batch, dim, dstate) fp32
+// buffer: the waves of the last segment copy the running state out of LDS after the tile loop -- the state after
+// token L - 1, which the full kernel puts into the last checkpoint row.
 // =========================================================================================================================
-template <typename T, int NS, int PASS, bool HAS_Z>
+template <typename T, int NS, int PASS, bool HAS_Z, bool LEAN = false>
 __global__ void __launch_bounds__(256) ssm_ls_fwd_kernel(const vivim_ssm_fwd_params p, const LsSeg sg) {
     typedef LsGeom<NS> G;
     constexpr int RPS = G::RPS, CPW = G::CPW, CPR = kLsCPR;
@@ -571,9 +575,9 @@ __global__ void __launch_bounds__(256) ssm_ls_fwd_kernel(const vivim_ssm_fwd_par
     auto flush = [&]() __attribute__((always_inline)) {
         if (PASS == 2) {
             const ls_kargs qs = ls_fresh_kargs();
-            to.st(qs, p_chu, p_t, p_st, p_o);
+            if (!(LEAN && HAS_Z)) to.st(qs, p_chu, p_t, p_st, p_o);
             if (HAS_Z) toz.st(qs, p_chu, p_t, p_st, p_oz);
-            tx.st(qs, p_chu, p_ck * NS + n, p_ckst, p_h);
+            if (!LEAN) tx.st(qs, p_chu, p_ck * NS + n, p_ckst, p_h);
         }
     };
     float Bv[16], Cv[16];
@@ -646,6 +650,22 @@ __global__ void __launch_bounds__(256) ssm_ls_fwd_kernel(const vivim_ssm_fwd_par
         }
     }
     flush();
+    if (PASS == 2 && LEAN && tile_hi == ntiles) {             // the last segment: the state after token L - 1
+        // (the lane's place is worked out again from the thread index: kept across the tile loop, the row's channel and the
+        // state cost the loop five VGPRs and the 16- and 32-state instantiations one wave per SIMD)
+        const ls_kargs q = ls_fresh_kargs();
+        float* __restrict__ xl = static_cast<float*>(ls_karg<void*>(q, LS_OFF(FP, x)));
+        if (xl) {
+            int t2 = threadIdx.x;
+            asm volatile("" : "+v"(t2));
+            const int row2 = (t2 & 63) >> 4;
+            const int n2 = (row2 % RPS) * 16 + (t2 & 15), d2 = dwave + (row2 / RPS) * CPR;
+            const float* cs2 = lds_state + (t2 >> 6) * (CPR * 2 * kWave) + (t2 & 63);
+            xl += ((int64_t)b * ls_karg<int>(q, LS_OFF(FP, dim)) + d2) * NS + n2;
+            for (int c = 0; c < CPR; ++c)
+                if (d2 + c < d_end) xl[c * NS] = cs2[(c * 2 + 0) * kWave];
+        }
+    }
     if (PASS == 1) {
         for (int c = 0; c < CPR; ++c) {
             const int d = dwave + rowch + c;
@@ -736,7 +756,7 @@ void launch_ls_bwd(const vivim_ssm_bwd_params& p, const BwdPlan& q, hipStream_t 
     if (q.ls2) launch_ls2_bwd(p, sg, q.W, stream, det);
 }
 
-void launch_ls_fwd(const vivim_ssm_fwd_params& p, const FwdPlan& q, hipStream_t stream) {
+void launch_ls_fwd(const vivim_ssm_fwd_params& p, const FwdPlan& q, hipStream_t stream, bool lean) {
     const LsSeg sg = ls_seg(p.workspace, p, q.S, q.seg, q.bc_vec);
     const int cpg = p.dim / p.n_groups;
     const int PW = 4;
@@ -752,8 +772,13 @@ void launch_ls_fwd(const vivim_ssm_fwd_params& p, const FwdPlan& q, hipStream_t 
             hipLaunchKernelGGL((ssm_ls_carry_kernel<false>), dim3((unsigned)((nthr + 255) / 256)), dim3(256), 0, stream,
                                static_cast<const float*>(p.A), p.A_d_stride, p.A_dstate_stride, p.batch, p.dim, p.dstate, sg);
         }
-        if (p.z) hipLaunchKernelGGL((ssm_ls_fwd_kernel<T, NS, 2, true>), grid, block, 0, stream, p, sg);
-        else     hipLaunchKernelGGL((ssm_ls_fwd_kernel<T, NS, 2, false>), grid, block, 0, stream, p, sg);
+        if (lean) {
+            if (p.z) hipLaunchKernelGGL((ssm_ls_fwd_kernel<T, NS, 2, true, true>), grid, block, 0, stream, p, sg);
+            else     hipLaunchKernelGGL((ssm_ls_fwd_kernel<T, NS, 2, false, true>), grid, block, 0, stream, p, sg);
+        } else {
+            if (p.z) hipLaunchKernelGGL((ssm_ls_fwd_kernel<T, NS, 2, true>), grid, block, 0, stream, p, sg);
+            else     hipLaunchKernelGGL((ssm_ls_fwd_kernel<T, NS, 2, false>), grid, block, 0, stream, p, sg);
+        }
     });
 }
 

@@ -91,10 +91,12 @@ template <typename K> inline int occupancy_query(K kernel, int W, size_t smem, i
 }
 
 // Family launches (kernel files).  Each issues exactly the launches of its plan.
-void launch_fwd_nsplit(const vivim_ssm_fwd_params&, const FwdPlan&, hipStream_t);     // scan_fwd.hip
-void launch_fwd_generic(const vivim_ssm_fwd_params&, hipStream_t);
-void launch_fwd_chan(const vivim_ssm_fwd_params&, const FwdPlan&, hipStream_t);       // scan_fwd_chan.hip
-void launch_ls_fwd(const vivim_ssm_fwd_params&, const FwdPlan&, hipStream_t);         // scan_ls.hip
+// `lean`: the variant of the output pass without checkpoint stores (and without the `out` store when z is given); the
+// params' `x` is then null or the (batch, dim, dstate) fp32 buffer that receives the state after the last token.
+void launch_fwd_nsplit(const vivim_ssm_fwd_params&, const FwdPlan&, hipStream_t, bool lean = false);   // scan_fwd.hip
+void launch_fwd_generic(const vivim_ssm_fwd_params&, hipStream_t, bool lean = false);
+void launch_fwd_chan(const vivim_ssm_fwd_params&, const FwdPlan&, hipStream_t, bool lean = false);     // scan_fwd_chan.hip
+void launch_ls_fwd(const vivim_ssm_fwd_params&, const FwdPlan&, hipStream_t, bool lean = false);       // scan_ls.hip
 // `det`: the deterministic variant (scan_det_layout in scan_plan.hip), with p's reduced outputs pointing into the slot workspace.
 void launch_ls_bwd(const vivim_ssm_bwd_params&, const BwdPlan&, hipStream_t, bool det = false);
 void launch_ls2_bwd(const vivim_ssm_bwd_params&, const LsSeg&, int W, hipStream_t, bool det = false);   // scan_ls2.hip

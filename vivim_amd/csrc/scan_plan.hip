@@ -275,6 +275,30 @@ bool ssm_fwd_dispatch(const vivim_ssm_fwd_params& p, hipStream_t s) {
     return false;
 }
 
+// The lean forward (vivim_selective_scan_fwd_lean): no checkpoints, no `out` beside `out_z`.  It is planned as the full call
+// on the same tensors would be -- same family, same cut of the token axis, hence the same bits -- with the `out` the full
+// call would have been given: one laid out like delta (what both Python wrappers allocate).  The kernels get `last_state`
+// (null, or fp32 (batch, dim, dstate)) in the place of `x`.
+bool ssm_fwd_lean_dispatch(const vivim_ssm_fwd_params& p, void* last_state, hipStream_t s) {
+    vivim_ssm_fwd_params f = p;
+    if (p.z) {
+        f.out = const_cast<void*>(p.delta);          // (planning only: nothing is written through it)
+        f.out_batch_stride = p.delta_batch_stride;
+        f.out_d_stride = p.delta_d_stride;
+    }
+    const FwdPlan q = plan_scan_fwd(f, true);
+    f = p;
+    f.x = last_state;
+    switch (q.family) {
+        case FwdFamily::chan: launch_fwd_chan(f, q, s, true); return true;
+        case FwdFamily::states: launch_ls_fwd(f, q, s, true); return true;
+        case FwdFamily::nsplit: launch_fwd_nsplit(f, q, s, true); return true;
+        case FwdFamily::generic: launch_fwd_generic(f, s, true); return true;
+        case FwdFamily::none: break;
+    }
+    return false;
+}
+
 // ---- backward ----------------------------------------------------------------------------------------------------------
 // Lanes = states workgroup width: 16 * W channels (dstate 16) of one group share the dB / dC reduction.
 static int ls_bwd_waves(const vivim_ssm_fwd_params& f) {

@@ -8,8 +8,14 @@ Deliberate differences:
     chunk/stack re-ordering raises for clips whose token count is not 5 equal chunks; here the
     frame-major -> pixel-major permutation is an exact reshape for any nframes dividing seqlen.
   * `step` / `allocate_inference_cache` (mamba_simple.py:356-413) are the stock single-direction decode step of the
-    reference (forward-direction parameters only), here on the single-token HIP kernels; the `inference_params` cache
-    plumbing of `forward` (mamba_simple.py:188-200) is not built -- Vivim never passes it.
+    reference (forward-direction parameters only), here on the single-token HIP kernels.
+  * `forward(inference_params=...)` is the reference's cache plumbing (mamba_simple.py:196-201, :311-353): the first call
+    (seqlen_offset == 0) is the PREFILL -- the forward-direction path over the whole prompt (conv1d + SiLU, x_proj,
+    dt_proj, the scan with z, D and delta_bias; like the reference, not the v3 composition), which leaves the last d_conv
+    pre-conv columns in conv_state and the scan's final state in ssm_state; later calls (seqlen_offset > 0) are `step`.
+    Under torch.no_grad the prefill's scan is the lean forward (no checkpoints, out_z only).  A prompt shorter than d_conv
+    left-pads conv_state with zeros -- what stepping through it from a fresh cache leaves; the reference's `copy_` of a
+    too-narrow slice raises there.
 """
 import math
 
@@ -20,8 +26,8 @@ import torch.nn.functional as F
 import os
 
 from .dirmap import combine_directions, stack_directions
-from .causal_conv1d_interface import causal_conv1d_update
-from .selective_scan_interface import mamba_inner_fn_no_out_proj, mamba_inner_grouped_fn_no_out_proj
+from .causal_conv1d_interface import causal_conv1d_fn, causal_conv1d_update
+from .selective_scan_interface import mamba_inner_fn_no_out_proj, mamba_inner_grouped_fn_no_out_proj, selective_scan_fn
 from .selective_state_update import selective_state_update
 
 _DIRECTIONS = ("", "_b", "_s")     # forward in time, backward in time, spatial (pixel-major) order
@@ -167,10 +173,16 @@ class Mamba(nn.Module):
             getattr(self, "D" + sfx).float(), delta_bias=dt_proj.bias.float(), delta_softplus=True)
 
     def forward(self, hidden_states, inference_params=None, nframes=None):
-        """hidden_states: (B, L, d_model) with L = nframes * H * W in frame-major order -> same shape."""
-        if inference_params is not None:
-            raise NotImplementedError("decode-time inference cache is outside Vivim's path")
+        """hidden_states: (B, L, d_model) with L = nframes * H * W in frame-major order -> same shape.
+        inference_params (any object with `seqlen_offset` and `key_value_memory_dict`, e.g. vivim_amd.InferenceParams):
+        the forward-direction recurrence with its states cached per layer_idx -- the prefill over the whole prompt when
+        seqlen_offset == 0, one `step` otherwise (mamba_simple.py:196-201)."""
         batch, seqlen, _ = hidden_states.shape
+        if inference_params is not None:
+            conv_state, ssm_state = self._get_states_from_cache(inference_params, batch)
+            if inference_params.seqlen_offset > 0:
+                return self.step(hidden_states, conv_state, ssm_state)[0]      # the states are advanced in place
+            return self._prefill(hidden_states, conv_state, ssm_state)
         nf = self.nframes if nframes is None else nframes
         if seqlen % nf != 0:
             raise ValueError(f"seqlen {seqlen} is not a multiple of nframes {nf}")
@@ -196,6 +208,42 @@ class Mamba(nn.Module):
             A, Dp.float().view(3 * D), dt_bias.float().view(3 * D), True).view(batch, 3, D, seqlen)
         y = combine_directions(o3, nf).transpose(1, 2)    # (out + out_b.flip + out_s^-1) / 3, one write
         return F.linear(y, self.out_proj.weight, self.out_proj.bias)
+
+    def _prefill(self, hidden_states, conv_state, ssm_state):
+        """The reference's single-direction slow path (mamba_simple.py:311-353) over a whole prompt, filling the cache."""
+        batch, seqlen, _ = hidden_states.shape
+        xz = (self.in_proj.weight @ hidden_states.reshape(batch * seqlen, -1).t()
+              ).view(2 * self.d_inner, batch, seqlen).transpose(0, 1)
+        if self.in_proj.bias is not None:
+            xz = xz + self.in_proj.bias.to(xz.dtype)[:, None]
+        x, z = xz.chunk(2, dim=1)
+        with torch.no_grad():                             # the last d_conv pre-conv columns, zeros left of a short prompt
+            k = min(seqlen, self.d_conv)
+            conv_state.zero_()
+            conv_state[:, :, self.d_conv - k:].copy_(x[:, :, seqlen - k:])
+        x = causal_conv1d_fn(x, self.conv1d.weight.squeeze(1), self.conv1d.bias, self.activation)
+        x_dbl = self.x_proj(x.transpose(1, 2).reshape(batch * seqlen, self.d_inner))          # ((b l), R + 2N)
+        dt, B, C = torch.split(x_dbl, [self.dt_rank, self.d_state, self.d_state], dim=-1)
+        dt = (self.dt_proj.weight @ dt.t()).view(self.d_inner, batch, seqlen).transpose(0, 1)
+        B = B.reshape(batch, seqlen, self.d_state).transpose(1, 2).contiguous()
+        C = C.reshape(batch, seqlen, self.d_state).transpose(1, 2).contiguous()
+        y, last_state = selective_scan_fn(x, dt, -torch.exp(self.A_log.float()), B, C, self.D.float(), z=z,
+                                          delta_bias=self.dt_proj.bias.float(), delta_softplus=True, return_last_state=True)
+        with torch.no_grad():
+            ssm_state.copy_(last_state)
+        return self.out_proj(y.transpose(1, 2))
+
+    def _get_states_from_cache(self, inference_params, batch_size, initialize_states=False):
+        """The (conv_state, ssm_state) of this layer in inference_params.key_value_memory_dict, created on first use
+        (mamba_simple.py:415-441)."""
+        assert self.layer_idx is not None
+        if self.layer_idx not in inference_params.key_value_memory_dict:
+            inference_params.key_value_memory_dict[self.layer_idx] = self.allocate_inference_cache(batch_size, 0)
+        conv_state, ssm_state = inference_params.key_value_memory_dict[self.layer_idx]
+        if initialize_states:
+            conv_state.zero_()
+            ssm_state.zero_()
+        return conv_state, ssm_state
 
     def _forward_separate(self, xz, batch, seqlen, nf, hw):
         """The reference's call pattern: three `mamba_inner_fn_no_out_proj` calls (mamba_simple.py:220-262)."""

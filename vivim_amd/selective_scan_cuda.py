@@ -2,6 +2,9 @@
 mamba/csrc/selective_scan/selective_scan.cpp:494-497): `fwd` and `bwd` with the same positional
 signatures, argument checks and return lists, running the gfx950 kernels through the C ABI
 (include/vivim_hip.h).  Tensor allocation is the only thing PyTorch does here.
+
+`fwd_lean` is ours: the forward for a call no backward follows.  Same kernels and bits as `fwd`, but neither the
+checkpoint tensor `x` nor (when z is given) the ungated `out` is allocated or written.
 """
 import ctypes
 
@@ -114,6 +117,31 @@ def fwd(u, delta, A, B, C, D_, z_, delta_bias_, delta_softplus):
     with torch.cuda.device(u.device):
         _lib.call("vivim_selective_scan_fwd", P, torch.cuda.current_stream().cuda_stream)
     return [out, x] + ([out_z] if out_z is not None else [])
+
+
+def fwd_lean(u, delta, A, B, C, D_, z_, delta_bias_, delta_softplus, return_last_state=False):
+    """-> [out_z if z is given else out] (+ [last_state] when asked: contiguous fp32 (batch, dim, dstate), the values of
+    `fwd`'s x[:, :, -1, :]).  Bit-identical to `fwd` on the same tensors (vivim_selective_scan_fwd_lean)."""
+    dims = _common_checks(u, delta, A, B, C, D_, z_, delta_bias_)
+    batch, dim, seqlen, dstate = dims[:4]
+    result = _lib.empty_like(z_ if z_ is not None else delta)
+    P = _lib.SsmFwdParams()
+    _fill_fwd(P, u, delta, A, B, C, D_, z_, delta_bias_, delta_softplus, dims)
+    if z_ is not None:
+        P.out_z = result.data_ptr()
+        P.out_z_batch_stride, P.out_z_d_stride = result.stride(0), result.stride(1)
+    else:
+        P.out = result.data_ptr()
+        P.out_batch_stride, P.out_d_stride = result.stride(0), result.stride(1)
+    last_state = _lib.empty((batch, dim, dstate), torch.float32, u.device) if return_last_state else None
+    ws_bytes = _lib.lib().vivim_scan_fwd_workspace_bytes(P)
+    last_workspace_bytes["fwd"] = ws_bytes
+    if ws_bytes:
+        workspace = _lib.empty((ws_bytes,), torch.uint8, u.device)
+        P.workspace, P.workspace_bytes = workspace.data_ptr(), ws_bytes
+    with torch.cuda.device(u.device):
+        _lib.call_lean_fwd(P, _ptr(last_state), torch.cuda.current_stream().cuda_stream)
+    return [result] + ([last_state] if return_last_state else [])
 
 
 def bwd(u, delta, A, B, C, D_, z_, delta_bias_, dout, x_, out_, dz_, delta_softplus, recompute_out_z):

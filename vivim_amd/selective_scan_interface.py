@@ -9,6 +9,13 @@ mamba/mamba_ssm/ops/selective_scan_interface.py:
 The CUDA extension calls are replaced by vivim_amd.selective_scan_cuda / causal_conv1d_cuda (gfx950
 kernels behind the C ABI); the GEMMs inside the fused op stay on PyTorch-ROCm (hipBLASLt), as in the
 reference where they are plain torch matmuls (:181-182, :272-277).
+
+The lean route: when no backward can follow a call -- grad mode is off (torch.no_grad, torch.inference_mode) or no
+tensor argument requires grad -- the public wrappers run the Function's forward body directly, with
+selective_scan_cuda.fwd_lean in the place of fwd: the same kernels and the same bits, but the checkpoint tensor and the
+ungated `out` (which only the backward reads) are neither allocated nor written, and nothing is saved.  The choice is
+made in the wrapper, before `.apply`: inside `Function.forward` grad mode is always off.  VIVIM_NO_LEAN_FWD=1 keeps
+every call on the full route (A/B runs).
 """
 import os
 
@@ -24,10 +31,33 @@ def _unit_l(t):
     return t if t is None or t.stride(-1) == 1 else t.contiguous()
 
 
+class _NoCtx:
+    """Stands in for the autograd context on the lean route: attributes are set and forgotten, nothing is saved."""
+
+    def save_for_backward(self, *tensors):
+        pass
+
+
+def _no_backward(*args):
+    """True when no backward can follow a call with these arguments (and the lean route is not switched off)."""
+    if os.environ.get("VIVIM_NO_LEAN_FWD", "0") == "1":
+        return False
+    return not torch.is_grad_enabled() or not any(torch.is_tensor(t) and t.requires_grad for t in args)
+
+
+def _lean_call(fn, *args):
+    with torch.no_grad():
+        return fn._forward(_NoCtx(), True, *args)
+
+
 class SelectiveScanFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, u, delta, A, B, C, D=None, z=None, delta_bias=None, delta_softplus=False,
                 return_last_state=False):
+        return SelectiveScanFn._forward(ctx, False, u, delta, A, B, C, D, z, delta_bias, delta_softplus, return_last_state)
+
+    @staticmethod
+    def _forward(ctx, lean, u, delta, A, B, C, D, z, delta_bias, delta_softplus, return_last_state):
         u, delta, B, C, z = (_unit_l(t) for t in (u, delta, B, C, z))
         if D is not None:
             D = D.contiguous()
@@ -37,6 +67,9 @@ class SelectiveScanFn(torch.autograd.Function):
             B = B.unsqueeze(1)
         if ctx.squeeze_C:
             C = C.unsqueeze(1)
+        if lean:                                          # [out_z | out] (+ [last_state]): contiguous, the values of x[:, :, -1, :]
+            res = selective_scan_cuda.fwd_lean(u, delta, A, B, C, D, z, delta_bias, delta_softplus, return_last_state)
+            return tuple(res) if return_last_state else res[0]
         out, x, *rest = selective_scan_cuda.fwd(u, delta, A, B, C, D, z, delta_bias, delta_softplus)
         ctx.delta_softplus = delta_softplus
         ctx.has_z = z is not None
@@ -72,7 +105,10 @@ def selective_scan_fn(u, delta, A, B, C, D=None, z=None, delta_bias=None, delta_
                       return_last_state=False):
     """If return_last_state, returns (out, last_state) with last_state (batch, dim, dstate); the gradient
     of last_state is not propagated (as in the reference, :79-82)."""
-    return SelectiveScanFn.apply(u, delta, A, B, C, D, z, delta_bias, delta_softplus, return_last_state)
+    args = (u, delta, A, B, C, D, z, delta_bias, delta_softplus, return_last_state)
+    if _no_backward(*args):
+        return _lean_call(SelectiveScanFn, *args)
+    return SelectiveScanFn.apply(*args)
 
 
 class MambaInnerFnNoOutProj(torch.autograd.Function):
@@ -85,6 +121,13 @@ class MambaInnerFnNoOutProj(torch.autograd.Function):
     def forward(ctx, xz, conv1d_weight, conv1d_bias, x_proj_weight, delta_proj_weight,
                 A, B=None, C=None, D=None, delta_bias=None, B_proj_bias=None, C_proj_bias=None,
                 delta_softplus=True, checkpoint_lvl=1):
+        return MambaInnerFnNoOutProj._forward(ctx, False, xz, conv1d_weight, conv1d_bias, x_proj_weight, delta_proj_weight,
+                                              A, B, C, D, delta_bias, B_proj_bias, C_proj_bias, delta_softplus, checkpoint_lvl)
+
+    @staticmethod
+    def _forward(ctx, lean, xz, conv1d_weight, conv1d_bias, x_proj_weight, delta_proj_weight,
+                 A, B=None, C=None, D=None, delta_bias=None, B_proj_bias=None, C_proj_bias=None,
+                 delta_softplus=True, checkpoint_lvl=1):
         assert checkpoint_lvl in (0, 1)
         if A.is_complex():
             raise NotImplementedError("complex A is outside Vivim's path (A is real fp32, mamba_simple.py:212)")
@@ -124,6 +167,8 @@ class MambaInnerFnNoOutProj(torch.autograd.Function):
             C = _unit_l(C)
         if D is not None:
             D = D.contiguous()
+        if lean:
+            return selective_scan_cuda.fwd_lean(conv1d_out, delta, A, B, C, D, z, delta_bias, delta_softplus)[0]
         out, scan_intermediates, out_z = selective_scan_cuda.fwd(
             conv1d_out, delta, A, B, C, D, z, delta_bias, delta_softplus)
         ctx.delta_softplus = delta_softplus
@@ -191,8 +236,11 @@ def mamba_inner_fn_no_out_proj(xz, conv1d_weight, conv1d_bias, x_proj_weight, de
                                A, B=None, C=None, D=None, delta_bias=None, B_proj_bias=None,
                                C_proj_bias=None, delta_softplus=True):
     """xz: (batch, 2*d_inner, seqlen) -> (batch, d_inner, seqlen)."""
-    return MambaInnerFnNoOutProj.apply(xz, conv1d_weight, conv1d_bias, x_proj_weight, delta_proj_weight,
-                                       A, B, C, D, delta_bias, B_proj_bias, C_proj_bias, delta_softplus)
+    args = (xz, conv1d_weight, conv1d_bias, x_proj_weight, delta_proj_weight,
+            A, B, C, D, delta_bias, B_proj_bias, C_proj_bias, delta_softplus)
+    if _no_backward(*args):
+        return _lean_call(MambaInnerFnNoOutProj, *args)
+    return MambaInnerFnNoOutProj.apply(*args)
 
 
 def _channel_major(t):
@@ -234,6 +282,12 @@ class MambaInnerGroupedFnNoOutProj(torch.autograd.Function):
     @custom_fwd(device_type="cuda")
     def forward(ctx, xz, conv1d_weight, conv1d_bias, x_proj_weight, delta_proj_weight, A, D, delta_bias,
                 delta_softplus=True):
+        return MambaInnerGroupedFnNoOutProj._forward(ctx, False, xz, conv1d_weight, conv1d_bias, x_proj_weight,
+                                                     delta_proj_weight, A, D, delta_bias, delta_softplus)
+
+    @staticmethod
+    def _forward(ctx, lean, xz, conv1d_weight, conv1d_bias, x_proj_weight, delta_proj_weight, A, D, delta_bias,
+                 delta_softplus=True):
         batch, two, G, Dm, L = xz.shape
         assert two == 2
         R = delta_proj_weight.shape[2]
@@ -253,6 +307,8 @@ class MambaInnerGroupedFnNoOutProj(torch.autograd.Function):
         delta = torch.bmm(delta_proj_weight, x_dbl[:, :R]).view(G * Dm, batch, L).permute(1, 0, 2)
         x_dbl4 = x_dbl.view(G, -1, batch, L)
         B, C = x_dbl4[:, R:R + N].permute(2, 0, 1, 3), x_dbl4[:, R + N:].permute(2, 0, 1, 3)   # (batch, G, N, l) views
+        if lean:
+            return selective_scan_cuda.fwd_lean(conv1d_out, delta, A, B, C, D.contiguous(), z, delta_bias, delta_softplus)[0]
         out, scan_intermediates, out_z = selective_scan_cuda.fwd(
             conv1d_out, delta, A, B, C, D.contiguous(), z, delta_bias, delta_softplus)
         ctx.delta_softplus = delta_softplus
@@ -309,8 +365,10 @@ class MambaInnerGroupedFnNoOutProj(torch.autograd.Function):
 
 def mamba_inner_grouped_fn_no_out_proj(xz, conv1d_weight, conv1d_bias, x_proj_weight, delta_proj_weight, A, D,
                                        delta_bias, delta_softplus=True):
-    return MambaInnerGroupedFnNoOutProj.apply(xz, conv1d_weight, conv1d_bias, x_proj_weight, delta_proj_weight,
-                                              A, D, delta_bias, delta_softplus)
+    args = (xz, conv1d_weight, conv1d_bias, x_proj_weight, delta_proj_weight, A, D, delta_bias, delta_softplus)
+    if _no_backward(*args):
+        return _lean_call(MambaInnerGroupedFnNoOutProj, *args)
+    return MambaInnerGroupedFnNoOutProj.apply(*args)
 
 
 def mamba_inner_fn(xz, conv1d_weight, conv1d_bias, x_proj_weight, delta_proj_weight,
@@ -372,6 +430,14 @@ class BiMambaInnerFn(torch.autograd.Function):
     def forward(ctx, xz, conv1d_weight, conv1d_bias, x_proj_weight, delta_proj_weight, out_proj_weight, out_proj_bias,
                 A, A_b, B=None, C=None, D=None, delta_bias=None, B_proj_bias=None, C_proj_bias=None,
                 delta_softplus=True, checkpoint_lvl=1):
+        return BiMambaInnerFn._forward(ctx, False, xz, conv1d_weight, conv1d_bias, x_proj_weight, delta_proj_weight,
+                                       out_proj_weight, out_proj_bias, A, A_b, B, C, D, delta_bias, B_proj_bias, C_proj_bias,
+                                       delta_softplus, checkpoint_lvl)
+
+    @staticmethod
+    def _forward(ctx, lean, xz, conv1d_weight, conv1d_bias, x_proj_weight, delta_proj_weight, out_proj_weight, out_proj_bias,
+                 A, A_b, B=None, C=None, D=None, delta_bias=None, B_proj_bias=None, C_proj_bias=None,
+                 delta_softplus=True, checkpoint_lvl=1):
         assert checkpoint_lvl in (0, 1)
         if A.is_complex() or A_b.is_complex():
             raise NotImplementedError("complex A is outside this build (the reference asserts a real A_b, :503)")
@@ -395,6 +461,9 @@ class BiMambaInnerFn(torch.autograd.Function):
         delta, Bv, Cv = BiMambaInnerFn._project(x_dbl, delta_proj_weight, B, C, B_proj_bias, C_proj_bias, batch, L, N)
         u2, delta2, z2, B2, C2, A2, D2, bias2 = BiMambaInnerFn._stack(
             conv1d_out, delta, z, Bv, Cv, A, A_b, D, delta_bias, ctx.is_variable_B, ctx.is_variable_C)
+        if lean:
+            out_z2 = selective_scan_cuda.fwd_lean(u2, delta2, A2, B2, C2, D2, z2, bias2, delta_softplus)[0]
+            return F.linear(BiMambaInnerFn._fold(out_z2).transpose(1, 2), out_proj_weight, out_proj_bias)
         out2, scan_intermediates, out_z2 = selective_scan_cuda.fwd(u2, delta2, A2, B2, C2, D2, z2, bias2, delta_softplus)
         out_z = BiMambaInnerFn._fold(out_z2)
         ctx.delta_softplus = delta_softplus
@@ -474,5 +543,8 @@ def bimamba_inner_fn(xz, conv1d_weight, conv1d_bias, x_proj_weight, delta_proj_w
                      A, A_b, B=None, C=None, D=None, delta_bias=None, B_proj_bias=None, C_proj_bias=None,
                      delta_softplus=True):
     """xz: (batch, 2*d_inner, seqlen) -> (batch, seqlen, d_model); selective_scan_interface.py:616-625."""
-    return BiMambaInnerFn.apply(xz, conv1d_weight, conv1d_bias, x_proj_weight, delta_proj_weight, out_proj_weight,
-                                out_proj_bias, A, A_b, B, C, D, delta_bias, B_proj_bias, C_proj_bias, delta_softplus)
+    args = (xz, conv1d_weight, conv1d_bias, x_proj_weight, delta_proj_weight, out_proj_weight,
+            out_proj_bias, A, A_b, B, C, D, delta_bias, B_proj_bias, C_proj_bias, delta_softplus)
+    if _no_backward(*args):
+        return _lean_call(BiMambaInnerFn, *args)
+    return BiMambaInnerFn.apply(*args)
