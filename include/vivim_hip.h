@@ -320,12 +320,53 @@ typedef struct {
     void *out;
 } vivim_wgrad_nt_params;
 
+/* ---- recall-focused segmentation loss: 0.4 * class-balanced focal + 0.6 * Tversky over softmax(logits) (opt-in) ---------------
+ * The train step's loss (vivim_amd/train_step.py: recall_focused_loss) as three launches: partial sums, finalise, gradient.
+ * Per pixel i of image n, classes c < C, label t; everything in f32, logits widened on load:
+ *   m = max_c x_c    e_c = exp(x_c - m)    S = sum_c e_c    p_c = e_c / S    q_c = (sum_{k != c} e_k) / S   (never 1 - p_c)
+ *   y_c = (t == c)   -- labels are only COMPARED with c, never used as an index: a label outside [0, C) gives y_c = 0 for every c
+ *   phi = sum_c alpha_c * ( y_c ? q_c^2 * -ln(p_c + eps) : p_c^2 * -ln(q_c + eps) )                       (gamma = 2)
+ *   TP[n,c] = sum_i y_c p_c    FP[n,c] = sum_i (1 - y_c) p_c    FN[n,c] = sum_i y_c q_c
+ *   den = TP + tversky_alpha * FP + tversky_beta * FN + smooth
+ *   loss = focal_weight * sum_{n,i} phi / (N * pixels) + tversky_weight * (1 - sum_{n,c} ((TP + smooth) / den) / (N * C))
+ * forward : writes loss (one f32) and, unless coef is NULL, coef[n][c] = { G1, G0 } = d((TP + smooth) / den) / d p_c at a pixel of
+ *           class c / of another class:  G1 = (den - (TP + smooth) * (1 - tversky_beta)) / den^2,  G0 = -(TP + smooth) * tversky_alpha / den^2
+ * backward: g_c = focal_weight / (N * pixels) * alpha_c * ( y_c ?  2 q_c ln(p_c + eps) - q_c^2 / (p_c + eps)
+ *                                                               : -2 p_c ln(q_c + eps) + p_c^2 / (q_c + eps) )
+ *                 - tversky_weight / (N * C) * ( y_c ? G1 : G0 )
+ *           dlogits_c = *grad_out * p_c * ( q_c * g_c - sum_{k != c} p_k g_k )      the softmax is recomputed, nothing is kept per pixel;
+ *           *grad_out is read on the device (no host synchronisation) and multiplied in f32 before the one rounding to itype.
+ * Determinism: no float atomics.  Every workgroup stores its partial sums into slot (image, block) of `workspace` and one
+ * workgroup adds the slots in slot order, so loss, coef and dlogits are pure functions of the inputs and the shape.
+ * logits, dlogits: (batch, classes, pixels) with unit pixel stride, itype; 16-byte vectors where base and strides allow, element
+ * accesses otherwise (any alignment of the element type is accepted).  target: (batch, pixels), unit pixel stride.
+ * classes outside 2..8 and gamma != 2 return VIVIM_ERR_UNSUPPORTED. */
+typedef struct {
+    int32_t batch, classes, pixels;
+    int32_t itype;                                   /* logits / dlogits: vivim_dtype_t */
+    int32_t ttype;                                   /* target: 0 = int64, 1 = uint8 */
+    float gamma;                                     /* 2 */
+    float focal_weight, tversky_weight;              /* 0.4, 0.6 in the train step */
+    float tversky_alpha, tversky_beta, smooth, eps;  /* 0.3, 0.7, 1e-6, 1e-6 */
+    int64_t logits_batch_stride, logits_c_stride;    /* elements */
+    int64_t dlogits_batch_stride, dlogits_c_stride;
+    int64_t target_batch_stride;
+    const void *logits, *target;
+    const void *alpha;                               /* (classes) f32 class weights of the focal term */
+    void *loss;                                      /* one f32: forward output */
+    void *coef;                                      /* (batch, classes, 2) f32: forward output (NULL: not wanted), backward input */
+    void *workspace;                                 /* forward scratch, vivim_seg_loss_workspace_bytes() of it, 4-byte aligned */
+    int64_t workspace_bytes;
+    const void *grad_out;                            /* one f32 on the device: backward input */
+    void *dlogits;                                   /* backward output */
+} vivim_seg_loss_params;
+
 int vivim_abi_version(void);
 const char *vivim_last_error(void);
 
 /* sizeof() of a params struct as this library was compiled, so a foreign-language binding can assert
  * its own layout: which = 0 ssm_fwd, 1 ssm_bwd, 2 conv_fwd, 3 conv_bwd, 4 dwconv, 5 dwconv_wgrad, 6 dir, 7 conv_update,
- * 8 state_update, 9 layernorm, 10 wgrad_nt, 11 add_layernorm; 0 for anything else. */
+ * 8 state_update, 9 layernorm, 10 wgrad_nt, 11 add_layernorm, 12 seg_loss; 0 for anything else. */
 size_t vivim_sizeof(int which);
 
 /* Tokens per checkpoint row of `x`: n_chunks = ceil(seqlen / vivim_scan_ckpt_len(f)).  Depends on the sizes and flags in
@@ -375,6 +416,9 @@ int vivim_wgrad_nt(const vivim_wgrad_nt_params *p, void *stream);
 int vivim_add_layernorm_cm_fwd(const vivim_add_layernorm_params *p, void *stream);
 int vivim_add_layernorm_cm_bwd(const vivim_add_layernorm_params *p, void *stream);
 size_t vivim_add_layernorm_bwd_workspace_bytes(const vivim_add_layernorm_params *p);   /* from batch, seqlen, channels, itype */
+int vivim_seg_loss_fwd(const vivim_seg_loss_params *p, void *stream);
+int vivim_seg_loss_bwd(const vivim_seg_loss_params *p, void *stream);
+size_t vivim_seg_loss_workspace_bytes(const vivim_seg_loss_params *p);   /* from batch, classes, pixels, itype; 0 on bad sizes */
 
 /* Deterministic backward (for torch.use_deterministic_algorithms).  Same parameters, checks and results as
  * vivim_selective_scan_bwd, and the same kernel family, but every gradient that the default call adds up across

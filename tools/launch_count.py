@@ -1,6 +1,8 @@
 """Kernel launches of one tri-directional Mamba block (forward + backward, bf16 autocast, stage-0 shape of the bench) and of
 one whole train step, by kernel name -- the step is host-bound, so launches are what it pays for.
-    python tools/launch_count.py [--dim 64] [--batch 3] [--frames 5] [--hw 4096] [--step]"""
+    python tools/launch_count.py [--dim 64] [--batch 3] [--frames 5] [--hw 4096] [--step] [--fused-loss]
+--fused-loss (with --step) counts the step with train_step(fused_loss=True) as well, and the loss alone (forward + backward on
+the step's logits shape) both ways."""
 import argparse
 import collections
 import os
@@ -41,6 +43,7 @@ def main():
     ap.add_argument("--frames", type=int, default=5)
     ap.add_argument("--hw", type=int, default=4096)
     ap.add_argument("--step", action="store_true")
+    ap.add_argument("--fused-loss", action="store_true")
     a = ap.parse_args()
     dev = torch.device("cuda:0")
     from vivim_amd.mamba_simple import Mamba
@@ -62,6 +65,19 @@ def main():
         def step():
             ts.train_step(model, opt, clip, onehot, 3, torch.bfloat16)
         show("train step", *launches(step), top=60)
+        if a.fused_loss:
+            from vivim_amd.seg_loss import recall_focused_loss_fused
+
+            def step_fused():
+                ts.train_step(model, opt, clip, onehot, 3, torch.bfloat16, fused_loss=True)
+            show("train step, fused_loss=True", *launches(step_fused), top=60)
+            logits = torch.randn(a.batch * a.frames, 3, 256, 256, device=dev, dtype=torch.bfloat16, requires_grad=True)
+            target = onehot.argmax(dim=2).view(a.batch * a.frames, 256, 256)
+            for title, fn in (("eager", ts.recall_focused_loss), ("fused", recall_focused_loss_fused)):
+                def loss_only(fn=fn):
+                    logits.grad = None
+                    fn(logits, target, 3).backward()
+                show(f"loss alone ({title}), forward + backward, {tuple(logits.shape)} bf16", *launches(loss_only), top=12)
 
 
 if __name__ == "__main__":

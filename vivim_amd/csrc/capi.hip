@@ -38,6 +38,8 @@ bool wgrad_nt_dispatch(const vivim_wgrad_nt_params&, hipStream_t);              
 bool add_layernorm_dispatch(const vivim_add_layernorm_params&, bool bwd, hipStream_t);   // add_layernorm.hip
 size_t add_layernorm_bwd_workspace_bytes(const vivim_add_layernorm_params&);
 size_t scan_fwd_workspace_bytes(const vivim_ssm_fwd_params&);
+bool seg_loss_dispatch(const vivim_seg_loss_params&, bool bwd, hipStream_t);       // seg_loss.hip
+size_t seg_loss_workspace_bytes(const vivim_seg_loss_params&);
 }  // namespace vivim
 
 static thread_local char g_err[512] = "";
@@ -147,6 +149,7 @@ size_t vivim_sizeof(int which) {
         case 9: return sizeof(vivim_layernorm_params);
         case 10: return sizeof(vivim_wgrad_nt_params);
         case 11: return sizeof(vivim_add_layernorm_params);
+        case 12: return sizeof(vivim_seg_loss_params);
     }
     return 0;
 }
@@ -500,6 +503,52 @@ int vivim_add_layernorm_cm_bwd(const vivim_add_layernorm_params* p, void* stream
         return fail(VIVIM_ERR_UNSUPPORTED, "add_layernorm_cm_bwd not implemented for x type %d / branch type %d / output type %d", p->itype,
                     p->btype, p->otype);
     return after_launch("add_layernorm_cm_bwd");
+}
+
+// what the forward and the backward of the segmentation loss share
+static int check_seg_loss(const vivim_seg_loss_params* p) {
+    VCHECK(p != nullptr);
+    VCHECK(dtype_ok(p->itype) && (p->ttype == 0 || p->ttype == 1));
+    VCHECK(p->batch > 0 && p->pixels > 0);
+    if (p->classes < 2 || p->classes > 8)
+        return fail(VIVIM_ERR_UNSUPPORTED, "seg_loss: %d classes: the kernels are built for 2 to 8 classes", p->classes);
+    if (p->gamma != 2.0f)
+        return fail(VIVIM_ERR_UNSUPPORTED, "seg_loss: gamma = %g: the kernels are built for gamma = 2 only", (double)p->gamma);
+    VCHECK((int64_t)p->batch * 64 <= INT32_MAX);                  // one workgroup index per (image, block)
+    const uintptr_t ib = p->itype == VIVIM_F32 ? 4 : 2, tbytes = p->ttype == 0 ? 8 : 1;
+    VCHECK(p->logits && reinterpret_cast<uintptr_t>(p->logits) % ib == 0);
+    VCHECK(p->target && reinterpret_cast<uintptr_t>(p->target) % tbytes == 0);
+    VCHECK(p->alpha && reinterpret_cast<uintptr_t>(p->alpha) % 4 == 0);
+    return VIVIM_OK;
+}
+
+size_t vivim_seg_loss_workspace_bytes(const vivim_seg_loss_params* p) {
+    return p && p->batch > 0 && p->pixels > 0 && p->classes > 0 && dtype_ok(p->itype) ? vivim::seg_loss_workspace_bytes(*p) : 0;
+}
+
+int vivim_seg_loss_fwd(const vivim_seg_loss_params* p, void* stream) {
+    if (int rc = check_seg_loss(p)) return rc;
+    VCHECK(p->loss && reinterpret_cast<uintptr_t>(p->loss) % 4 == 0);
+    VCHECK(reinterpret_cast<uintptr_t>(p->coef) % 4 == 0);          // NULL: not wanted
+    const size_t need = vivim::seg_loss_workspace_bytes(*p);
+    if (p->workspace == nullptr || reinterpret_cast<uintptr_t>(p->workspace) % 4 != 0 || p->workspace_bytes < 0 ||
+        (size_t)p->workspace_bytes < need)
+        return fail(VIVIM_ERR_INVALID, "seg_loss_fwd: workspace of %lld bytes at %p: need a 4-byte aligned one of "
+                    "vivim_seg_loss_workspace_bytes() = %zu", (long long)p->workspace_bytes, p->workspace, need);
+    if (!vivim::seg_loss_dispatch(*p, false, static_cast<hipStream_t>(stream)))
+        return fail(VIVIM_ERR_UNSUPPORTED, "seg_loss_fwd not implemented for input type %d / %d classes", p->itype, p->classes);
+    return after_launch("seg_loss_fwd");
+}
+
+int vivim_seg_loss_bwd(const vivim_seg_loss_params* p, void* stream) {
+    if (int rc = check_seg_loss(p)) return rc;
+    const uintptr_t ib = p->itype == VIVIM_F32 ? 4 : 2;
+    VCHECK(p->coef && reinterpret_cast<uintptr_t>(p->coef) % 4 == 0);
+    VCHECK(p->grad_out && reinterpret_cast<uintptr_t>(p->grad_out) % 4 == 0);
+    VCHECK(p->dlogits && reinterpret_cast<uintptr_t>(p->dlogits) % ib == 0);
+    if (!vivim::seg_loss_dispatch(*p, true, static_cast<hipStream_t>(stream)))
+        return fail(VIVIM_ERR_UNSUPPORTED, "seg_loss_bwd not implemented for input type %d / %d classes", p->itype, p->classes);
+    return after_launch("seg_loss_bwd");
 }
 
 }  // extern "C"

@@ -150,17 +150,23 @@ def synthetic_batch(batch, clip_length, image_size, num_classes, device, seed):
 _SCALERS = {}
 
 
-def train_step(model, optimizer, clip, onehot, num_classes, amp_dtype=torch.bfloat16, clip_grad_norm=None):
+def train_step(model, optimizer, clip, onehot, num_classes, amp_dtype=torch.bfloat16, clip_grad_norm=None, fused_loss=False):
     """One fwd + loss + bwd + optimizer step; returns the detached loss.  fp16 autocast runs under a GradScaler (the
     reference trains with Trainer(precision=16), multiclass_training_folds.py:800-811; bf16 / fp32 need none);
-    `clip_grad_norm` (the reference's gradient_clip_val) clips the global gradient norm before the update."""
+    `clip_grad_norm` (the reference's gradient_clip_val) clips the global gradient norm before the update.
+    `fused_loss=True` takes the loss and its gradient from the fused kernels (seg_loss.recall_focused_loss_fused: three
+    launches, cancellation-free) instead of the eager chain of recall_focused_loss; opt-in, the default step is unchanged."""
     if not model.training:                 # Module.train() walks all ~4000 submodules: 3 ms of host time when repeated per step
         model.train()
     with torch.autocast("cuda", dtype=amp_dtype, enabled=amp_dtype != torch.float32):
         logits = model(clip)                                   # (B*nf, C, H, W)
     B, T = onehot.shape[:2]
     target = onehot.argmax(dim=2).view(B * T, *onehot.shape[-2:])
-    loss = recall_focused_loss(logits, target, num_classes)
+    if fused_loss:
+        from .seg_loss import recall_focused_loss_fused
+        loss = recall_focused_loss_fused(logits, target, num_classes)
+    else:
+        loss = recall_focused_loss(logits, target, num_classes)
     optimizer.zero_grad(set_to_none=True)
     if amp_dtype == torch.float16:
         sc = _SCALERS.setdefault(id(optimizer), {"scale": 65536.0, "good": 0})      # dynamic loss scale, GradScaler's policy
