@@ -361,12 +361,43 @@ typedef struct {
     void *dlogits;                                   /* backward output */
 } vivim_seg_loss_params;
 
+/* ---- Validation metrics of a batch of logits (vivim_seg_metrics; csrc/seg_metrics.hip): argmax + confusion counts ----------
+ * Per pixel i of image n: pred = the FIRST index of the maximum of the C logits, compared in their own values (widening to f32 is
+ * exact); a NaN counts as the maximum and the first NaN wins (numpy.argmax's rule; no softmax).  With the label t:
+ *   tp[n,c] = #(pred == c and t == c)    fp[n,c] = #(pred == c and t != c)    fn[n,c] = #(pred != c and t == c)
+ * Labels are only COMPARED with c: a label outside [0, C) is a pixel of no class and adds to fp of the class predicted there only.
+ * Outputs: counts (batch, classes, 3) int32 = {tp, fp, fn}; pred (optional) the prediction map, one uint8 per pixel; state
+ * (optional) (classes, 7) f64, owned and zeroed by the caller, ADDED into: for n = 0 .. batch-1 in that order and every class
+ * present in image n's label map (tp + fn > 0), with HW = pixels and tn = HW - tp - fp - fn,
+ *   state[c][0] += dice        = 2 tp / (2 tp + fp + fn)              state[c][1] += jaccard = tp / (tp + fp + fn)
+ *   state[c][2] += precision   = tp + fp == 0 ? 0 : tp / (tp + fp)    state[c][3] += recall  = tp / (tp + fn)
+ *   state[c][4] += f_measure   = 2 precision recall / (precision + recall + 1e-5)
+ *   state[c][5] += specificity = tp + fn == HW ? 0 : tn / (tn + fp)   state[c][6] += 1
+ * Determinism: integer counts, no atomics; every workgroup stores its counts into slot (image, block) of `workspace`, one
+ * workgroup adds the slots in slot order, and the order over n is fixed, so counts, pred and state are pure functions of the inputs.
+ * logits: (batch, classes, pixels) with unit pixel stride, itype; 16-byte vectors where base and strides allow, element accesses
+ * otherwise.  target: (batch, pixels), pred: (batch, pixels), unit pixel stride.  classes outside 2..8 return VIVIM_ERR_UNSUPPORTED. */
+typedef struct {
+    int32_t batch, classes, pixels;
+    int32_t itype;                                   /* logits: vivim_dtype_t */
+    int32_t ttype;                                   /* target: 0 = int64, 1 = uint8 */
+    int32_t _pad0;
+    int64_t logits_batch_stride, logits_c_stride;    /* elements */
+    int64_t target_batch_stride, pred_batch_stride;
+    const void *logits, *target;
+    void *counts;                                    /* (batch, classes, 3) int32, 4-byte aligned */
+    void *pred;                                      /* (batch, pixels) uint8, any alignment; NULL: not wanted */
+    void *state;                                     /* (classes, 7) f64, 8-byte aligned, added into; NULL: not wanted */
+    void *workspace;                                 /* vivim_seg_metrics_workspace_bytes() of it, 4-byte aligned */
+    int64_t workspace_bytes;
+} vivim_seg_metrics_params;
+
 int vivim_abi_version(void);
 const char *vivim_last_error(void);
 
 /* sizeof() of a params struct as this library was compiled, so a foreign-language binding can assert
  * its own layout: which = 0 ssm_fwd, 1 ssm_bwd, 2 conv_fwd, 3 conv_bwd, 4 dwconv, 5 dwconv_wgrad, 6 dir, 7 conv_update,
- * 8 state_update, 9 layernorm, 10 wgrad_nt, 11 add_layernorm, 12 seg_loss; 0 for anything else. */
+ * 8 state_update, 9 layernorm, 10 wgrad_nt, 11 add_layernorm, 12 seg_loss, 13 seg_metrics; 0 for anything else. */
 size_t vivim_sizeof(int which);
 
 /* Tokens per checkpoint row of `x`: n_chunks = ceil(seqlen / vivim_scan_ckpt_len(f)).  Depends on the sizes and flags in
@@ -419,6 +450,8 @@ size_t vivim_add_layernorm_bwd_workspace_bytes(const vivim_add_layernorm_params 
 int vivim_seg_loss_fwd(const vivim_seg_loss_params *p, void *stream);
 int vivim_seg_loss_bwd(const vivim_seg_loss_params *p, void *stream);
 size_t vivim_seg_loss_workspace_bytes(const vivim_seg_loss_params *p);   /* from batch, classes, pixels, itype; 0 on bad sizes */
+int vivim_seg_metrics(const vivim_seg_metrics_params *p, void *stream);
+size_t vivim_seg_metrics_workspace_bytes(const vivim_seg_metrics_params *p);   /* from batch, classes, pixels, itype; 0 on bad sizes */
 
 /* Deterministic backward (for torch.use_deterministic_algorithms).  Same parameters, checks and results as
  * vivim_selective_scan_bwd, and the same kernel family, but every gradient that the default call adds up across

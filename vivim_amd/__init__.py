@@ -7,3 +7,11 @@ vivim_amd/csrc/libvivim_hip.so raises ImportError on first use.
 """
 __version__ = "0.1.0"
 from .generation import InferenceParams  # noqa: E402,F401  (a plain dataclass: importing it loads neither torch nor the library)
+
+
+def __getattr__(name):
+    # the validation metrics (seg_metrics.py) need torch: exported here, imported on first use
+    if name in ("SegMetricsTracker", "seg_confusion_counts"):
+        from . import seg_metrics
+        return getattr(seg_metrics, name)
+    raise AttributeError(f"module {__name__!r} has no attribute {name!r}")

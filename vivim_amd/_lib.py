@@ -140,6 +140,13 @@ class SegLossParams(ctypes.Structure):
                 + [("workspace_bytes", i64), ("grad_out", vp), ("dlogits", vp)])
 
 
+class SegMetricsParams(ctypes.Structure):
+    _fields_ = ([(n, i32) for n in ("batch", "classes", "pixels", "itype", "ttype", "_pad0")]
+                + [(n, i64) for n in ("logits_batch_stride", "logits_c_stride", "target_batch_stride", "pred_batch_stride")]
+                + [(n, vp) for n in ("logits", "target", "counts", "pred", "state", "workspace")]
+                + [("workspace_bytes", i64)])
+
+
 EXPORTS = ("vivim_abi_version", "vivim_last_error", "vivim_scan_chunk_len", "vivim_scan_ckpt_len", "vivim_sizeof",
            "vivim_scan_bwd_workspace_bytes", "vivim_scan_fwd_workspace_bytes", "vivim_set_tuning",
            "vivim_selective_scan_fwd", "vivim_selective_scan_bwd", "vivim_selective_scan_fwd_lean",
@@ -150,7 +157,8 @@ EXPORTS = ("vivim_abi_version", "vivim_last_error", "vivim_scan_chunk_len", "viv
            "vivim_causal_conv1d_bwd_det_workspace_bytes", "vivim_causal_conv1d_bwd_det",
            "vivim_dwconv_wgrad_det_workspace_bytes", "vivim_dwconv_wgrad_det",
            "vivim_add_layernorm_cm_fwd", "vivim_add_layernorm_cm_bwd", "vivim_add_layernorm_bwd_workspace_bytes",
-           "vivim_seg_loss_fwd", "vivim_seg_loss_bwd", "vivim_seg_loss_workspace_bytes")
+           "vivim_seg_loss_fwd", "vivim_seg_loss_bwd", "vivim_seg_loss_workspace_bytes",
+           "vivim_seg_metrics", "vivim_seg_metrics_workspace_bytes")
 
 _lib = None
 
@@ -196,7 +204,8 @@ def lib():
                          ("vivim_wgrad_nt", WgradNtParams),
                          ("vivim_add_layernorm_cm_fwd", AddLayerNormParams),
                          ("vivim_add_layernorm_cm_bwd", AddLayerNormParams),
-                         ("vivim_seg_loss_fwd", SegLossParams), ("vivim_seg_loss_bwd", SegLossParams)):
+                         ("vivim_seg_loss_fwd", SegLossParams), ("vivim_seg_loss_bwd", SegLossParams),
+                         ("vivim_seg_metrics", SegMetricsParams)):
             fn = getattr(L, name)
             fn.argtypes = [ctypes.POINTER(st), vp]
             fn.restype = ctypes.c_int
@@ -219,11 +228,13 @@ def lib():
         L.vivim_add_layernorm_bwd_workspace_bytes.restype = ctypes.c_size_t
         L.vivim_seg_loss_workspace_bytes.argtypes = [ctypes.POINTER(SegLossParams)]
         L.vivim_seg_loss_workspace_bytes.restype = ctypes.c_size_t
+        L.vivim_seg_metrics_workspace_bytes.argtypes = [ctypes.POINTER(SegMetricsParams)]
+        L.vivim_seg_metrics_workspace_bytes.restype = ctypes.c_size_t
         if L.vivim_abi_version() != 8:
             raise ImportError("libvivim_hip.so ABI version mismatch")
         for which, st in enumerate((SsmFwdParams, SsmBwdParams, ConvFwdParams, ConvBwdParams, DwConvParams,
                                     DwConvWgradParams, DirParams, ConvUpdateParams, StateUpdateParams, LayerNormParams,
-                                    WgradNtParams, AddLayerNormParams, SegLossParams)):
+                                    WgradNtParams, AddLayerNormParams, SegLossParams, SegMetricsParams)):
             if L.vivim_sizeof(which) != ctypes.sizeof(st):
                 raise ImportError(f"struct layout mismatch for {st.__name__}: "
                                   f"C {L.vivim_sizeof(which)} vs ctypes {ctypes.sizeof(st)}")
@@ -245,6 +256,9 @@ def algorithmic_bytes(name, P):
             return n * (2 * _ISIZE[P.itype] + _ISIZE[P.btype] + _ISIZE[P.otype]) + 8 * P.batch * P.seqlen + 8 * P.channels
         res = (_ISIZE[P.itype] if P.dres else 0) + (_ISIZE[P.otype] if P.dy else 0) + (_ISIZE[P.btype] if P.dbranch else 0)
         return n * (2 * _ISIZE[P.itype] + res) + 8 * P.batch * P.seqlen + 12 * P.channels   # x_new, dx + what is present
+    if name.startswith("vivim_seg_metrics"):                            # logits, labels, the prediction map if wanted, the counts
+        n = P.batch * P.pixels
+        return n * (P.classes * _ISIZE[P.itype] + (8 if P.ttype == 0 else 1) + (1 if P.pred else 0)) + 12 * P.batch * P.classes
     if name.startswith("vivim_seg_loss"):                               # logits (+ dlogits), labels, the per-image factors
         n = P.batch * P.pixels
         return (n * ((2 if name.endswith("bwd") else 1) * P.classes * _ISIZE[P.itype] + (8 if P.ttype == 0 else 1))

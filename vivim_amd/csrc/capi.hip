@@ -40,6 +40,8 @@ size_t add_layernorm_bwd_workspace_bytes(const vivim_add_layernorm_params&);
 size_t scan_fwd_workspace_bytes(const vivim_ssm_fwd_params&);
 bool seg_loss_dispatch(const vivim_seg_loss_params&, bool bwd, hipStream_t);       // seg_loss.hip
 size_t seg_loss_workspace_bytes(const vivim_seg_loss_params&);
+bool seg_metrics_dispatch(const vivim_seg_metrics_params&, hipStream_t);          // seg_metrics.hip
+size_t seg_metrics_workspace_bytes(const vivim_seg_metrics_params&);
 }  // namespace vivim
 
 static thread_local char g_err[512] = "";
@@ -150,6 +152,7 @@ size_t vivim_sizeof(int which) {
         case 10: return sizeof(vivim_wgrad_nt_params);
         case 11: return sizeof(vivim_add_layernorm_params);
         case 12: return sizeof(vivim_seg_loss_params);
+        case 13: return sizeof(vivim_seg_metrics_params);
     }
     return 0;
 }
@@ -549,6 +552,32 @@ int vivim_seg_loss_bwd(const vivim_seg_loss_params* p, void* stream) {
     if (!vivim::seg_loss_dispatch(*p, true, static_cast<hipStream_t>(stream)))
         return fail(VIVIM_ERR_UNSUPPORTED, "seg_loss_bwd not implemented for input type %d / %d classes", p->itype, p->classes);
     return after_launch("seg_loss_bwd");
+}
+
+size_t vivim_seg_metrics_workspace_bytes(const vivim_seg_metrics_params* p) {
+    return p && p->batch > 0 && p->pixels > 0 && p->classes > 0 && dtype_ok(p->itype) ? vivim::seg_metrics_workspace_bytes(*p) : 0;
+}
+
+int vivim_seg_metrics(const vivim_seg_metrics_params* p, void* stream) {
+    VCHECK(p != nullptr);
+    VCHECK(dtype_ok(p->itype) && (p->ttype == 0 || p->ttype == 1));
+    VCHECK(p->batch > 0 && p->pixels > 0);
+    if (p->classes < 2 || p->classes > 8)
+        return fail(VIVIM_ERR_UNSUPPORTED, "seg_metrics: %d classes: the kernels are built for 2 to 8 classes", p->classes);
+    VCHECK((int64_t)p->batch * 64 <= INT32_MAX);                  // one workgroup index per (image, block)
+    const uintptr_t ib = p->itype == VIVIM_F32 ? 4 : 2, tbytes = p->ttype == 0 ? 8 : 1;
+    VCHECK(p->logits && reinterpret_cast<uintptr_t>(p->logits) % ib == 0);
+    VCHECK(p->target && reinterpret_cast<uintptr_t>(p->target) % tbytes == 0);
+    VCHECK(p->counts && reinterpret_cast<uintptr_t>(p->counts) % 4 == 0);
+    VCHECK(reinterpret_cast<uintptr_t>(p->state) % 8 == 0);         // NULL: not wanted (pred: any address)
+    const size_t need = vivim::seg_metrics_workspace_bytes(*p);
+    if (p->workspace == nullptr || reinterpret_cast<uintptr_t>(p->workspace) % 4 != 0 || p->workspace_bytes < 0 ||
+        (size_t)p->workspace_bytes < need)
+        return fail(VIVIM_ERR_INVALID, "seg_metrics: workspace of %lld bytes at %p: need a 4-byte aligned one of "
+                    "vivim_seg_metrics_workspace_bytes() = %zu", (long long)p->workspace_bytes, p->workspace, need);
+    if (!vivim::seg_metrics_dispatch(*p, static_cast<hipStream_t>(stream)))
+        return fail(VIVIM_ERR_UNSUPPORTED, "seg_metrics not implemented for input type %d / %d classes", p->itype, p->classes);
+    return after_launch("seg_metrics");
 }
 
 }  // extern "C"

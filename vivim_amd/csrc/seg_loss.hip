@@ -12,8 +12,8 @@
 // slot order, writes the loss and, per (image, class), the two Tversky gradient factors the backward needs.
 // seg_loss_bwd_kernel recomputes the softmax with the same tiling and writes dlogits in the logits' type.
 // Labels are only ever COMPARED with the class index: a label outside [0, C) is a pixel that belongs to no class.
-#include <initializer_list>
 #include "common.cuh"
+#include "seg_load.cuh"      // sl_load, sl_labels, sl_aligned16: shared with seg_metrics.hip
 
 namespace vivim {
 
@@ -32,60 +32,6 @@ size_t seg_loss_workspace_bytes(const vivim_seg_loss_params& p) {
 
 // which of the three tensors a workgroup may move in whole 16-byte vectors (host-side alignment verdicts, wave-uniform)
 enum { kSlVecLogits = 1, kSlVecTarget = 2, kSlVecDlogits = 4 };
-
-// E consecutive pixels of C channel rows, widened to f32; pixels >= nv read as 0
-template <typename T, int C, int E>
-__device__ __forceinline__ void sl_load(const T* __restrict__ base, int64_t c_stride, int nv, bool vec, float (&x)[C][E]) {
-    if (vec && nv >= E) {
-#pragma unroll
-        for (int c = 0; c < C; ++c) {
-            const RawK<T, E> r = load_vec<T, E>(base + c * c_stride, true);
-            unpack<T, E>(r, x[c]);
-        }
-    } else {
-#pragma unroll
-        for (int c = 0; c < C; ++c)
-#pragma unroll
-            for (int k = 0; k < E; ++k) x[c][k] = k < nv ? to_f32<T>(base[c * c_stride + k]) : 0.0f;
-    }
-}
-
-__device__ __forceinline__ int sl_label64(uint32_t lo, uint32_t hi) { return hi == 0u && lo < 256u ? (int)lo : -1; }
-
-// E labels as ints in [0, 256) or -1 (any other value, or a pixel >= nv): only compared with c afterwards
-template <int E>
-__device__ __forceinline__ void sl_labels(const void* __restrict__ target, int ttype, int64_t off, int nv, bool vec, int (&lab)[E]) {
-    if (ttype == 0) {
-        const int64_t* __restrict__ q = static_cast<const int64_t*>(target) + off;
-        if (vec && nv >= E) {
-#pragma unroll
-            for (int i = 0; i < E / 2; ++i) {
-                const u32x4 v = reinterpret_cast<const u32x4*>(q)[i];
-                lab[2 * i] = sl_label64(v.x, v.y);
-                lab[2 * i + 1] = sl_label64(v.z, v.w);
-            }
-        } else {
-#pragma unroll
-            for (int k = 0; k < E; ++k) {
-                const int64_t v = k < nv ? q[k] : (int64_t)-1;
-                lab[k] = v >= 0 && v < 256 ? (int)v : -1;
-            }
-        }
-    } else {
-        const uint8_t* __restrict__ q = static_cast<const uint8_t*>(target) + off;
-        if (vec && nv >= E) {
-#pragma unroll
-            for (int i = 0; i < E / 4; ++i) {
-                const uint32_t v = reinterpret_cast<const uint32_t*>(q)[i];
-#pragma unroll
-                for (int j = 0; j < 4; ++j) lab[4 * i + j] = (int)((v >> (8 * j)) & 255u);
-            }
-        } else {
-#pragma unroll
-            for (int k = 0; k < E; ++k) lab[k] = k < nv ? (int)q[k] : -1;
-        }
-    }
-}
 
 // softmax of one pixel: p_c and q_c = 1 - p_c as the other classes' share of the denominator
 template <int C>
@@ -268,13 +214,6 @@ __global__ void __launch_bounds__(kSlThreads) seg_loss_bwd_kernel(const vivim_se
                     if (k < nv) db[c * p.dlogits_c_stride + pix0 + k] = from_f32<T>(x[c][k]);
         }
     }
-}
-
-static bool sl_aligned16(const void* q, int64_t elem_bytes, std::initializer_list<int64_t> strides) {
-    if (reinterpret_cast<uintptr_t>(q) & 15) return false;
-    for (int64_t s : strides)
-        if ((s * elem_bytes) & 15) return false;
-    return true;
 }
 
 template <typename T, int C>

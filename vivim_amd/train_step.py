@@ -189,3 +189,24 @@ def train_step(model, optimizer, clip, onehot, num_classes, amp_dtype=torch.bflo
         torch.nn.utils.clip_grad_norm_([p for p in model.parameters() if p.grad is not None], clip_grad_norm)
     optimizer.step()
     return loss.detach()
+
+
+def eval_step(model, clip, onehot, num_classes, tracker=None, amp_dtype=torch.bfloat16, fused_loss=False):
+    """The validation counterpart of train_step: forward under no_grad + autocast, the loss (eager, or the fused kernels with
+    `fused_loss=True`), and, when a `tracker` (seg_metrics.SegMetricsTracker) is given, its update with the logits and the label
+    map -- two launches on the device, no host synchronisation.  Returns the detached loss."""
+    if model.training:                     # Module.eval() walks all ~4000 submodules, like train() in train_step
+        model.eval()
+    with torch.no_grad():
+        with torch.autocast("cuda", dtype=amp_dtype, enabled=amp_dtype != torch.float32):
+            logits = model(clip)                               # (B*nf, C, H, W)
+        B, T = onehot.shape[:2]
+        target = onehot.argmax(dim=2).view(B * T, *onehot.shape[-2:])
+        if fused_loss:
+            from .seg_loss import recall_focused_loss_fused
+            loss = recall_focused_loss_fused(logits, target, num_classes)
+        else:
+            loss = recall_focused_loss(logits, target, num_classes)
+        if tracker is not None:
+            tracker.update(logits, target)
+    return loss.detach()
