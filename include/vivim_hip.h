@@ -392,12 +392,37 @@ typedef struct {
     int64_t workspace_bytes;
 } vivim_seg_metrics_params;
 
+/* ---- Bilinear 2-D upsampling, align_corners = False, no explicit scale factors (csrc/upsample.hip; opt-in in Vivim) ----------
+ * ATen's definition, per axis in fp32:  r = float(n_in) / float(n_out);  src = max(0, r * (o + 0.5) - 0.5);  i0 = (int)src;
+ * i1 = i0 + (i0 < n_in - 1);  l1 = src - i0;  l0 = 1 - l1.
+ *   forward : y[oh][ow] = l0h * (l0w * x[i0h][i0w] + l1w * x[i0h][i1w]) + l1h * (l0w * x[i1h][i0w] + l1w * x[i1h][i1w]), fp32, rounded
+ *             once to itype
+ *   backward: dx = the transpose of that linear map applied to dy, in GATHER form: every dx element adds, in ascending output
+ *             order, the dy elements whose taps (recomputed with the forward's own expressions) name it.
+ * Determinism: no atomics and no workspace; y and dx are pure functions of the inputs and the shape.
+ * layout 0, planes: x / dx are (batch, channels, in_h, in_w) and y / dy (batch, channels, out_h, out_w), each image contiguous.
+ * layout 1, channels-last: x / dx are (batch, in_h, in_w, channels) MEMORY and y / dy (batch, out_h, out_w, channels), each image
+ * dense; 16-byte accesses when channels is a whole number of them and bases and batch strides are 16-byte aligned, element
+ * accesses otherwise (element-size alignment is the only requirement).  Batch strides are free, in elements.
+ * Upsampling only: out_h >= in_h and out_w >= in_w, else VIVIM_ERR_UNSUPPORTED.  An image (channels * h * w elements, input and
+ * output), (2 * n_in + 3) * n_out per axis and the number of workgroups must fit 31 bits, else VIVIM_ERR_INVALID. */
+typedef struct {
+    int32_t batch, channels, in_h, in_w, out_h, out_w;
+    int32_t itype;                                   /* x, y, dy, dx: vivim_dtype_t */
+    int32_t layout;                                  /* 0 = planes, 1 = channels-last */
+    int64_t x_batch_stride, y_batch_stride;          /* of x and dx / of y and dy, in elements */
+    const void *x;                                   /* forward input */
+    void *y;                                         /* forward output */
+    const void *dy;                                  /* backward input */
+    void *dx;                                        /* backward output */
+} vivim_upsample_params;
+
 int vivim_abi_version(void);
 const char *vivim_last_error(void);
 
 /* sizeof() of a params struct as this library was compiled, so a foreign-language binding can assert
  * its own layout: which = 0 ssm_fwd, 1 ssm_bwd, 2 conv_fwd, 3 conv_bwd, 4 dwconv, 5 dwconv_wgrad, 6 dir, 7 conv_update,
- * 8 state_update, 9 layernorm, 10 wgrad_nt, 11 add_layernorm, 12 seg_loss, 13 seg_metrics; 0 for anything else. */
+ * 8 state_update, 9 layernorm, 10 wgrad_nt, 11 add_layernorm, 12 seg_loss, 13 seg_metrics, 14 upsample; 0 for anything else. */
 size_t vivim_sizeof(int which);
 
 /* Tokens per checkpoint row of `x`: n_chunks = ceil(seqlen / vivim_scan_ckpt_len(f)).  Depends on the sizes and flags in
@@ -452,6 +477,8 @@ int vivim_seg_loss_bwd(const vivim_seg_loss_params *p, void *stream);
 size_t vivim_seg_loss_workspace_bytes(const vivim_seg_loss_params *p);   /* from batch, classes, pixels, itype; 0 on bad sizes */
 int vivim_seg_metrics(const vivim_seg_metrics_params *p, void *stream);
 size_t vivim_seg_metrics_workspace_bytes(const vivim_seg_metrics_params *p);   /* from batch, classes, pixels, itype; 0 on bad sizes */
+int vivim_upsample_bilinear2d_fwd(const vivim_upsample_params *p, void *stream);   /* reads x, writes y */
+int vivim_upsample_bilinear2d_bwd(const vivim_upsample_params *p, void *stream);   /* reads dy, writes dx */
 
 /* Deterministic backward (for torch.use_deterministic_algorithms).  Same parameters, checks and results as
  * vivim_selective_scan_bwd, and the same kernel family, but every gradient that the default call adds up across

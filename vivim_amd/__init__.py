@@ -14,4 +14,7 @@ def __getattr__(name):
     if name in ("SegMetricsTracker", "seg_confusion_counts"):
         from . import seg_metrics
         return getattr(seg_metrics, name)
+    if name == "bilinear_upsample":                    # the decode head's upsampling (upsample.py), likewise
+        from . import upsample
+        return upsample.bilinear_upsample
     raise AttributeError(f"module {__name__!r} has no attribute {name!r}")

@@ -147,6 +147,12 @@ class SegMetricsParams(ctypes.Structure):
                 + [("workspace_bytes", i64)])
 
 
+class UpsampleParams(ctypes.Structure):
+    _fields_ = ([(n, i32) for n in ("batch", "channels", "in_h", "in_w", "out_h", "out_w", "itype", "layout")]
+                + [("x_batch_stride", i64), ("y_batch_stride", i64)]
+                + [(n, vp) for n in ("x", "y", "dy", "dx")])
+
+
 EXPORTS = ("vivim_abi_version", "vivim_last_error", "vivim_scan_chunk_len", "vivim_scan_ckpt_len", "vivim_sizeof",
            "vivim_scan_bwd_workspace_bytes", "vivim_scan_fwd_workspace_bytes", "vivim_set_tuning",
            "vivim_selective_scan_fwd", "vivim_selective_scan_bwd", "vivim_selective_scan_fwd_lean",
@@ -158,7 +164,8 @@ EXPORTS = ("vivim_abi_version", "vivim_last_error", "vivim_scan_chunk_len", "viv
            "vivim_dwconv_wgrad_det_workspace_bytes", "vivim_dwconv_wgrad_det",
            "vivim_add_layernorm_cm_fwd", "vivim_add_layernorm_cm_bwd", "vivim_add_layernorm_bwd_workspace_bytes",
            "vivim_seg_loss_fwd", "vivim_seg_loss_bwd", "vivim_seg_loss_workspace_bytes",
-           "vivim_seg_metrics", "vivim_seg_metrics_workspace_bytes")
+           "vivim_seg_metrics", "vivim_seg_metrics_workspace_bytes",
+           "vivim_upsample_bilinear2d_fwd", "vivim_upsample_bilinear2d_bwd")
 
 _lib = None
 
@@ -205,7 +212,9 @@ def lib():
                          ("vivim_add_layernorm_cm_fwd", AddLayerNormParams),
                          ("vivim_add_layernorm_cm_bwd", AddLayerNormParams),
                          ("vivim_seg_loss_fwd", SegLossParams), ("vivim_seg_loss_bwd", SegLossParams),
-                         ("vivim_seg_metrics", SegMetricsParams)):
+                         ("vivim_seg_metrics", SegMetricsParams),
+                         ("vivim_upsample_bilinear2d_fwd", UpsampleParams),
+                         ("vivim_upsample_bilinear2d_bwd", UpsampleParams)):
             fn = getattr(L, name)
             fn.argtypes = [ctypes.POINTER(st), vp]
             fn.restype = ctypes.c_int
@@ -234,7 +243,8 @@ def lib():
             raise ImportError("libvivim_hip.so ABI version mismatch")
         for which, st in enumerate((SsmFwdParams, SsmBwdParams, ConvFwdParams, ConvBwdParams, DwConvParams,
                                     DwConvWgradParams, DirParams, ConvUpdateParams, StateUpdateParams, LayerNormParams,
-                                    WgradNtParams, AddLayerNormParams, SegLossParams, SegMetricsParams)):
+                                    WgradNtParams, AddLayerNormParams, SegLossParams, SegMetricsParams,
+                                    UpsampleParams)):
             if L.vivim_sizeof(which) != ctypes.sizeof(st):
                 raise ImportError(f"struct layout mismatch for {st.__name__}: "
                                   f"C {L.vivim_sizeof(which)} vs ctypes {ctypes.sizeof(st)}")
@@ -256,6 +266,8 @@ def algorithmic_bytes(name, P):
             return n * (2 * _ISIZE[P.itype] + _ISIZE[P.btype] + _ISIZE[P.otype]) + 8 * P.batch * P.seqlen + 8 * P.channels
         res = (_ISIZE[P.itype] if P.dres else 0) + (_ISIZE[P.otype] if P.dy else 0) + (_ISIZE[P.btype] if P.dbranch else 0)
         return n * (2 * _ISIZE[P.itype] + res) + 8 * P.batch * P.seqlen + 12 * P.channels   # x_new, dx + what is present
+    if name.startswith("vivim_upsample"):                               # the small and the large tensor once, either direction
+        return P.batch * P.channels * (P.in_h * P.in_w + P.out_h * P.out_w) * _ISIZE[P.itype]
     if name.startswith("vivim_seg_metrics"):                            # logits, labels, the prediction map if wanted, the counts
         n = P.batch * P.pixels
         return n * (P.classes * _ISIZE[P.itype] + (8 if P.ttype == 0 else 1) + (1 if P.pred else 0)) + 12 * P.batch * P.classes

@@ -42,6 +42,8 @@ bool seg_loss_dispatch(const vivim_seg_loss_params&, bool bwd, hipStream_t);    
 size_t seg_loss_workspace_bytes(const vivim_seg_loss_params&);
 bool seg_metrics_dispatch(const vivim_seg_metrics_params&, hipStream_t);          // seg_metrics.hip
 size_t seg_metrics_workspace_bytes(const vivim_seg_metrics_params&);
+bool upsample_dispatch(const vivim_upsample_params&, bool bwd, hipStream_t);      // upsample.hip
+int64_t upsample_blocks(const vivim_upsample_params&, bool bwd);
 }  // namespace vivim
 
 static thread_local char g_err[512] = "";
@@ -153,6 +155,7 @@ size_t vivim_sizeof(int which) {
         case 11: return sizeof(vivim_add_layernorm_params);
         case 12: return sizeof(vivim_seg_loss_params);
         case 13: return sizeof(vivim_seg_metrics_params);
+        case 14: return sizeof(vivim_upsample_params);
     }
     return 0;
 }
@@ -578,6 +581,41 @@ int vivim_seg_metrics(const vivim_seg_metrics_params* p, void* stream) {
     if (!vivim::seg_metrics_dispatch(*p, static_cast<hipStream_t>(stream)))
         return fail(VIVIM_ERR_UNSUPPORTED, "seg_metrics not implemented for input type %d / %d classes", p->itype, p->classes);
     return after_launch("seg_metrics");
+}
+
+// every refusal of the upsampling calls, before any launch
+static int check_upsample(const vivim_upsample_params* p, bool bwd) {
+    VCHECK(p != nullptr);
+    VCHECK(dtype_ok(p->itype) && (p->layout == 0 || p->layout == 1));
+    VCHECK(p->batch > 0 && p->channels > 0 && p->in_h > 0 && p->in_w > 0 && p->out_h > 0 && p->out_w > 0);
+    if (p->out_h < p->in_h || p->out_w < p->in_w)
+        return fail(VIVIM_ERR_UNSUPPORTED, "upsample_bilinear2d: (%d, %d) -> (%d, %d): upsampling only", p->in_h, p->in_w, p->out_h,
+                    p->out_w);
+    const uintptr_t ib = p->itype == VIVIM_F32 ? 4 : 2;
+    const void* src = bwd ? p->dy : p->x;
+    const void* dst = bwd ? p->dx : p->y;
+    VCHECK(src != nullptr && reinterpret_cast<uintptr_t>(src) % ib == 0);
+    VCHECK(dst != nullptr && reinterpret_cast<uintptr_t>(dst) % ib == 0);
+    // the kernels index inside an image, and build their windows and their grid, with 32-bit integers
+    VCHECK((int64_t)p->channels * p->in_h * p->in_w <= INT32_MAX && (int64_t)p->channels * p->out_h * p->out_w <= INT32_MAX);
+    VCHECK((2 * (int64_t)p->in_h + 3) * p->out_h <= INT32_MAX && (2 * (int64_t)p->in_w + 3) * p->out_w <= INT32_MAX);
+    VCHECK((int64_t)p->batch * p->channels <= INT32_MAX && (int64_t)p->batch * p->out_h <= INT32_MAX);
+    VCHECK(vivim::upsample_blocks(*p, bwd) <= INT32_MAX);
+    return VIVIM_OK;
+}
+
+int vivim_upsample_bilinear2d_fwd(const vivim_upsample_params* p, void* stream) {
+    if (int rc = check_upsample(p, false)) return rc;
+    if (!vivim::upsample_dispatch(*p, false, static_cast<hipStream_t>(stream)))
+        return fail(VIVIM_ERR_UNSUPPORTED, "upsample_bilinear2d_fwd not implemented for type %d", p->itype);
+    return after_launch("upsample_bilinear2d_fwd");
+}
+
+int vivim_upsample_bilinear2d_bwd(const vivim_upsample_params* p, void* stream) {
+    if (int rc = check_upsample(p, true)) return rc;
+    if (!vivim::upsample_dispatch(*p, true, static_cast<hipStream_t>(stream)))
+        return fail(VIVIM_ERR_UNSUPPORTED, "upsample_bilinear2d_bwd not implemented for type %d", p->itype);
+    return after_launch("upsample_bilinear2d_bwd");
 }
 
 }  // extern "C"

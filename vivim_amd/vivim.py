@@ -16,6 +16,9 @@ Differences from the reference, all additive:
   * the Mlp's depthwise Conv3d runs on the token-major HIP kernel (csrc/dwconv.hip) when the
     tensor qualifies; `fast_backbone_dwconv=True` swaps the SegFormer blocks' DropPath for the one-kernel form and routes the SegFormer Mix-FFN 3x3 depthwise convs
     through the same kernel (same parameters, same math, state-dict keys unchanged).
+  * `Vivim(..., fused_upsample=True)` takes the decode head's bilinear upsampling (the per-stage features, the logits and the
+    edge map) through csrc/upsample.hip, whose gather-form backward is bit-repeatable and runs under
+    torch.use_deterministic_algorithms(True) (upsample.py); off by default, `VIVIM_NO_UPSAMPLE=1` opts out again.
   * timm is not required: DropPath / trunc_normal_ are the torch equivalents.
 """
 import math
@@ -28,6 +31,7 @@ import torch.nn.functional as F
 
 from . import dwconv as _dw
 from . import layernorm as _ln
+from . import upsample as _up
 from .mamba_simple import Mamba
 
 
@@ -325,8 +329,10 @@ class Vivim(nn.Module):
     def __init__(self, in_chans=3, out_chans=3, depths=[2, 2, 2, 2], feat_size=[64, 128, 320, 512],
                  drop_path_rate=0.2, layer_scale_init_value=1e-6, hidden_size: int = 768, norm_name="instance",
                  conv_block: bool = True, res_block: bool = True, spatial_dims=2, with_edge=False,
-                 dropout_rate=0.3, backbone=None, mamba_kwargs=None, fast_backbone_dwconv=False) -> None:
+                 dropout_rate=0.3, backbone=None, mamba_kwargs=None, fast_backbone_dwconv=False,
+                 fused_upsample=False) -> None:
         super().__init__()
+        self.fused_upsample = fused_upsample
         self.hidden_size = hidden_size
         self.in_chans, self.out_chans = in_chans, out_chans
         self.depths, self.feat_size = depths, feat_size
@@ -347,6 +353,11 @@ class Vivim(nn.Module):
         if with_edge:
             self.edgeocr_cls_head = nn.Conv2d(64, 1, kernel_size=1, stride=1, padding=0, bias=True)
 
+    def _upsample(self, x, size):
+        if self.fused_upsample:
+            return _up.bilinear_upsample(x, size)
+        return F.interpolate(x, size=size, mode="bilinear", align_corners=False)
+
     def _decoder_projections(self):
         dec = self.decoder
         return dec.linear_c if hasattr(dec, "linear_c") else dec.linear_projections
@@ -358,7 +369,7 @@ class Vivim(nn.Module):
         for state, mlp in zip(encoder_hidden_states, self._decoder_projections()):
             height, width = state.shape[2], state.shape[3]
             state = mlp(state).permute(0, 2, 1).reshape(batch_size, -1, height, width)
-            state = F.interpolate(state, size=size0, mode="bilinear", align_corners=False)
+            state = self._upsample(state, size0)
             if torch.rand(1).item() > 0.5:          # per-map dropout coin flip on the CPU RNG (vivim.py:310-312)
                 state = F.dropout(state, p=self.dropout_rate / 2, training=self.training)
             feats += (state,)
@@ -376,8 +387,8 @@ class Vivim(nn.Module):
     def forward(self, x_in):
         bz, nf, nc, h, w = x_in.shape
         outs = self.encoder(x_in)
-        logits = F.interpolate(self.decode(outs, bz, nf), size=(h, w), mode="bilinear", align_corners=False)
+        logits = self._upsample(self.decode(outs, bz, nf), (h, w))
         if self.with_edge:
-            edge = F.interpolate(self.edgeocr_cls_head(outs[0]), size=(h, w), mode="bilinear", align_corners=False)
+            edge = self._upsample(self.edgeocr_cls_head(outs[0]), (h, w))
             return logits, edge
         return logits
