@@ -26,11 +26,11 @@ def test_header_symbols_exported():
 
 def test_struct_layouts_match():
     L = _lib.lib()
-    for which, st in enumerate((_lib.SsmFwdParams, _lib.SsmBwdParams, _lib.ConvFwdParams, _lib.ConvBwdParams,
-                                _lib.DwConvParams, _lib.DwConvWgradParams, _lib.DirParams, _lib.ConvUpdateParams,
-                                _lib.StateUpdateParams, _lib.LayerNormParams, _lib.WgradNtParams)):
-        assert L.vivim_sizeof(which) == ctypes.sizeof(st)
-    assert L.vivim_sizeof(99) == 0
+    assert len(_lib.STRUCTS) == 15
+    for which, st in enumerate(_lib.STRUCTS):
+        assert L.vivim_sizeof(which) == ctypes.sizeof(st), st.__name__
+    assert len(_lib.STRUCTS) == 1 + max(which for which in range(256) if L.vivim_sizeof(which))
+    assert L.vivim_sizeof(99) == 0 and L.vivim_sizeof(-1) == 0
     assert L.vivim_abi_version() == 8
     assert L.vivim_scan_chunk_len(_lib.F32) > 0 and L.vivim_scan_chunk_len(_lib.BF16) % 64 == 0
 
@@ -135,6 +135,103 @@ def test_rejects_before_launch():
 def test_call_raises_runtime_error():
     with pytest.raises(RuntimeError, match="check failed"):
         _lib.call("vivim_selective_scan_fwd", _lib.SsmFwdParams(), 0)
+
+
+LAUNCHING = [name for name, e in _lib.ENTRY_POINTS.items() if e.struct is not None and e.stream]
+
+
+def test_entry_point_table_is_the_header():
+    """Every declared function has one entry; the launching ones are those that take a params struct and a stream."""
+    assert list(_lib.EXPORTS) == list(_lib.ENTRY_POINTS) and len(set(_lib.EXPORTS)) == len(_lib.EXPORTS)
+    assert len(LAUNCHING) == 24 and all(_lib.ENTRY_POINTS[n].restype is ctypes.c_int for n in LAUNCHING)
+    with_extras = {n: _lib.ENTRY_POINTS[n].extra for n in LAUNCHING if _lib.ENTRY_POINTS[n].extra}
+    det = (ctypes.c_void_p, ctypes.c_size_t)
+    assert with_extras == {"vivim_selective_scan_fwd_lean": (ctypes.c_void_p,), "vivim_selective_scan_bwd_det": det,
+                           "vivim_causal_conv1d_bwd_det": det, "vivim_dwconv_wgrad_det": det}
+
+
+@pytest.mark.parametrize("name", LAUNCHING)
+def test_call_reaches_every_entry_point(name):
+    """An all-zero struct fails the entry point's first size check: `call` passes the right number of arguments to every
+    launching function, and nothing is launched."""
+    e = _lib.ENTRY_POINTS[name]
+    with pytest.raises(RuntimeError) as info:
+        _lib.call(name, e.struct(), 0, *([0] * len(e.extra)))
+    assert str(info.value)
+
+
+def _both_ways(name, P, *extra):
+    """The refusal text of `name` through _lib.call and through the ctypes function itself."""
+    L = _lib.lib()
+    assert getattr(L, name)(ctypes.byref(P), *extra, None) != 0
+    direct = L.vivim_last_error().decode()
+    with pytest.raises(RuntimeError) as info:
+        _lib.call(name, P, 0, *extra)
+    assert direct and str(info.value) == direct
+    return direct
+
+
+def test_call_passes_extras_in_c_order():
+    """The arguments between params and stream arrive in the C signature's order: the workspace refusals of the three
+    deterministic calls print the pointer and the byte count they were given, the lean forward takes last_state."""
+    import test_abi_deterministic as det
+    import test_abi_lean_fwd as lean
+    conv, conv_need = det._conv_bwd_params()
+    dw, dw_need = det._dw_wgrad_params()
+    scan = det._bwd_params()
+    scan_need = _lib.lib().vivim_scan_bwd_det_call_workspace_bytes(ctypes.byref(scan))
+    for name, P, need in (("vivim_selective_scan_bwd_det", scan, scan_need), ("vivim_causal_conv1d_bwd_det", conv, conv_need),
+                          ("vivim_dwconv_wgrad_det", dw, dw_need)):
+        assert need > 4
+        assert "workspace of %d bytes at (nil)" % need in _both_ways(name, P, None, need)              # null workspace
+        assert "workspace of %d bytes at 0x1000" % (need - 4) in _both_ways(name, P, 4096, need - 4)   # short workspace
+    for z in (True, False):
+        P = lean._params(z=z)
+        P.x = lean.PTR
+        for last_state in (None, lean.PTR):
+            assert "x must be NULL" in _both_ways(lean.LEAN, P, last_state)
+
+
+def test_launch_enters_the_device_context_only_off_the_current_device(monkeypatch):
+    """_lib.launch with torch.cuda stubbed out (no GPU here): on the current device it calls `call` on the current stream
+    with no context manager; for another device it enters torch.cuda.device(that device) first and takes that device's
+    current stream.  The extras are passed through after the stream."""
+    import contextlib
+    import types
+
+    import torch
+    state = {"current": 0}
+    events = []
+
+    @contextlib.contextmanager
+    def device(dev):
+        prev, state["current"] = state["current"], dev.index
+        events.append(("enter", dev.index))
+        yield
+        state["current"] = prev
+        events.append(("exit", dev.index))
+
+    monkeypatch.setattr(torch.cuda, "current_device", lambda: state["current"])
+    monkeypatch.setattr(torch.cuda, "device", device)
+    monkeypatch.setattr(torch.cuda, "current_stream", lambda: types.SimpleNamespace(cuda_stream=1000 + state["current"]))
+    monkeypatch.setattr(_lib, "call", lambda *args: events.append(("call",) + args))
+    P = _lib.ConvBwdParams()
+    _lib.launch("vivim_causal_conv1d_bwd", P, torch.device("cuda", 0))
+    assert events == [("call", "vivim_causal_conv1d_bwd", P, 1000)]
+    del events[:]
+    _lib.launch("vivim_causal_conv1d_bwd_det", P, torch.device("cuda", 1), 4096, 64)
+    assert events == [("enter", 1), ("call", "vivim_causal_conv1d_bwd_det", P, 1001, 4096, 64), ("exit", 1)]
+    assert state["current"] == 0
+
+
+def test_algorithmic_bytes_of_the_deterministic_twins():
+    """A `*_det` name counts the bytes of its default twin, read from the struct's forward half."""
+    import test_abi_deterministic as det
+    for name, P in (("vivim_selective_scan_bwd", det._bwd_params()), ("vivim_causal_conv1d_bwd", det._conv_bwd_params()[0]),
+                    ("vivim_dwconv_wgrad", det._dw_wgrad_params()[0])):
+        assert _lib.algorithmic_bytes(name + "_det", P) == _lib.algorithmic_bytes(name, P) > 0
+    conv = det._conv_bwd_params()[0]
+    assert _lib.algorithmic_bytes("vivim_causal_conv1d_bwd_det", conv) == 3 * 2 * 64 * 4096 * 2 + 8 * 64 * 5
 
 
 def test_python_surface_imports_without_gpu():

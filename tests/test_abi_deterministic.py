@@ -138,28 +138,39 @@ def test_det_call_workspace_exact_per_family():
         L.vivim_set_tuning(1, prev[1])
 
 
-def test_conv_and_dwconv_det_reject_before_launch():
-    L = _lib.lib()
+def _conv_bwd_params():
+    """Conv1d backward params that pass every check (never dereferenced pointers) and their det workspace size."""
     f = _lib.ConvFwdParams()
     f.batch, f.dim, f.seqlen, f.width, f.itype, f.wtype = 2, 64, 4096, 4, _lib.BF16, _lib.F32
     f.x_batch_stride, f.x_c_stride, f.x_l_stride = 64 * 4096, 4096, 1
     f.x = f.weight = 1 << 20
-    need = L.vivim_causal_conv1d_bwd_det_workspace_bytes(ctypes.byref(f))
-    assert need == 4 * 2 * (4096 // 2048) * 64 * 5                # batch * tiles of 256 x 8 tokens, dim * (width + 1)
+    need = _lib.lib().vivim_causal_conv1d_bwd_det_workspace_bytes(ctypes.byref(f))
     p = _lib.ConvBwdParams()
     ctypes.memmove(ctypes.addressof(p.f), ctypes.addressof(f), ctypes.sizeof(f))
     p.dout = p.dx = p.dweight = 1 << 20
     p.dout_l_stride = p.dx_l_stride = 1
-    assert L.vivim_causal_conv1d_bwd_det(ctypes.byref(p), None, need, None) == 1
-    assert L.vivim_causal_conv1d_bwd_det(ctypes.byref(p), 4096, need - 4, None) == 1
-    p.f.width = 5
-    assert L.vivim_causal_conv1d_bwd_det(ctypes.byref(p), 4096, need, None) == 1
+    return p, need
+
+
+def _dw_wgrad_params():
+    """Depthwise weight-gradient params that pass every check and their det workspace size."""
     w = _lib.DwConvWgradParams()
     w.batch, w.depth, w.height, w.width, w.channels, w.kd, w.itype = 2, 3, 16, 16, 64, 3, _lib.BF16
     w.x = w.dy = w.dwt = 1 << 20
     w.x_token_stride = w.dy_token_stride = 64
     w.x_batch_stride = w.dy_batch_stride = 64 * 768
-    dneed = L.vivim_dwconv_wgrad_det_workspace_bytes(ctypes.byref(w))
+    return w, _lib.lib().vivim_dwconv_wgrad_det_workspace_bytes(ctypes.byref(w))
+
+
+def test_conv_and_dwconv_det_reject_before_launch():
+    L = _lib.lib()
+    p, need = _conv_bwd_params()
+    assert need == 4 * 2 * (4096 // 2048) * 64 * 5                # batch * tiles of 256 x 8 tokens, dim * (width + 1)
+    assert L.vivim_causal_conv1d_bwd_det(ctypes.byref(p), None, need, None) == 1
+    assert L.vivim_causal_conv1d_bwd_det(ctypes.byref(p), 4096, need - 4, None) == 1
+    p.f.width = 5
+    assert L.vivim_causal_conv1d_bwd_det(ctypes.byref(p), 4096, need, None) == 1
+    w, dneed = _dw_wgrad_params()
     assert dneed > 0 and dneed % (4 * 28 * 64 * 2) == 0           # whole (batch, block) slots of 28 x channels floats
     assert L.vivim_dwconv_wgrad_det(ctypes.byref(w), None, dneed, None) == 1
     assert L.vivim_dwconv_wgrad_det(ctypes.byref(w), 4096, dneed - 4, None) == 1

@@ -3,9 +3,12 @@
 The library is the product: if it is missing or fails to load this module raises -- there is no
 PyTorch/CPU fallback anywhere in vivim_amd.
 """
+import collections
 import ctypes
 import os
 import subprocess
+
+import torch
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(_HERE, "csrc")
@@ -153,19 +156,68 @@ class UpsampleParams(ctypes.Structure):
                 + [(n, vp) for n in ("x", "y", "dy", "dx")])
 
 
-EXPORTS = ("vivim_abi_version", "vivim_last_error", "vivim_scan_chunk_len", "vivim_scan_ckpt_len", "vivim_sizeof",
-           "vivim_scan_bwd_workspace_bytes", "vivim_scan_fwd_workspace_bytes", "vivim_set_tuning",
-           "vivim_selective_scan_fwd", "vivim_selective_scan_bwd", "vivim_selective_scan_fwd_lean",
-           "vivim_causal_conv1d_fwd", "vivim_causal_conv1d_bwd", "vivim_dwconv_fwd", "vivim_dwconv_wgrad",
-           "vivim_dir_scatter", "vivim_dir_gather", "vivim_causal_conv1d_update", "vivim_selective_state_update",
-           "vivim_layernorm_cm_fwd", "vivim_layernorm_cm_bwd", "vivim_layernorm_bwd_workspace_bytes", "vivim_wgrad_nt",
-           "vivim_scan_bwd_det_workspace_bytes", "vivim_scan_bwd_det_call_workspace_bytes", "vivim_selective_scan_bwd_det",
-           "vivim_causal_conv1d_bwd_det_workspace_bytes", "vivim_causal_conv1d_bwd_det",
-           "vivim_dwconv_wgrad_det_workspace_bytes", "vivim_dwconv_wgrad_det",
-           "vivim_add_layernorm_cm_fwd", "vivim_add_layernorm_cm_bwd", "vivim_add_layernorm_bwd_workspace_bytes",
-           "vivim_seg_loss_fwd", "vivim_seg_loss_bwd", "vivim_seg_loss_workspace_bytes",
-           "vivim_seg_metrics", "vivim_seg_metrics_workspace_bytes",
-           "vivim_upsample_bilinear2d_fwd", "vivim_upsample_bilinear2d_bwd")
+# The structs in vivim_sizeof order.
+STRUCTS = (SsmFwdParams, SsmBwdParams, ConvFwdParams, ConvBwdParams, DwConvParams, DwConvWgradParams, DirParams,
+           ConvUpdateParams, StateUpdateParams, LayerNormParams, WgradNtParams, AddLayerNormParams, SegLossParams,
+           SegMetricsParams, UpsampleParams)
+
+# One entry per exported function: its params struct (or None), the ctypes types of the arguments between `params` and
+# `stream` in the C signature, whether a stream comes last, and the restype.
+Entry = collections.namedtuple("Entry", "struct extra stream restype")
+_int, _size = ctypes.c_int, ctypes.c_size_t
+
+
+def _kernel(struct, *extra):
+    return Entry(struct, extra, True, _int)
+
+
+def _query(struct, restype=_size):
+    return Entry(struct, (), False, restype)
+
+
+ENTRY_POINTS = {
+    "vivim_abi_version": Entry(None, (), False, _int),
+    "vivim_last_error": Entry(None, (), False, ctypes.c_char_p),
+    "vivim_scan_chunk_len": Entry(None, (_int,), False, _int),
+    "vivim_sizeof": Entry(None, (_int,), False, _size),
+    "vivim_set_tuning": Entry(None, (_int, _int), False, _int),
+    "vivim_scan_ckpt_len": _query(SsmFwdParams, _int),
+    "vivim_scan_fwd_workspace_bytes": _query(SsmFwdParams),
+    "vivim_scan_bwd_workspace_bytes": _query(SsmFwdParams),
+    "vivim_selective_scan_fwd": _kernel(SsmFwdParams),
+    "vivim_selective_scan_fwd_lean": _kernel(SsmFwdParams, vp),
+    "vivim_selective_scan_bwd": _kernel(SsmBwdParams),
+    "vivim_scan_bwd_det_workspace_bytes": _query(SsmFwdParams),
+    "vivim_scan_bwd_det_call_workspace_bytes": _query(SsmBwdParams),
+    "vivim_selective_scan_bwd_det": _kernel(SsmBwdParams, vp, _size),
+    "vivim_causal_conv1d_fwd": _kernel(ConvFwdParams),
+    "vivim_causal_conv1d_bwd": _kernel(ConvBwdParams),
+    "vivim_causal_conv1d_bwd_det_workspace_bytes": _query(ConvFwdParams),
+    "vivim_causal_conv1d_bwd_det": _kernel(ConvBwdParams, vp, _size),
+    "vivim_dwconv_fwd": _kernel(DwConvParams),
+    "vivim_dwconv_wgrad": _kernel(DwConvWgradParams),
+    "vivim_dwconv_wgrad_det_workspace_bytes": _query(DwConvWgradParams),
+    "vivim_dwconv_wgrad_det": _kernel(DwConvWgradParams, vp, _size),
+    "vivim_dir_scatter": _kernel(DirParams),
+    "vivim_dir_gather": _kernel(DirParams),
+    "vivim_causal_conv1d_update": _kernel(ConvUpdateParams),
+    "vivim_selective_state_update": _kernel(StateUpdateParams),
+    "vivim_layernorm_cm_fwd": _kernel(LayerNormParams),
+    "vivim_layernorm_cm_bwd": _kernel(LayerNormParams),
+    "vivim_layernorm_bwd_workspace_bytes": _query(LayerNormParams),
+    "vivim_wgrad_nt": _kernel(WgradNtParams),
+    "vivim_add_layernorm_cm_fwd": _kernel(AddLayerNormParams),
+    "vivim_add_layernorm_cm_bwd": _kernel(AddLayerNormParams),
+    "vivim_add_layernorm_bwd_workspace_bytes": _query(AddLayerNormParams),
+    "vivim_seg_loss_fwd": _kernel(SegLossParams),
+    "vivim_seg_loss_bwd": _kernel(SegLossParams),
+    "vivim_seg_loss_workspace_bytes": _query(SegLossParams),
+    "vivim_seg_metrics": _kernel(SegMetricsParams),
+    "vivim_seg_metrics_workspace_bytes": _query(SegMetricsParams),
+    "vivim_upsample_bilinear2d_fwd": _kernel(UpsampleParams),
+    "vivim_upsample_bilinear2d_bwd": _kernel(UpsampleParams),
+}
+EXPORTS = tuple(ENTRY_POINTS)
 
 _lib = None
 
@@ -186,65 +238,18 @@ def lib():
             raise ImportError(
                 f"{SO_PATH} is missing: run `python -c 'import __graft_entry__ as g; g.build()'` "
                 "(or `make -C vivim_amd/csrc`). vivim_amd has no fallback path.")
-        # torch first: its bundled HIP runtime must be the one this process initialises -- loading the library (and with it
-        # /opt/rocm's libamdhip64) before `import torch` leaves two runtimes in the process and every launch of ours then fails
-        # with "no ROCm-capable device is detected" (seen with build() followed by smoke() in one process)
-        import torch  # noqa: F401
+        # torch is imported above, before the library: its bundled HIP runtime must be the one this process initialises --
+        # loading the library (and with it /opt/rocm's libamdhip64) before `import torch` leaves two runtimes in the process
+        # and every launch of ours then fails with "no ROCm-capable device is detected" (seen with build() followed by
+        # smoke() in one process)
         L = ctypes.CDLL(SO_PATH)
-        L.vivim_last_error.restype = ctypes.c_char_p
-        L.vivim_sizeof.restype = ctypes.c_size_t
-        L.vivim_sizeof.argtypes = [ctypes.c_int]
-        L.vivim_set_tuning.restype = ctypes.c_int
-        L.vivim_set_tuning.argtypes = [ctypes.c_int, ctypes.c_int]
-        L.vivim_scan_ckpt_len.restype = ctypes.c_int
-        L.vivim_scan_ckpt_len.argtypes = [ctypes.POINTER(SsmFwdParams)]
-        for fn in (L.vivim_scan_bwd_workspace_bytes, L.vivim_scan_fwd_workspace_bytes):
-            fn.restype = ctypes.c_size_t
-            fn.argtypes = [ctypes.POINTER(SsmFwdParams)]
-        for name, st in (("vivim_selective_scan_fwd", SsmFwdParams), ("vivim_selective_scan_bwd", SsmBwdParams),
-                         ("vivim_causal_conv1d_fwd", ConvFwdParams), ("vivim_causal_conv1d_bwd", ConvBwdParams),
-                         ("vivim_dwconv_fwd", DwConvParams), ("vivim_dwconv_wgrad", DwConvWgradParams),
-                         ("vivim_dir_scatter", DirParams), ("vivim_dir_gather", DirParams),
-                         ("vivim_causal_conv1d_update", ConvUpdateParams),
-                         ("vivim_selective_state_update", StateUpdateParams),
-                         ("vivim_layernorm_cm_fwd", LayerNormParams), ("vivim_layernorm_cm_bwd", LayerNormParams),
-                         ("vivim_wgrad_nt", WgradNtParams),
-                         ("vivim_add_layernorm_cm_fwd", AddLayerNormParams),
-                         ("vivim_add_layernorm_cm_bwd", AddLayerNormParams),
-                         ("vivim_seg_loss_fwd", SegLossParams), ("vivim_seg_loss_bwd", SegLossParams),
-                         ("vivim_seg_metrics", SegMetricsParams),
-                         ("vivim_upsample_bilinear2d_fwd", UpsampleParams),
-                         ("vivim_upsample_bilinear2d_bwd", UpsampleParams)):
+        for name, e in ENTRY_POINTS.items():
             fn = getattr(L, name)
-            fn.argtypes = [ctypes.POINTER(st), vp]
-            fn.restype = ctypes.c_int
-        L.vivim_selective_scan_fwd_lean.argtypes = [ctypes.POINTER(SsmFwdParams), vp, vp]
-        L.vivim_selective_scan_fwd_lean.restype = ctypes.c_int
-        L.vivim_scan_bwd_det_workspace_bytes.restype = ctypes.c_size_t
-        L.vivim_scan_bwd_det_workspace_bytes.argtypes = [ctypes.POINTER(SsmFwdParams)]
-        for name, st in (("vivim_scan_bwd_det_call_workspace_bytes", SsmBwdParams),
-                         ("vivim_causal_conv1d_bwd_det_workspace_bytes", ConvFwdParams),
-                         ("vivim_dwconv_wgrad_det_workspace_bytes", DwConvWgradParams)):
-            getattr(L, name).restype = ctypes.c_size_t
-            getattr(L, name).argtypes = [ctypes.POINTER(st)]
-        for name, st in (("vivim_selective_scan_bwd_det", SsmBwdParams), ("vivim_causal_conv1d_bwd_det", ConvBwdParams),
-                         ("vivim_dwconv_wgrad_det", DwConvWgradParams)):
-            getattr(L, name).argtypes = [ctypes.POINTER(st), vp, ctypes.c_size_t, vp]
-            getattr(L, name).restype = ctypes.c_int
-        L.vivim_layernorm_bwd_workspace_bytes.argtypes = [ctypes.POINTER(LayerNormParams)]
-        L.vivim_layernorm_bwd_workspace_bytes.restype = ctypes.c_size_t
-        L.vivim_add_layernorm_bwd_workspace_bytes.argtypes = [ctypes.POINTER(AddLayerNormParams)]
-        L.vivim_add_layernorm_bwd_workspace_bytes.restype = ctypes.c_size_t
-        L.vivim_seg_loss_workspace_bytes.argtypes = [ctypes.POINTER(SegLossParams)]
-        L.vivim_seg_loss_workspace_bytes.restype = ctypes.c_size_t
-        L.vivim_seg_metrics_workspace_bytes.argtypes = [ctypes.POINTER(SegMetricsParams)]
-        L.vivim_seg_metrics_workspace_bytes.restype = ctypes.c_size_t
+            fn.argtypes = ([ctypes.POINTER(e.struct)] if e.struct else []) + list(e.extra) + ([vp] if e.stream else [])
+            fn.restype = e.restype
         if L.vivim_abi_version() != 8:
             raise ImportError("libvivim_hip.so ABI version mismatch")
-        for which, st in enumerate((SsmFwdParams, SsmBwdParams, ConvFwdParams, ConvBwdParams, DwConvParams,
-                                    DwConvWgradParams, DirParams, ConvUpdateParams, StateUpdateParams, LayerNormParams,
-                                    WgradNtParams, AddLayerNormParams, SegLossParams, SegMetricsParams,
-                                    UpsampleParams)):
+        for which, st in enumerate(STRUCTS):
             if L.vivim_sizeof(which) != ctypes.sizeof(st):
                 raise ImportError(f"struct layout mismatch for {st.__name__}: "
                                   f"C {L.vivim_sizeof(which)} vs ctypes {ctypes.sizeof(st)}")
@@ -257,7 +262,10 @@ _ISIZE = {F32: 4, F16: 2, BF16: 2}
 
 def algorithmic_bytes(name, P):
     """Compulsory HBM traffic of one launch: every tensor of the op read or written once
-    (the checkpoint tensor x is an implementation choice and is excluded)."""
+    (the checkpoint tensor x is an implementation choice and is excluded).  A `*_det` entry point
+    moves the bytes of its default twin."""
+    name = name.removesuffix("_det")
+    f = P.f if isinstance(P, (SsmBwdParams, ConvBwdParams)) else P       # the forward half of a backward struct
     if name.startswith("vivim_add_layernorm"):
         n = P.batch * P.seqlen * P.channels
         if not P.weight:                                               # add-only: x, branch, x_new / dres, dbranch
@@ -276,7 +284,6 @@ def algorithmic_bytes(name, P):
         return (n * ((2 if name.endswith("bwd") else 1) * P.classes * _ISIZE[P.itype] + (8 if P.ttype == 0 else 1))
                 + 8 * P.batch * P.classes)
     if name.startswith("vivim_selective_scan"):
-        f = P.f if name.endswith("bwd") else P
         s = _ISIZE[f.itype]
         act = f.batch * f.dim * f.seqlen * s
         bc = (f.batch * f.n_groups * f.dstate * f.seqlen) if f.is_variable_B else f.dim * f.dstate
@@ -296,7 +303,13 @@ def algorithmic_bytes(name, P):
     if name.startswith("vivim_dwconv"):
         act = P.batch * P.depth * P.height * P.width * P.channels * _ISIZE[P.itype]
         return 2 * act + 4 * P.channels * (P.kd * 9 + 1)            # x and y (or x and dy) once + taps
-    f = P.f if name.endswith("bwd") else P
+    if name.startswith("vivim_layernorm"):                              # x, y + mean, rstd | x, dy, dx + mean, rstd
+        n = P.batch * P.seqlen * P.channels
+        if name.endswith("fwd"):
+            return n * (_ISIZE[P.itype] + _ISIZE[P.otype]) + 8 * P.batch * P.seqlen + 8 * P.channels
+        return n * (2 * _ISIZE[P.itype] + _ISIZE[P.otype]) + 8 * P.batch * P.seqlen + 12 * P.channels
+    if name.startswith("vivim_wgrad"):                                  # both operands, the fp32 products
+        return P.groups * ((P.m + P.n) * P.k * _ISIZE[P.itype] + 4 * P.m * P.n)
     s = _ISIZE[f.itype]
     act = f.batch * f.dim * f.seqlen * s
     if name.endswith("fwd"):
@@ -312,7 +325,7 @@ _PROFILED = ("vivim_selective_scan_fwd", "vivim_selective_scan_bwd", "vivim_caus
 
 def profile_begin(all_kernels=False):
     """Start recording one (name, algorithmic bytes, start event, end event) tuple per C-ABI call of the hot-path
-    kernels (every kernel with all_kernels=True); events are recorded on the stream the kernel is launched on
+    kernels (with all_kernels=True of every launching entry point, under its own name); events are recorded on the stream the kernel is launched on
     (torch's current stream) and come from a reusable pool, so the timed region pays two hipEventRecord per call."""
     global _profile
     _profile = ([], bool(all_kernels))
@@ -334,7 +347,6 @@ def profile_end():
 def _event():
     if _event_pool:
         return _event_pool.pop()
-    import torch
     return torch.cuda.Event(enable_timing=True)
 
 
@@ -346,7 +358,6 @@ _guards = []
 
 
 def _guarded_storage(nbytes, device):
-    import torch
     buf = torch.full((nbytes + 2 * _GUARD_BYTES,), 0xA5, dtype=torch.uint8, device=device)
     _guards.append(buf)
     return buf[_GUARD_BYTES:_GUARD_BYTES + nbytes]
@@ -354,7 +365,6 @@ def _guarded_storage(nbytes, device):
 
 def empty(shape, dtype, device):
     """torch.empty, or its canary-bracketed twin under VIVIM_GUARD=1."""
-    import torch
     if not GUARD:
         return torch.empty(shape, dtype=dtype, device=device)
     n = 1
@@ -366,7 +376,6 @@ def empty(shape, dtype, device):
 def zeros(n, device):
     """A zeroed fp32 accumulator of n elements (dA / dB / dC / dD / dbias, dweight / dbias of the convolutions: what the
     kernels ADD into), or its canary-bracketed twin under VIVIM_GUARD=1."""
-    import torch
     if not GUARD:
         return torch.zeros(n, dtype=torch.float32, device=device)
     return _guarded_storage(4 * n, device).view(torch.float32).zero_()
@@ -374,7 +383,6 @@ def zeros(n, device):
 
 def empty_like(t):
     """torch.empty_like (dense, same strides), or its canary-bracketed twin under VIVIM_GUARD=1."""
-    import torch
     if not GUARD:
         return torch.empty_like(t)
     ref = torch.empty_like(t)                               # for its strides
@@ -383,7 +391,6 @@ def empty_like(t):
 
 
 def check_guards(what):
-    import torch
     torch.cuda.synchronize()
     for buf in _guards:
         lo, hi = buf[:_GUARD_BYTES], buf[-_GUARD_BYTES:]
@@ -398,52 +405,53 @@ def check_guards(what):
 def deterministic():
     """True while torch.use_deterministic_algorithms is on (warn_only included): the backward entry points then take
     their deterministic variants."""
-    import torch
     return torch.are_deterministic_algorithms_enabled()
 
 
-def call_det(name, params, det_ws, det_ws_bytes, stream):
-    """Enqueue a deterministic-variant entry point (params, det workspace, its bytes, stream); RuntimeError on a
-    nonzero return."""
+def call(name, params, stream, *extra):
+    """Enqueue one entry point on `stream` (int hipStream_t): fn(&params, *extra, stream), `extra` being what the C
+    signature has between the two (ENTRY_POINTS).  RuntimeError on a nonzero return, like the TORCH_CHECKs of the
+    reference bindings."""
     L = lib()
-    rc = getattr(L, name)(ctypes.byref(params), vp(det_ws), ctypes.c_size_t(det_ws_bytes), vp(stream))
-    if rc != 0:
-        raise RuntimeError(L.vivim_last_error().decode())
-    if GUARD:
-        check_guards(name)
-
-
-def call_lean_fwd(params, last_state, stream):
-    """Enqueue vivim_selective_scan_fwd_lean (params, last_state pointer or None, stream); profiled and guarded like `call`."""
-    L = lib()
-    name = "vivim_selective_scan_fwd_lean"
-    if _profile is not None and _profile[1]:
-        e0, e1 = _event(), _event()
-        e0.record()
-        rc = L.vivim_selective_scan_fwd_lean(ctypes.byref(params), vp(last_state), vp(stream))
-        e1.record()
-        _profile[0].append((name, algorithmic_bytes(name, params), e0, e1))
-    else:
-        rc = L.vivim_selective_scan_fwd_lean(ctypes.byref(params), vp(last_state), vp(stream))
-    if rc != 0:
-        raise RuntimeError(L.vivim_last_error().decode())
-    if GUARD:
-        check_guards(name)
-
-
-def call(name, params, stream):
-    """Enqueue one entry point on `stream` (int hipStream_t); RuntimeError on a nonzero return,
-    like the TORCH_CHECKs of the reference bindings."""
-    L = lib()
+    fn = getattr(L, name)
     if _profile is not None and (_profile[1] or name in _PROFILED):
         e0, e1 = _event(), _event()
         e0.record()
-        rc = getattr(L, name)(ctypes.byref(params), vp(stream))
+        rc = fn(ctypes.byref(params), *extra, stream)
         e1.record()
         _profile[0].append((name, algorithmic_bytes(name, params), e0, e1))
     else:
-        rc = getattr(L, name)(ctypes.byref(params), vp(stream))
+        rc = fn(ctypes.byref(params), *extra, stream)
     if rc != 0:
         raise RuntimeError(L.vivim_last_error().decode())
     if GUARD:
         check_guards(name)
+
+
+def launch(name, params, device, *extra):
+    """`call` on torch's current stream of `device`.  The step is host-paced: the device context manager (~15 us) is
+    entered only when `device` is not already the current one."""
+    if device.index == torch.cuda.current_device():
+        call(name, params, torch.cuda.current_stream().cuda_stream, *extra)
+    else:
+        with torch.cuda.device(device):
+            call(name, params, torch.cuda.current_stream().cuda_stream, *extra)
+
+
+# ---- what every wrapper module needs around a launch
+ITYPE = {torch.float32: F32, torch.float16: F16, torch.bfloat16: BF16}
+
+
+def ptr(t):
+    return None if t is None else t.data_ptr()
+
+
+def check(cond, msg):
+    if not cond:
+        raise RuntimeError(msg)
+
+
+def workspace(query, params, device):
+    """-> (bytes the query `query` asks for `params`, a uint8 buffer of that size on `device` or None for 0 bytes)."""
+    n = getattr(lib(), query)(params)
+    return n, (empty((n,), torch.uint8, device) if n else None)

@@ -4,6 +4,7 @@
 #include <hip/hip_runtime.h>
 #include <stdarg.h>
 #include <stdio.h>
+#include <type_traits>
 #include "../../include/vivim_hip.h"
 #include "det.cuh"
 
@@ -68,6 +69,15 @@ static int after_launch(const char* what) {
 }
 
 static bool dtype_ok(int t) { return t == VIVIM_F32 || t == VIVIM_F16 || t == VIVIM_BF16; }
+static bool aligned(const void* q, uintptr_t bytes) { return reinterpret_cast<uintptr_t>(q) % bytes == 0; }
+static bool aligned16(const void* q) { return aligned(q, 16); }
+static hipStream_t as_stream(void* stream) { return static_cast<hipStream_t>(stream); }
+
+// the refusal of a missing, short or misaligned workspace: `fn` is the entry point, `query` the call that sizes it
+static int bad_workspace(const char* fn, const char* query, long long bytes, const void* at, int align, size_t need) {
+    return fail(VIVIM_ERR_INVALID, "%s: workspace of %lld bytes at %p: need a %d-byte aligned one of %s() = %zu", fn, bytes, at, align,
+                query, need);
+}
 
 // mode: the full forward, the backward (its `f` half), or the lean forward (no checkpoints; out_z alone when z is given)
 enum SsmCheck { kSsmFwd, kSsmBwd, kSsmFwdLean };
@@ -102,6 +112,23 @@ static int check_ssm_fwd(const vivim_ssm_fwd_params* p, SsmCheck mode) {
         return fail(VIVIM_ERR_UNSUPPORTED,
                     "selective_scan: mixed constant/variable B and C is not built (Vivim uses variable B and C)");
     if (!p->is_variable_B) VCHECK(p->n_groups == 1);
+    return VIVIM_OK;
+}
+
+// the checks on logits, target and classes that the segmentation loss (`name` "seg_loss") and metrics ("seg_metrics") share;
+// the loss's gamma is refused where it always was, between the class count and the grid bound
+template <class P> static int check_seg_inputs(const P* p, const char* name) {
+    VCHECK(p != nullptr);
+    VCHECK(dtype_ok(p->itype) && (p->ttype == 0 || p->ttype == 1));
+    VCHECK(p->batch > 0 && p->pixels > 0);
+    if (p->classes < 2 || p->classes > 8)
+        return fail(VIVIM_ERR_UNSUPPORTED, "%s: %d classes: the kernels are built for 2 to 8 classes", name, p->classes);
+    if constexpr (std::is_same<P, vivim_seg_loss_params>::value)
+        if (p->gamma != 2.0f)
+            return fail(VIVIM_ERR_UNSUPPORTED, "seg_loss: gamma = %g: the kernels are built for gamma = 2 only", (double)p->gamma);
+    VCHECK((int64_t)p->batch * 64 <= INT32_MAX);                  // one workgroup index per (image, block)
+    VCHECK(p->logits && aligned(p->logits, p->itype == VIVIM_F32 ? 4 : 2));
+    VCHECK(p->target && aligned(p->target, p->ttype == 0 ? 8 : 1));
     return VIVIM_OK;
 }
 
@@ -140,36 +167,25 @@ size_t vivim_scan_fwd_workspace_bytes(const vivim_ssm_fwd_params* f) {
     return f ? vivim::scan_fwd_workspace_bytes(*f) : 0;
 }
 size_t vivim_sizeof(int which) {
-    switch (which) {
-        case 0: return sizeof(vivim_ssm_fwd_params);
-        case 1: return sizeof(vivim_ssm_bwd_params);
-        case 2: return sizeof(vivim_conv_fwd_params);
-        case 3: return sizeof(vivim_conv_bwd_params);
-        case 4: return sizeof(vivim_dwconv_params);
-        case 5: return sizeof(vivim_dwconv_wgrad_params);
-        case 6: return sizeof(vivim_dir_params);
-        case 7: return sizeof(vivim_conv_update_params);
-        case 8: return sizeof(vivim_state_update_params);
-        case 9: return sizeof(vivim_layernorm_params);
-        case 10: return sizeof(vivim_wgrad_nt_params);
-        case 11: return sizeof(vivim_add_layernorm_params);
-        case 12: return sizeof(vivim_seg_loss_params);
-        case 13: return sizeof(vivim_seg_metrics_params);
-        case 14: return sizeof(vivim_upsample_params);
-    }
-    return 0;
+    static const size_t sizes[] = {
+        sizeof(vivim_ssm_fwd_params), sizeof(vivim_ssm_bwd_params), sizeof(vivim_conv_fwd_params), sizeof(vivim_conv_bwd_params),
+        sizeof(vivim_dwconv_params), sizeof(vivim_dwconv_wgrad_params), sizeof(vivim_dir_params), sizeof(vivim_conv_update_params),
+        sizeof(vivim_state_update_params), sizeof(vivim_layernorm_params), sizeof(vivim_wgrad_nt_params),
+        sizeof(vivim_add_layernorm_params), sizeof(vivim_seg_loss_params), sizeof(vivim_seg_metrics_params),
+        sizeof(vivim_upsample_params)};
+    return which >= 0 && which < (int)(sizeof(sizes) / sizeof(sizes[0])) ? sizes[which] : 0;
 }
 
 int vivim_selective_scan_fwd(const vivim_ssm_fwd_params* p, void* stream) {
     if (int rc = check_ssm_fwd(p, kSsmFwd)) return rc;
-    if (!vivim::ssm_fwd_dispatch(*p, static_cast<hipStream_t>(stream)))
+    if (!vivim::ssm_fwd_dispatch(*p, as_stream(stream)))
         return fail(VIVIM_ERR_UNSUPPORTED, "selective_scan_fwd not implemented for input type %d", p->itype);
     return after_launch("selective_scan_fwd");
 }
 
 int vivim_selective_scan_fwd_lean(const vivim_ssm_fwd_params* p, void* last_state, void* stream) {
     if (int rc = check_ssm_fwd(p, kSsmFwdLean)) return rc;
-    if (!vivim::ssm_fwd_lean_dispatch(*p, last_state, static_cast<hipStream_t>(stream)))
+    if (!vivim::ssm_fwd_lean_dispatch(*p, last_state, as_stream(stream)))
         return fail(VIVIM_ERR_UNSUPPORTED, "selective_scan_fwd_lean not implemented for input type %d", p->itype);
     return after_launch("selective_scan_fwd_lean");
 }
@@ -186,7 +202,7 @@ static int check_ssm_bwd(const vivim_ssm_bwd_params* p) {
 
 int vivim_selective_scan_bwd(const vivim_ssm_bwd_params* p, void* stream) {
     if (int rc = check_ssm_bwd(p)) return rc;
-    if (!vivim::ssm_bwd_dispatch(*p, static_cast<hipStream_t>(stream)))
+    if (!vivim::ssm_bwd_dispatch(*p, as_stream(stream)))
         return fail(VIVIM_ERR_UNSUPPORTED, "selective_scan_bwd not implemented for input type %d", p->f.itype);
     return after_launch("selective_scan_bwd");
 }
@@ -202,10 +218,10 @@ size_t vivim_scan_bwd_det_call_workspace_bytes(const vivim_ssm_bwd_params* p) {
 
 int vivim_selective_scan_bwd_det(const vivim_ssm_bwd_params* p, void* det_ws, size_t det_ws_bytes, void* stream) {
     if (int rc = check_ssm_bwd(p)) return rc;
-    switch (vivim::ssm_bwd_det_dispatch(*p, det_ws, det_ws_bytes, static_cast<hipStream_t>(stream))) {
+    switch (vivim::ssm_bwd_det_dispatch(*p, det_ws, det_ws_bytes, as_stream(stream))) {
         case 0: break;
-        case 2: return fail(VIVIM_ERR_INVALID, "selective_scan_bwd_det: workspace of %zu bytes at %p: need a 16-byte aligned one of "
-                            "vivim_scan_bwd_det_call_workspace_bytes() = %zu", det_ws_bytes, det_ws, vivim::scan_bwd_det_call_workspace_bytes(*p));
+        case 2: return bad_workspace("selective_scan_bwd_det", "vivim_scan_bwd_det_call_workspace_bytes", det_ws_bytes, det_ws, 16,
+                                     vivim::scan_bwd_det_call_workspace_bytes(*p));
         default: return fail(VIVIM_ERR_UNSUPPORTED, "selective_scan_bwd_det not implemented for input type %d", p->f.itype);
     }
     return after_launch("selective_scan_bwd_det");
@@ -232,8 +248,8 @@ int vivim_causal_conv1d_fwd(const vivim_conv_fwd_params* p, void* stream) {
     VCHECK(p->out != nullptr);
     const bool cl = conv_channel_last(p);
     if (cl) { VCHECK(p->out_c_stride == 1); } else { VCHECK(p->out_l_stride == 1); }
-    if (!(cl ? vivim::conv_cl_fwd_dispatch(*p, static_cast<hipStream_t>(stream))
-             : vivim::conv_fwd_dispatch(*p, static_cast<hipStream_t>(stream))))
+    if (!(cl ? vivim::conv_cl_fwd_dispatch(*p, as_stream(stream))
+             : vivim::conv_fwd_dispatch(*p, as_stream(stream))))
         return fail(VIVIM_ERR_UNSUPPORTED, "causal_conv1d_fwd not implemented for input type %d / weight type %d",
                     p->itype, p->wtype);
     return after_launch("causal_conv1d_fwd");
@@ -244,8 +260,8 @@ static int check_conv_bwd(const vivim_conv_bwd_params* p) {
     if (int rc = check_conv(&p->f)) return rc;
     VCHECK(p->dout && p->dx && p->dweight);
     const bool cl = conv_channel_last(&p->f);
-    if (cl) { VCHECK(p->dout_c_stride == 1 && p->dx_c_stride == 1); }
-    else    { VCHECK(p->dout_l_stride == 1 && p->dx_l_stride == 1); }
+    if (cl) { VCHECK(p->dout_c_stride == 1 && p->dx_c_stride == 1); }      // causal_conv1d.cpp:221, 237
+    else    { VCHECK(p->dout_l_stride == 1 && p->dx_l_stride == 1); }      // causal_conv1d.cpp:220, 236
     VCHECK((p->f.bias == nullptr) == (p->dbias == nullptr));
     return VIVIM_OK;
 }
@@ -259,11 +275,10 @@ size_t vivim_causal_conv1d_bwd_det_workspace_bytes(const vivim_conv_fwd_params* 
 int vivim_causal_conv1d_bwd_det(const vivim_conv_bwd_params* p, void* det_ws, size_t det_ws_bytes, void* stream) {
     if (int rc = check_conv_bwd(p)) return rc;
     const size_t need = vivim_causal_conv1d_bwd_det_workspace_bytes(&p->f);
-    if (det_ws == nullptr || det_ws_bytes < need || reinterpret_cast<uintptr_t>(det_ws) % 16 != 0)
-        return fail(VIVIM_ERR_INVALID, "causal_conv1d_bwd_det: workspace of %zu bytes at %p: need a 16-byte aligned one of "
-                    "vivim_causal_conv1d_bwd_det_workspace_bytes() = %zu", det_ws_bytes, det_ws, need);
+    if (det_ws == nullptr || det_ws_bytes < need || !aligned16(det_ws))
+        return bad_workspace("causal_conv1d_bwd_det", "vivim_causal_conv1d_bwd_det_workspace_bytes", det_ws_bytes, det_ws, 16, need);
     const bool cl = conv_channel_last(&p->f);
-    const hipStream_t s = static_cast<hipStream_t>(stream);
+    const hipStream_t s = as_stream(stream);
     vivim_conv_bwd_params d = *p;
     d.dweight = det_ws;
     d.dbias = nullptr;
@@ -279,15 +294,9 @@ int vivim_causal_conv1d_bwd_det(const vivim_conv_bwd_params* p, void* det_ws, si
 }
 
 int vivim_causal_conv1d_bwd(const vivim_conv_bwd_params* p, void* stream) {
-    VCHECK(p != nullptr);
-    if (int rc = check_conv(&p->f)) return rc;
-    VCHECK(p->dout && p->dx && p->dweight);
-    const bool cl = conv_channel_last(&p->f);
-    if (cl) { VCHECK(p->dout_c_stride == 1 && p->dx_c_stride == 1); }      // causal_conv1d.cpp:221, 237
-    else    { VCHECK(p->dout_l_stride == 1 && p->dx_l_stride == 1); }      // causal_conv1d.cpp:220, 236
-    VCHECK((p->f.bias == nullptr) == (p->dbias == nullptr));
-    if (!(cl ? vivim::conv_cl_bwd_dispatch(*p, static_cast<hipStream_t>(stream))
-             : vivim::conv_bwd_dispatch(*p, static_cast<hipStream_t>(stream))))
+    if (int rc = check_conv_bwd(p)) return rc;
+    if (!(conv_channel_last(&p->f) ? vivim::conv_cl_bwd_dispatch(*p, as_stream(stream))
+             : vivim::conv_bwd_dispatch(*p, as_stream(stream))))
         return fail(VIVIM_ERR_UNSUPPORTED, "causal_conv1d_bwd not implemented for input type %d / weight type %d",
                     p->f.itype, p->f.wtype);
     return after_launch("causal_conv1d_bwd");
@@ -308,12 +317,12 @@ int vivim_dwconv_fwd(const vivim_dwconv_params* p, void* stream) {
     const int64_t cv = p->itype == VIVIM_F32 ? 4 : 8;
     VCHECK(p->channels % cv == 0 && p->x_token_stride % cv == 0 && p->x_batch_stride % cv == 0 &&
            p->y_token_stride % cv == 0 && p->y_batch_stride % cv == 0);
-    VCHECK((reinterpret_cast<uintptr_t>(p->x) & 15) == 0 && (reinterpret_cast<uintptr_t>(p->y) & 15) == 0);
+    VCHECK(aligned16(p->x) && aligned16(p->y));
     VCHECK(p->act >= 0 && p->act <= 2 && (p->act == 0 || p->flip == 0));
     if (p->act == 2)
-        VCHECK(p->aux && (reinterpret_cast<uintptr_t>(p->aux) & 15) == 0 && p->aux_token_stride % cv == 0 &&
+        VCHECK(p->aux && aligned16(p->aux) && p->aux_token_stride % cv == 0 &&
                p->aux_batch_stride % cv == 0);
-    if (!vivim::dwconv_fwd_dispatch(*p, static_cast<hipStream_t>(stream)))
+    if (!vivim::dwconv_fwd_dispatch(*p, as_stream(stream)))
         return fail(VIVIM_ERR_UNSUPPORTED, "dwconv_fwd not implemented for input type %d", p->itype);
     return after_launch("dwconv_fwd");
 }
@@ -324,7 +333,7 @@ static int check_dw_wgrad(const vivim_dwconv_wgrad_params* p) {
     VCHECK(p->x && p->dy && p->dwt);
     VCHECK(p->channels % 2 == 0 && p->x_token_stride % 2 == 0 && p->x_batch_stride % 2 == 0 &&
            p->dy_token_stride % 2 == 0 && p->dy_batch_stride % 2 == 0);
-    VCHECK((reinterpret_cast<uintptr_t>(p->x) & 7) == 0 && (reinterpret_cast<uintptr_t>(p->dy) & 7) == 0);
+    VCHECK(aligned(p->x, 8) && aligned(p->dy, 8));
     return VIVIM_OK;
 }
 
@@ -336,24 +345,18 @@ size_t vivim_dwconv_wgrad_det_workspace_bytes(const vivim_dwconv_wgrad_params* p
 
 int vivim_dwconv_wgrad_det(const vivim_dwconv_wgrad_params* p, void* det_ws, size_t det_ws_bytes, void* stream) {
     if (int rc = check_dw_wgrad(p)) return rc;
-    switch (vivim::dwconv_wgrad_det_dispatch(*p, det_ws, det_ws_bytes, static_cast<hipStream_t>(stream))) {
+    switch (vivim::dwconv_wgrad_det_dispatch(*p, det_ws, det_ws_bytes, as_stream(stream))) {
         case 0: break;
-        case 2: return fail(VIVIM_ERR_INVALID, "dwconv_wgrad_det: workspace of %zu bytes at %p: need a 16-byte aligned one of "
-                            "vivim_dwconv_wgrad_det_workspace_bytes() = %zu", det_ws_bytes, det_ws,
-                            vivim::dwconv_wgrad_det_workspace_bytes(*p));
+        case 2: return bad_workspace("dwconv_wgrad_det", "vivim_dwconv_wgrad_det_workspace_bytes", det_ws_bytes, det_ws, 16,
+                                     vivim::dwconv_wgrad_det_workspace_bytes(*p));
         default: return fail(VIVIM_ERR_UNSUPPORTED, "dwconv_wgrad_det not implemented for input type %d", p->itype);
     }
     return after_launch("dwconv_wgrad_det");
 }
 
 int vivim_dwconv_wgrad(const vivim_dwconv_wgrad_params* p, void* stream) {
-    VCHECK(p != nullptr);
-    if (int rc = check_dw_dims(p->batch, p->depth, p->height, p->width, p->channels, p->kd, p->itype)) return rc;
-    VCHECK(p->x && p->dy && p->dwt);
-    VCHECK(p->channels % 2 == 0 && p->x_token_stride % 2 == 0 && p->x_batch_stride % 2 == 0 &&
-           p->dy_token_stride % 2 == 0 && p->dy_batch_stride % 2 == 0);
-    VCHECK((reinterpret_cast<uintptr_t>(p->x) & 7) == 0 && (reinterpret_cast<uintptr_t>(p->dy) & 7) == 0);
-    if (!vivim::dwconv_wgrad_dispatch(*p, static_cast<hipStream_t>(stream)))
+    if (int rc = check_dw_wgrad(p)) return rc;
+    if (!vivim::dwconv_wgrad_dispatch(*p, as_stream(stream)))
         return fail(VIVIM_ERR_UNSUPPORTED, "dwconv_wgrad not implemented for input type %d", p->itype);
     return after_launch("dwconv_wgrad");
 }
@@ -367,7 +370,7 @@ static int check_dir(const vivim_dir_params* p) {
     VCHECK(p->src && p->dst);
     const int64_t e = p->itype == VIVIM_F32 ? 4 : 8;            // 16-byte vectors on both sides
     VCHECK(p->seqlen % e == 0);
-    VCHECK((reinterpret_cast<uintptr_t>(p->src) & 15) == 0 && (reinterpret_cast<uintptr_t>(p->dst) & 15) == 0);
+    VCHECK(aligned16(p->src) && aligned16(p->dst));
     VCHECK(p->flat_batch_stride % e == 0 && p->flat_c_stride % e == 0 && p->stk_batch_stride % e == 0 &&
            p->stk_half_stride % e == 0 && p->stk_dir_stride % e == 0 && p->stk_c_stride % e == 0);
     return VIVIM_OK;
@@ -375,13 +378,13 @@ static int check_dir(const vivim_dir_params* p) {
 
 int vivim_dir_scatter(const vivim_dir_params* p, void* stream) {
     if (int rc = check_dir(p)) return rc;
-    if (!vivim::dir_dispatch<false>(*p, static_cast<hipStream_t>(stream))) return fail(VIVIM_ERR_UNSUPPORTED, "dir_scatter: bad itype");
+    if (!vivim::dir_dispatch<false>(*p, as_stream(stream))) return fail(VIVIM_ERR_UNSUPPORTED, "dir_scatter: bad itype");
     return after_launch("dir_scatter");
 }
 
 int vivim_dir_gather(const vivim_dir_params* p, void* stream) {
     if (int rc = check_dir(p)) return rc;
-    if (!vivim::dir_dispatch<true>(*p, static_cast<hipStream_t>(stream))) return fail(VIVIM_ERR_UNSUPPORTED, "dir_gather: bad itype");
+    if (!vivim::dir_dispatch<true>(*p, as_stream(stream))) return fail(VIVIM_ERR_UNSUPPORTED, "dir_gather: bad itype");
     return after_launch("dir_gather");
 }
 
@@ -392,7 +395,7 @@ int vivim_causal_conv1d_update(const vivim_conv_update_params* p, void* stream) 
     if (p->width < 2 || p->width > 4)
         return fail(VIVIM_ERR_UNSUPPORTED, "causal_conv1d only supports width between 2 and 4");   // causal_conv1d.cpp:295
     VCHECK(p->x && p->conv_state && p->weight && p->out);
-    vivim::conv_update_launch(*p, static_cast<hipStream_t>(stream));
+    vivim::conv_update_launch(*p, as_stream(stream));
     return after_launch("causal_conv1d_update");
 }
 
@@ -401,7 +404,7 @@ int vivim_selective_state_update(const vivim_state_update_params* p, void* strea
     VCHECK(dtype_ok(p->itype) && (p->stype == VIVIM_F32 || p->stype == p->itype));
     VCHECK(p->batch > 0 && p->dim > 0 && p->dstate > 0 && p->batch <= 65535);
     VCHECK(p->state && p->x && p->dt && p->A && p->B && p->C && p->out);
-    vivim::state_update_launch(*p, static_cast<hipStream_t>(stream));
+    vivim::state_update_launch(*p, as_stream(stream));
     return after_launch("selective_state_update");
 }
 
@@ -413,14 +416,14 @@ static int check_layernorm(const vivim_layernorm_params* p) {
         return fail(VIVIM_ERR_UNSUPPORTED, "layernorm_cm: more than 512 channels do not fit the backward's two LDS tiles");
     const int64_t e = p->itype == VIVIM_F32 ? 4 : 8;             // 16-byte vectors along the tokens of x / dx
     VCHECK(p->seqlen % e == 0 && p->x_batch_stride % e == 0 && p->x_c_stride % e == 0);
-    VCHECK(p->x && (reinterpret_cast<uintptr_t>(p->x) & 15) == 0 && p->mean && p->rstd);
+    VCHECK(p->x && aligned16(p->x) && p->mean && p->rstd);
     return VIVIM_OK;
 }
 
 int vivim_layernorm_cm_fwd(const vivim_layernorm_params* p, void* stream) {
     if (int rc = check_layernorm(p)) return rc;
     VCHECK(p->y != nullptr);
-    if (!vivim::layernorm_dispatch(*p, false, static_cast<hipStream_t>(stream)))
+    if (!vivim::layernorm_dispatch(*p, false, as_stream(stream)))
         return fail(VIVIM_ERR_UNSUPPORTED, "layernorm_cm_fwd not implemented for input type %d / output type %d", p->itype, p->otype);
     return after_launch("layernorm_cm_fwd");
 }
@@ -431,12 +434,12 @@ size_t vivim_layernorm_bwd_workspace_bytes(const vivim_layernorm_params* p) {
 
 int vivim_layernorm_cm_bwd(const vivim_layernorm_params* p, void* stream) {
     if (int rc = check_layernorm(p)) return rc;
-    VCHECK(p->dy && p->dx && (reinterpret_cast<uintptr_t>(p->dx) & 15) == 0);
+    VCHECK(p->dy && p->dx && aligned16(p->dx));
     const int64_t e = p->itype == VIVIM_F32 ? 4 : 8;
     VCHECK(p->dx_batch_stride % e == 0 && p->dx_c_stride % e == 0);
     if ((p->dweight || p->dbias) && !p->workspace)
         return fail(VIVIM_ERR_INVALID, "layernorm_cm_bwd: dweight / dbias need the workspace (vivim_layernorm_bwd_workspace_bytes)");
-    if (!vivim::layernorm_dispatch(*p, true, static_cast<hipStream_t>(stream)))
+    if (!vivim::layernorm_dispatch(*p, true, as_stream(stream)))
         return fail(VIVIM_ERR_UNSUPPORTED, "layernorm_cm_bwd not implemented for input type %d / output type %d", p->itype, p->otype);
     return after_launch("layernorm_cm_bwd");
 }
@@ -449,14 +452,12 @@ int vivim_wgrad_nt(const vivim_wgrad_nt_params* p, void* stream) {
         return fail(VIVIM_ERR_UNSUPPORTED, "wgrad_nt takes f16 or bf16 operands (type %d given): f32 products stay on the library GEMM", p->itype);
     VCHECK(p->k % 8 == 0 && p->a_row_stride % 8 == 0 && p->b_row_stride % 8 == 0 && p->a_group_stride % 8 == 0 &&
            p->b_group_stride % 8 == 0);
-    VCHECK((reinterpret_cast<uintptr_t>(p->a) & 15) == 0 && (reinterpret_cast<uintptr_t>(p->b) & 15) == 0);
+    VCHECK(aligned16(p->a) && aligned16(p->b));
     VCHECK((int64_t)((p->m + 63) / 64) * ((p->n + 15) / 16) <= 65535);
-    if (!vivim::wgrad_nt_dispatch(*p, static_cast<hipStream_t>(stream)))
+    if (!vivim::wgrad_nt_dispatch(*p, as_stream(stream)))
         return fail(VIVIM_ERR_UNSUPPORTED, "wgrad_nt not implemented for type %d", p->itype);
     return after_launch("wgrad_nt");
 }
-
-static bool aligned16(const void* q) { return (reinterpret_cast<uintptr_t>(q) & 15) == 0; }
 
 // what the forward and the backward of the residual-add LayerNorm share; `e` <- elements per 16-byte vector of x / x_new / dres / dx
 static int check_add_layernorm(const vivim_add_layernorm_params* p, int64_t* e) {
@@ -481,7 +482,7 @@ int vivim_add_layernorm_cm_fwd(const vivim_add_layernorm_params* p, void* stream
     VCHECK(p->x && p->branch && p->x_new && aligned16(p->x) && aligned16(p->x_new));
     VCHECK(p->x_batch_stride % e == 0 && p->x_c_stride % e == 0 && p->x_new_batch_stride % e == 0 && p->x_new_c_stride % e == 0);
     if (p->weight) VCHECK(p->y && p->mean && p->rstd);
-    if (!vivim::add_layernorm_dispatch(*p, false, static_cast<hipStream_t>(stream)))
+    if (!vivim::add_layernorm_dispatch(*p, false, as_stream(stream)))
         return fail(VIVIM_ERR_UNSUPPORTED, "add_layernorm_cm_fwd not implemented for x type %d / branch type %d / output type %d", p->itype,
                     p->btype, p->otype);
     return after_launch("add_layernorm_cm_fwd");
@@ -505,7 +506,7 @@ int vivim_add_layernorm_cm_bwd(const vivim_add_layernorm_params* p, void* stream
     } else {
         VCHECK(p->dres && p->dbranch);                 // add-only: dbranch = scale * dres, dx is dres itself
     }
-    if (!vivim::add_layernorm_dispatch(*p, true, static_cast<hipStream_t>(stream)))
+    if (!vivim::add_layernorm_dispatch(*p, true, as_stream(stream)))
         return fail(VIVIM_ERR_UNSUPPORTED, "add_layernorm_cm_bwd not implemented for x type %d / branch type %d / output type %d", p->itype,
                     p->btype, p->otype);
     return after_launch("add_layernorm_cm_bwd");
@@ -513,18 +514,8 @@ int vivim_add_layernorm_cm_bwd(const vivim_add_layernorm_params* p, void* stream
 
 // what the forward and the backward of the segmentation loss share
 static int check_seg_loss(const vivim_seg_loss_params* p) {
-    VCHECK(p != nullptr);
-    VCHECK(dtype_ok(p->itype) && (p->ttype == 0 || p->ttype == 1));
-    VCHECK(p->batch > 0 && p->pixels > 0);
-    if (p->classes < 2 || p->classes > 8)
-        return fail(VIVIM_ERR_UNSUPPORTED, "seg_loss: %d classes: the kernels are built for 2 to 8 classes", p->classes);
-    if (p->gamma != 2.0f)
-        return fail(VIVIM_ERR_UNSUPPORTED, "seg_loss: gamma = %g: the kernels are built for gamma = 2 only", (double)p->gamma);
-    VCHECK((int64_t)p->batch * 64 <= INT32_MAX);                  // one workgroup index per (image, block)
-    const uintptr_t ib = p->itype == VIVIM_F32 ? 4 : 2, tbytes = p->ttype == 0 ? 8 : 1;
-    VCHECK(p->logits && reinterpret_cast<uintptr_t>(p->logits) % ib == 0);
-    VCHECK(p->target && reinterpret_cast<uintptr_t>(p->target) % tbytes == 0);
-    VCHECK(p->alpha && reinterpret_cast<uintptr_t>(p->alpha) % 4 == 0);
+    if (int rc = check_seg_inputs(p, "seg_loss")) return rc;
+    VCHECK(p->alpha && aligned(p->alpha, 4));
     return VIVIM_OK;
 }
 
@@ -534,14 +525,12 @@ size_t vivim_seg_loss_workspace_bytes(const vivim_seg_loss_params* p) {
 
 int vivim_seg_loss_fwd(const vivim_seg_loss_params* p, void* stream) {
     if (int rc = check_seg_loss(p)) return rc;
-    VCHECK(p->loss && reinterpret_cast<uintptr_t>(p->loss) % 4 == 0);
-    VCHECK(reinterpret_cast<uintptr_t>(p->coef) % 4 == 0);          // NULL: not wanted
+    VCHECK(p->loss && aligned(p->loss, 4));
+    VCHECK(aligned(p->coef, 4));                                    // NULL: not wanted
     const size_t need = vivim::seg_loss_workspace_bytes(*p);
-    if (p->workspace == nullptr || reinterpret_cast<uintptr_t>(p->workspace) % 4 != 0 || p->workspace_bytes < 0 ||
-        (size_t)p->workspace_bytes < need)
-        return fail(VIVIM_ERR_INVALID, "seg_loss_fwd: workspace of %lld bytes at %p: need a 4-byte aligned one of "
-                    "vivim_seg_loss_workspace_bytes() = %zu", (long long)p->workspace_bytes, p->workspace, need);
-    if (!vivim::seg_loss_dispatch(*p, false, static_cast<hipStream_t>(stream)))
+    if (p->workspace == nullptr || !aligned(p->workspace, 4) || p->workspace_bytes < 0 || (size_t)p->workspace_bytes < need)
+        return bad_workspace("seg_loss_fwd", "vivim_seg_loss_workspace_bytes", p->workspace_bytes, p->workspace, 4, need);
+    if (!vivim::seg_loss_dispatch(*p, false, as_stream(stream)))
         return fail(VIVIM_ERR_UNSUPPORTED, "seg_loss_fwd not implemented for input type %d / %d classes", p->itype, p->classes);
     return after_launch("seg_loss_fwd");
 }
@@ -549,10 +538,10 @@ int vivim_seg_loss_fwd(const vivim_seg_loss_params* p, void* stream) {
 int vivim_seg_loss_bwd(const vivim_seg_loss_params* p, void* stream) {
     if (int rc = check_seg_loss(p)) return rc;
     const uintptr_t ib = p->itype == VIVIM_F32 ? 4 : 2;
-    VCHECK(p->coef && reinterpret_cast<uintptr_t>(p->coef) % 4 == 0);
-    VCHECK(p->grad_out && reinterpret_cast<uintptr_t>(p->grad_out) % 4 == 0);
-    VCHECK(p->dlogits && reinterpret_cast<uintptr_t>(p->dlogits) % ib == 0);
-    if (!vivim::seg_loss_dispatch(*p, true, static_cast<hipStream_t>(stream)))
+    VCHECK(p->coef && aligned(p->coef, 4));
+    VCHECK(p->grad_out && aligned(p->grad_out, 4));
+    VCHECK(p->dlogits && aligned(p->dlogits, ib));
+    if (!vivim::seg_loss_dispatch(*p, true, as_stream(stream)))
         return fail(VIVIM_ERR_UNSUPPORTED, "seg_loss_bwd not implemented for input type %d / %d classes", p->itype, p->classes);
     return after_launch("seg_loss_bwd");
 }
@@ -562,23 +551,13 @@ size_t vivim_seg_metrics_workspace_bytes(const vivim_seg_metrics_params* p) {
 }
 
 int vivim_seg_metrics(const vivim_seg_metrics_params* p, void* stream) {
-    VCHECK(p != nullptr);
-    VCHECK(dtype_ok(p->itype) && (p->ttype == 0 || p->ttype == 1));
-    VCHECK(p->batch > 0 && p->pixels > 0);
-    if (p->classes < 2 || p->classes > 8)
-        return fail(VIVIM_ERR_UNSUPPORTED, "seg_metrics: %d classes: the kernels are built for 2 to 8 classes", p->classes);
-    VCHECK((int64_t)p->batch * 64 <= INT32_MAX);                  // one workgroup index per (image, block)
-    const uintptr_t ib = p->itype == VIVIM_F32 ? 4 : 2, tbytes = p->ttype == 0 ? 8 : 1;
-    VCHECK(p->logits && reinterpret_cast<uintptr_t>(p->logits) % ib == 0);
-    VCHECK(p->target && reinterpret_cast<uintptr_t>(p->target) % tbytes == 0);
-    VCHECK(p->counts && reinterpret_cast<uintptr_t>(p->counts) % 4 == 0);
-    VCHECK(reinterpret_cast<uintptr_t>(p->state) % 8 == 0);         // NULL: not wanted (pred: any address)
+    if (int rc = check_seg_inputs(p, "seg_metrics")) return rc;
+    VCHECK(p->counts && aligned(p->counts, 4));
+    VCHECK(aligned(p->state, 8));         // NULL: not wanted (pred: any address)
     const size_t need = vivim::seg_metrics_workspace_bytes(*p);
-    if (p->workspace == nullptr || reinterpret_cast<uintptr_t>(p->workspace) % 4 != 0 || p->workspace_bytes < 0 ||
-        (size_t)p->workspace_bytes < need)
-        return fail(VIVIM_ERR_INVALID, "seg_metrics: workspace of %lld bytes at %p: need a 4-byte aligned one of "
-                    "vivim_seg_metrics_workspace_bytes() = %zu", (long long)p->workspace_bytes, p->workspace, need);
-    if (!vivim::seg_metrics_dispatch(*p, static_cast<hipStream_t>(stream)))
+    if (p->workspace == nullptr || !aligned(p->workspace, 4) || p->workspace_bytes < 0 || (size_t)p->workspace_bytes < need)
+        return bad_workspace("seg_metrics", "vivim_seg_metrics_workspace_bytes", p->workspace_bytes, p->workspace, 4, need);
+    if (!vivim::seg_metrics_dispatch(*p, as_stream(stream)))
         return fail(VIVIM_ERR_UNSUPPORTED, "seg_metrics not implemented for input type %d / %d classes", p->itype, p->classes);
     return after_launch("seg_metrics");
 }
@@ -594,8 +573,8 @@ static int check_upsample(const vivim_upsample_params* p, bool bwd) {
     const uintptr_t ib = p->itype == VIVIM_F32 ? 4 : 2;
     const void* src = bwd ? p->dy : p->x;
     const void* dst = bwd ? p->dx : p->y;
-    VCHECK(src != nullptr && reinterpret_cast<uintptr_t>(src) % ib == 0);
-    VCHECK(dst != nullptr && reinterpret_cast<uintptr_t>(dst) % ib == 0);
+    VCHECK(src != nullptr && aligned(src, ib));
+    VCHECK(dst != nullptr && aligned(dst, ib));
     // the kernels index inside an image, and build their windows and their grid, with 32-bit integers
     VCHECK((int64_t)p->channels * p->in_h * p->in_w <= INT32_MAX && (int64_t)p->channels * p->out_h * p->out_w <= INT32_MAX);
     VCHECK((2 * (int64_t)p->in_h + 3) * p->out_h <= INT32_MAX && (2 * (int64_t)p->in_w + 3) * p->out_w <= INT32_MAX);
@@ -606,14 +585,14 @@ static int check_upsample(const vivim_upsample_params* p, bool bwd) {
 
 int vivim_upsample_bilinear2d_fwd(const vivim_upsample_params* p, void* stream) {
     if (int rc = check_upsample(p, false)) return rc;
-    if (!vivim::upsample_dispatch(*p, false, static_cast<hipStream_t>(stream)))
+    if (!vivim::upsample_dispatch(*p, false, as_stream(stream)))
         return fail(VIVIM_ERR_UNSUPPORTED, "upsample_bilinear2d_fwd not implemented for type %d", p->itype);
     return after_launch("upsample_bilinear2d_fwd");
 }
 
 int vivim_upsample_bilinear2d_bwd(const vivim_upsample_params* p, void* stream) {
     if (int rc = check_upsample(p, true)) return rc;
-    if (!vivim::upsample_dispatch(*p, true, static_cast<hipStream_t>(stream)))
+    if (!vivim::upsample_dispatch(*p, true, as_stream(stream)))
         return fail(VIVIM_ERR_UNSUPPORTED, "upsample_bilinear2d_bwd not implemented for type %d", p->itype);
     return after_launch("upsample_bilinear2d_bwd");
 }

@@ -9,14 +9,13 @@ Each reads its input once; each is the other's gradient (up to the scale)."""
 import torch
 
 from . import _lib
-
-_ITYPE = {torch.float32: _lib.F32, torch.float16: _lib.F16, torch.bfloat16: _lib.BF16}
+from ._lib import ITYPE
 
 
 def _params(flat, stacked, nframes, csplit, scale, src, dst):
     B, C, L = flat.shape
     P = _lib.DirParams()
-    P.batch, P.channels, P.seqlen, P.nframes, P.csplit, P.itype, P.scale = B, C, L, nframes, csplit, _ITYPE[flat.dtype], scale
+    P.batch, P.channels, P.seqlen, P.nframes, P.csplit, P.itype, P.scale = B, C, L, nframes, csplit, ITYPE[flat.dtype], scale
     P.flat_batch_stride, P.flat_c_stride = flat.stride(0), flat.stride(1)
     P.stk_batch_stride, P.stk_half_stride, P.stk_dir_stride, P.stk_c_stride = (stacked.stride(0), stacked.stride(1),
                                                                                stacked.stride(2), stacked.stride(3))
@@ -33,9 +32,7 @@ def _scatter(flat, nframes, csplit, scale):
         flat = flat.contiguous()
     B, C, L = flat.shape
     stacked = _lib.empty((C // csplit, 3, csplit, B, L), flat.dtype, flat.device).permute(3, 0, 1, 2, 4)
-    with torch.cuda.device(flat.device):
-        _lib.call("vivim_dir_scatter", _params(flat, stacked, nframes, csplit, scale, flat, stacked),
-                  torch.cuda.current_stream().cuda_stream)
+    _lib.launch("vivim_dir_scatter", _params(flat, stacked, nframes, csplit, scale, flat, stacked), flat.device)
     return stacked
 
 
@@ -45,9 +42,7 @@ def _gather(stacked, nframes, scale):
         stacked = stacked.contiguous()
     B, H, _, csplit, L = stacked.shape
     flat = _lib.empty((B, H * csplit, L), stacked.dtype, stacked.device)
-    with torch.cuda.device(stacked.device):
-        _lib.call("vivim_dir_gather", _params(flat, stacked, nframes, csplit, scale, stacked, flat),
-                  torch.cuda.current_stream().cuda_stream)
+    _lib.launch("vivim_dir_gather", _params(flat, stacked, nframes, csplit, scale, stacked, flat), stacked.device)
     return flat
 
 

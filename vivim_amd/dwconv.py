@@ -2,19 +2,17 @@
 MambaLayer's Mlp (`DWConv`, modeling/vivim.py:57-68 -- nn.Conv3d(dim, dim, 3, 1, 1, groups=dim) applied to
 x.transpose(1, 2).view(B, C, nf, H, W)) without the transposes, on the gfx950 kernels of csrc/dwconv.hip.
 SURVEY.md section 8f row 4.  Same parameters as the nn.Conv3d / nn.Conv2d it replaces (weight (C,1,[kd,]3,3))."""
-import ctypes
 import os
 
 import torch
 
 from . import _lib
-
-_DT = {torch.float32: _lib.F32, torch.float16: _lib.F16, torch.bfloat16: _lib.BF16}
+from ._lib import ITYPE, ptr
 
 
 def supported(x, weight):
     """True when the kernels apply: CUDA tensor, channels contiguous, 3x3(x3) taps, aligned channel count."""
-    if os.environ.get("VIVIM_NO_DWCONV") or not (x.is_cuda and x.dim() == 3 and x.dtype in _DT and x.stride(2) == 1):
+    if os.environ.get("VIVIM_NO_DWCONV") or not (x.is_cuda and x.dim() == 3 and x.dtype in ITYPE and x.stride(2) == 1):
         return False
     cv = 16 // x.element_size()
     ks = tuple(weight.shape[2:])
@@ -42,16 +40,15 @@ def _run_fwd(x, wt, bias, dims, flip, act=0, aux=None):
     y = _lib.empty((B, L, C), x.dtype, x.device)
     P = _lib.DwConvParams()
     P.batch, P.depth, P.height, P.width, P.channels = B, D, H, W, C
-    P.kd, P.itype, P.flip = wt.shape[0] // 9, _DT[x.dtype], int(flip)
+    P.kd, P.itype, P.flip = wt.shape[0] // 9, ITYPE[x.dtype], int(flip)
     P.x_batch_stride, P.x_token_stride = x.stride(0), x.stride(1)
     P.y_batch_stride, P.y_token_stride = y.stride(0), y.stride(1)
     P.x, P.wt, P.y = x.data_ptr(), wt.data_ptr(), y.data_ptr()
-    P.bias = None if bias is None else bias.data_ptr()
+    P.bias = ptr(bias)
     P.act = act
     if aux is not None:
         P.aux, P.aux_batch_stride, P.aux_token_stride = aux.data_ptr(), aux.stride(0), aux.stride(1)
-    with torch.cuda.device(x.device):
-        _lib.call("vivim_dwconv_fwd", P, torch.cuda.current_stream().cuda_stream)
+    _lib.launch("vivim_dwconv_fwd", P, x.device)
     return y
 
 
@@ -62,18 +59,16 @@ def _run_wgrad(x, dy, wt, dims, has_bias):
     acc = _lib.zeros(wt.shape[0] * C + C, x.device)
     P = _lib.DwConvWgradParams()
     P.batch, P.depth, P.height, P.width, P.channels = B, D, H, W, C
-    P.kd, P.itype = wt.shape[0] // 9, _DT[x.dtype]
+    P.kd, P.itype = wt.shape[0] // 9, ITYPE[x.dtype]
     P.x_batch_stride, P.x_token_stride = x.stride(0), x.stride(1)
     P.dy_batch_stride, P.dy_token_stride = dy.stride(0), dy.stride(1)
     P.x, P.dy, P.dwt = x.data_ptr(), dy.data_ptr(), acc.data_ptr()
     P.dbias = acc.data_ptr() + 4 * wt.shape[0] * C if has_bias else None
-    with torch.cuda.device(x.device):
-        if _lib.deterministic():                      # fixed-order slot reduction of dwt / dbias, no float atomics
-            nbytes = _lib.lib().vivim_dwconv_wgrad_det_workspace_bytes(ctypes.byref(P))
-            ws = _lib.empty((nbytes,), torch.uint8, x.device)
-            _lib.call_det("vivim_dwconv_wgrad_det", P, ws.data_ptr(), nbytes, torch.cuda.current_stream().cuda_stream)
-        else:
-            _lib.call("vivim_dwconv_wgrad", P, torch.cuda.current_stream().cuda_stream)
+    if _lib.deterministic():                          # fixed-order slot reduction of dwt / dbias, no float atomics
+        nbytes, ws = _lib.workspace("vivim_dwconv_wgrad_det_workspace_bytes", P, x.device)
+        _lib.launch("vivim_dwconv_wgrad_det", P, x.device, ptr(ws), nbytes)
+    else:
+        _lib.launch("vivim_dwconv_wgrad", P, x.device)
     return acc
 
 

@@ -16,13 +16,10 @@ The residual add in front of the norm, fused with it (csrc/add_layernorm.hip; vi
                                             x_new = x + scale[b] * branch in x's dtype and layout, y = layer_norm(x_new)
     add_cm(x, branch, scale=None) -> x_new  the add alone
 `add_norm_supported(x, branch, weight)` says whether they apply; the caller keeps its composition of torch ops otherwise."""
-import ctypes
-
 import torch
 
 from . import _lib
-
-_ITYPE = {torch.float32: _lib.F32, torch.float16: _lib.F16, torch.bfloat16: _lib.BF16}
+from ._lib import ITYPE, ptr
 
 
 def supported(x, weight):
@@ -30,7 +27,7 @@ def supported(x, weight):
     # groups into dweight / dbias with float atomics
     if _lib.deterministic():
         return False
-    if not (x.is_cuda and x.dim() == 3 and x.dtype in _ITYPE and weight is not None and weight.dtype == torch.float32):
+    if not (x.is_cuda and x.dim() == 3 and x.dtype in ITYPE and weight is not None and weight.dtype == torch.float32):
         return False
     B, L, C = x.shape
     e = 16 // x.element_size()
@@ -49,19 +46,10 @@ def worthwhile(x):
 def _params(x, out_dtype, eps):
     B, L, C = x.shape
     P = _lib.LayerNormParams()
-    P.batch, P.seqlen, P.channels, P.itype, P.otype, P.eps = B, L, C, _ITYPE[x.dtype], _ITYPE[out_dtype], eps
+    P.batch, P.seqlen, P.channels, P.itype, P.otype, P.eps = B, L, C, ITYPE[x.dtype], ITYPE[out_dtype], eps
     P.x_batch_stride, P.x_c_stride = x.stride(0), x.stride(2)
     P.x = x.data_ptr()
     return P
-
-
-def _launch(name, P, device):
-    # the step is host-paced: no device context manager when the tensor's device is already the current one (~15 us each)
-    if device.index == torch.cuda.current_device():
-        _lib.call(name, P, torch.cuda.current_stream().cuda_stream)
-    else:
-        with torch.cuda.device(device):
-            _lib.call(name, P, torch.cuda.current_stream().cuda_stream)
 
 
 class _LayerNormCM(torch.autograd.Function):
@@ -72,10 +60,10 @@ class _LayerNormCM(torch.autograd.Function):
         stats = _lib.empty((2, B, L), torch.float32, x.device)              # mean, rstd
         P = _params(x, out_dtype, eps)
         P.y_batch_stride, P.y_token_stride = L * C, C
-        P.weight, P.bias = weight.data_ptr(), (bias.data_ptr() if bias is not None else None)
+        P.weight, P.bias = weight.data_ptr(), ptr(bias)
         P.y, P.mean = y.data_ptr(), stats.data_ptr()
         P.rstd = P.mean + 4 * B * L
-        _launch("vivim_layernorm_cm_fwd", P, x.device)
+        _lib.launch("vivim_layernorm_cm_fwd", P, x.device)
         ctx.save_for_backward(x, weight, stats)
         ctx.eps, ctx.has_bias, ctx.out_dtype = eps, bias is not None, out_dtype
         return y
@@ -98,9 +86,9 @@ class _LayerNormCM(torch.autograd.Function):
         P.rstd = P.mean + 4 * B * L
         P.dy, P.dx, P.dweight = dy.data_ptr(), dx.data_ptr(), dwb.data_ptr()
         P.dbias = P.dweight + 4 * C if ctx.has_bias else None
-        ws = _lib.empty((_lib.lib().vivim_layernorm_bwd_workspace_bytes(ctypes.byref(P)) // 4,), torch.float32, x.device)
-        P.workspace = ws.data_ptr()                                          # per-tile dweight / dbias partial sums
-        _launch("vivim_layernorm_cm_bwd", P, x.device)
+        ws = _lib.workspace("vivim_layernorm_bwd_workspace_bytes", P, x.device)[1]
+        P.workspace = ptr(ws)                                                # per-tile dweight / dbias partial sums
+        _lib.launch("vivim_layernorm_cm_bwd", P, x.device)
         return dx, dwb[:C], (dwb[C:] if ctx.has_bias else None), None, None
 
 
@@ -121,7 +109,7 @@ def add_norm_supported(x, branch, weight=None):
     torch.use_deterministic_algorithms, as `supported`: the reduce kernel adds into dweight / dbias with float atomics."""
     if _lib.deterministic():
         return False
-    if not (x.is_cuda and x.dim() == 3 and x.dtype in _ITYPE and branch.device == x.device and branch.shape == x.shape):
+    if not (x.is_cuda and x.dim() == 3 and x.dtype in ITYPE and branch.device == x.device and branch.shape == x.shape):
         return False
     if weight is not None and weight.dtype != torch.float32:
         return False
@@ -134,8 +122,8 @@ def add_norm_supported(x, branch, weight=None):
 def _add_params(x, branch, scale):
     B, L, C = x.shape
     P = _lib.AddLayerNormParams()
-    P.batch, P.seqlen, P.channels, P.itype, P.btype, P.otype = B, L, C, _ITYPE[x.dtype], _ITYPE[branch.dtype], _ITYPE[x.dtype]
-    P.scale = scale.data_ptr() if scale is not None else None
+    P.batch, P.seqlen, P.channels, P.itype, P.btype, P.otype = B, L, C, ITYPE[x.dtype], ITYPE[branch.dtype], ITYPE[x.dtype]
+    P.scale = ptr(scale)
     return P
 
 
@@ -171,15 +159,15 @@ class _AddLayerNormCM(torch.autograd.Function):
     def forward(ctx, x, branch, weight, bias, scale, eps, out_dtype):
         B, L, C = x.shape
         P = _add_params(x, branch, scale)
-        P.otype, P.eps = _ITYPE[out_dtype], eps
+        P.otype, P.eps = ITYPE[out_dtype], eps
         x_new = _add_forward(x, branch, scale, P)
         y = _lib.empty((B, L, C), out_dtype, x.device)
         stats = _lib.empty((2, B, L), torch.float32, x.device)              # mean, rstd
         P.y_batch_stride, P.y_token_stride = L * C, C
-        P.weight, P.bias = weight.data_ptr(), (bias.data_ptr() if bias is not None else None)
+        P.weight, P.bias = weight.data_ptr(), ptr(bias)
         P.y, P.mean = y.data_ptr(), stats.data_ptr()
         P.rstd = P.mean + 4 * B * L
-        _launch("vivim_add_layernorm_cm_fwd", P, x.device)
+        _lib.launch("vivim_add_layernorm_cm_fwd", P, x.device)
         ctx.save_for_backward(x_new, weight, stats, scale)
         ctx.eps, ctx.has_bias, ctx.out_dtype, ctx.branch_dtype = eps, bias is not None, out_dtype, branch.dtype
         ctx.set_materialize_grads(False)                                    # an unused output's gradient stays None: the kernel skips it
@@ -193,8 +181,8 @@ class _AddLayerNormCM(torch.autograd.Function):
         B, L, C = x_new.shape
         P = _lib.AddLayerNormParams()
         P.batch, P.seqlen, P.channels, P.eps = B, L, C, ctx.eps
-        P.itype, P.btype, P.otype = _ITYPE[x_new.dtype], _ITYPE[ctx.branch_dtype], _ITYPE[ctx.out_dtype]
-        P.scale = scale.data_ptr() if scale is not None else None
+        P.itype, P.btype, P.otype = ITYPE[x_new.dtype], ITYPE[ctx.branch_dtype], ITYPE[ctx.out_dtype]
+        P.scale = ptr(scale)
         P.x_new_batch_stride, P.x_new_c_stride = x_new.stride(0), x_new.stride(2)
         P.x_new, P.weight, P.mean = x_new.data_ptr(), weight.data_ptr(), stats.data_ptr()
         P.rstd = P.mean + 4 * B * L
@@ -208,8 +196,8 @@ class _AddLayerNormCM(torch.autograd.Function):
             dwb = _lib.zeros(2 * C, x_new.device)                            # dweight, dbias: one zero fill
             P.dweight = dwb.data_ptr()
             P.dbias = P.dweight + 4 * C if ctx.has_bias else None
-            ws = _lib.empty((_lib.lib().vivim_add_layernorm_bwd_workspace_bytes(ctypes.byref(P)) // 4,), torch.float32, x_new.device)
-            P.workspace = ws.data_ptr()                                      # per-tile dweight / dbias partial sums
+            ws = _lib.workspace("vivim_add_layernorm_bwd_workspace_bytes", P, x_new.device)[1]
+            P.workspace = ptr(ws)                                            # per-tile dweight / dbias partial sums
         if dres is not None:
             dres = _as_cm(dres, x_new)
             P.dres, P.dres_batch_stride, P.dres_c_stride = dres.data_ptr(), dres.stride(0), dres.stride(2)
@@ -220,7 +208,7 @@ class _AddLayerNormCM(torch.autograd.Function):
         if ctx.needs_input_grad[1]:
             dbranch = _lib.empty((B, L, C), ctx.branch_dtype, x_new.device)
             P.dbranch, P.dbranch_batch_stride, P.dbranch_token_stride = dbranch.data_ptr(), L * C, C
-        _launch("vivim_add_layernorm_cm_bwd", P, x_new.device)
+        _lib.launch("vivim_add_layernorm_cm_bwd", P, x_new.device)
         return (dx, dbranch, (dwb[:C] if dwb is not None else None),
                 (dwb[C:] if dwb is not None and ctx.has_bias else None), None, None, None)
 
@@ -230,7 +218,7 @@ class _AddCM(torch.autograd.Function):
     def forward(ctx, x, branch, scale):
         P = _add_params(x, branch, scale)
         x_new = _add_forward(x, branch, scale, P)
-        _launch("vivim_add_layernorm_cm_fwd", P, x.device)
+        _lib.launch("vivim_add_layernorm_cm_fwd", P, x.device)
         ctx.save_for_backward(scale)
         ctx.branch_dtype = branch.dtype
         return x_new
@@ -245,11 +233,11 @@ class _AddCM(torch.autograd.Function):
         dbranch = _lib.empty((B, L, C), ctx.branch_dtype, dres.device)
         P = _lib.AddLayerNormParams()
         P.batch, P.seqlen, P.channels = B, L, C
-        P.itype, P.btype, P.otype = _ITYPE[dres.dtype], _ITYPE[ctx.branch_dtype], _ITYPE[dres.dtype]
-        P.scale = scale.data_ptr() if scale is not None else None
+        P.itype, P.btype, P.otype = ITYPE[dres.dtype], ITYPE[ctx.branch_dtype], ITYPE[dres.dtype]
+        P.scale = ptr(scale)
         P.dres, P.dres_batch_stride, P.dres_c_stride = dres.data_ptr(), dres.stride(0), dres.stride(2)
         P.dbranch, P.dbranch_batch_stride, P.dbranch_token_stride = dbranch.data_ptr(), L * C, C
-        _launch("vivim_add_layernorm_cm_bwd", P, dres.device)
+        _lib.launch("vivim_add_layernorm_cm_bwd", P, dres.device)
         return dres, dbranch, None                                           # dx is dres itself: no kernel
 
 

@@ -14,14 +14,12 @@ autograd keeps is the logits, the targets and 2 * N * C floats, against about te
 1 - p is never formed by subtraction, so the fp32 gradient holds to ~5e-7 of an fp64 evaluation at any logit scale (the eager
 composition loses three digits and more once the softmax is confident).  No float atomics: loss and gradient are bit-repeatable.
 The upstream gradient is read on the device and multiplied in fp32 before dlogits is rounded to the logits' dtype."""
-import ctypes
-
 import torch
 
 from . import _lib
+from ._lib import ITYPE
 from .train_step import _alpha_tensor, recall_focused_loss
 
-_ITYPE = {torch.float32: _lib.F32, torch.float16: _lib.F16, torch.bfloat16: _lib.BF16}
 _TTYPE = {torch.int64: 0, torch.uint8: 1}
 FOCAL_WEIGHT, TVERSKY_WEIGHT, TVERSKY_ALPHA, TVERSKY_BETA, SMOOTH, EPS = 0.4, 0.6, 0.3, 0.7, 1e-6, 1e-6
 
@@ -30,7 +28,7 @@ def supported(logits, targets, num_classes, gamma=2.0):
     if not (torch.is_tensor(logits) and torch.is_tensor(targets) and logits.is_cuda and targets.is_cuda
             and logits.device == targets.device):
         return False
-    if not (logits.dim() == 4 and logits.dtype in _ITYPE and targets.dim() == 3 and targets.dtype in _TTYPE):
+    if not (logits.dim() == 4 and logits.dtype in ITYPE and targets.dim() == 3 and targets.dtype in _TTYPE):
         return False
     N, C, H, W = logits.shape
     if not (C == num_classes and 2 <= C <= 8 and gamma == 2 and N > 0 and 0 < H * W < 2 ** 31 and N * 64 < 2 ** 31):
@@ -43,7 +41,7 @@ def supported(logits, targets, num_classes, gamma=2.0):
 def _params(logits, targets, alpha):
     N, C, H, W = logits.shape
     P = _lib.SegLossParams()
-    P.batch, P.classes, P.pixels, P.itype, P.ttype = N, C, H * W, _ITYPE[logits.dtype], _TTYPE[targets.dtype]
+    P.batch, P.classes, P.pixels, P.itype, P.ttype = N, C, H * W, ITYPE[logits.dtype], _TTYPE[targets.dtype]
     P.gamma, P.focal_weight, P.tversky_weight = 2.0, FOCAL_WEIGHT, TVERSKY_WEIGHT
     P.tversky_alpha, P.tversky_beta, P.smooth, P.eps = TVERSKY_ALPHA, TVERSKY_BETA, SMOOTH, EPS
     P.logits_batch_stride, P.logits_c_stride, P.target_batch_stride = logits.stride(0), logits.stride(1), targets.stride(0)
@@ -51,27 +49,18 @@ def _params(logits, targets, alpha):
     return P
 
 
-def _launch(name, P, device):
-    # the step is host-paced: no device context manager when the tensor's device is already the current one
-    if device.index == torch.cuda.current_device():
-        _lib.call(name, P, torch.cuda.current_stream().cuda_stream)
-    else:
-        with torch.cuda.device(device):
-            _lib.call(name, P, torch.cuda.current_stream().cuda_stream)
-
-
 class _RecallFocusedLoss(torch.autograd.Function):
     @staticmethod
     def forward(ctx, logits, targets, alpha, track):
         N, C = logits.shape[:2]
         P = _params(logits, targets, alpha)
-        ws_bytes = _lib.lib().vivim_seg_loss_workspace_bytes(ctypes.byref(P))
+        ws_bytes = _lib.lib().vivim_seg_loss_workspace_bytes(P)
         # one buffer: the partial-sum slots, then (only when a backward can follow) the (N, C, 2) Tversky gradient factors
         buf = _lib.empty((ws_bytes // 4 + (2 * N * C if track else 0),), torch.float32, logits.device)
         loss = _lib.empty((), torch.float32, logits.device)
         P.workspace, P.workspace_bytes, P.loss = buf.data_ptr(), ws_bytes, loss.data_ptr()
         P.coef = buf.data_ptr() + ws_bytes if track else None
-        _launch("vivim_seg_loss_fwd", P, logits.device)
+        _lib.launch("vivim_seg_loss_fwd", P, logits.device)
         if track:
             ctx.save_for_backward(logits, targets, alpha, buf)
             ctx.ws_bytes = ws_bytes
@@ -91,7 +80,7 @@ class _RecallFocusedLoss(torch.autograd.Function):
         P = _params(logits, targets, alpha)
         P.coef, P.grad_out, P.dlogits = buf.data_ptr() + ctx.ws_bytes, go.data_ptr(), dlogits.data_ptr()
         P.dlogits_batch_stride, P.dlogits_c_stride = C * H * W, H * W
-        _launch("vivim_seg_loss_bwd", P, logits.device)
+        _lib.launch("vivim_seg_loss_bwd", P, logits.device)
         return dlogits, None, None, None
 
 

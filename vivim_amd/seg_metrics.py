@@ -23,13 +23,11 @@ with HW pixels and tn = HW - tp - fp - fn (misc2.py at nan_for_nonexisting=False
     specificity = 0 if tp + fn == HW else tn / (tn + fp)                       (the image is all this class: zero by rule)
 `state[c] = [sum of each of the six over the (image, class c) pairs seen, their number]`, fp64, added in image order: additive
 across batches and ranks (all_reduce it), and bit-repeatable -- the counts are integers and nothing is added atomically."""
-import ctypes
-
 import torch
 
 from . import _lib
+from ._lib import ITYPE
 
-_ITYPE = {torch.float32: _lib.F32, torch.float16: _lib.F16, torch.bfloat16: _lib.BF16}
 _TTYPE = {torch.int64: 0, torch.uint8: 1}
 METRICS = ("dice", "jaccard", "precision", "recall", "f_measure", "specificity")
 
@@ -38,7 +36,7 @@ def supported(logits, targets, num_classes):
     if not (torch.is_tensor(logits) and torch.is_tensor(targets) and logits.is_cuda and targets.is_cuda
             and logits.device == targets.device):
         return False
-    if not (logits.dim() == 4 and logits.dtype in _ITYPE and targets.dim() == 3 and targets.dtype in _TTYPE):
+    if not (logits.dim() == 4 and logits.dtype in ITYPE and targets.dim() == 3 and targets.dtype in _TTYPE):
         return False
     N, C, H, W = logits.shape
     if not (C == num_classes and 2 <= C <= 8 and N > 0 and 0 < H * W < 2 ** 31 and N * 64 < 2 ** 31):
@@ -73,28 +71,22 @@ def _eager_accumulate(state, counts, pixels):
         state += vals[n]
 
 
-def _launch(logits, targets, return_preds, state):
+def _run(logits, targets, return_preds, state):
     N, C, H, W = logits.shape
     dev = logits.device
     P = _lib.SegMetricsParams()
-    P.batch, P.classes, P.pixels, P.itype, P.ttype = N, C, H * W, _ITYPE[logits.dtype], _TTYPE[targets.dtype]
+    P.batch, P.classes, P.pixels, P.itype, P.ttype = N, C, H * W, ITYPE[logits.dtype], _TTYPE[targets.dtype]
     P.logits_batch_stride, P.logits_c_stride, P.target_batch_stride = logits.stride(0), logits.stride(1), targets.stride(0)
     P.logits, P.target = logits.data_ptr(), targets.data_ptr()
-    ws_bytes = _lib.lib().vivim_seg_metrics_workspace_bytes(ctypes.byref(P))
-    ws = _lib.empty((ws_bytes // 4,), torch.int32, dev)
+    ws_bytes, ws = _lib.workspace("vivim_seg_metrics_workspace_bytes", P, dev)
     counts = _lib.empty((N, C, 3), torch.int32, dev)
     pred = _lib.empty((N, H, W), torch.uint8, dev) if return_preds else None
-    P.workspace, P.workspace_bytes, P.counts = ws.data_ptr(), ws_bytes, counts.data_ptr()
+    P.workspace, P.workspace_bytes, P.counts = _lib.ptr(ws), ws_bytes, counts.data_ptr()
     if pred is not None:
         P.pred, P.pred_batch_stride = pred.data_ptr(), H * W
     if state is not None:
         P.state = state.data_ptr()
-    # validation is host-paced like the step: no device context manager when the tensor's device is already the current one
-    if dev.index == torch.cuda.current_device():
-        _lib.call("vivim_seg_metrics", P, torch.cuda.current_stream().cuda_stream)
-    else:
-        with torch.cuda.device(dev):
-            _lib.call("vivim_seg_metrics", P, torch.cuda.current_stream().cuda_stream)
+    _lib.launch("vivim_seg_metrics", P, dev)
     return (counts, pred) if return_preds else counts
 
 
@@ -104,7 +96,7 @@ def seg_confusion_counts(logits, targets, num_classes, return_preds=False):
     logits = logits.detach()
     if not supported(logits, targets, num_classes):
         return _eager_counts(logits, targets, num_classes, return_preds)
-    return _launch(logits, targets, return_preds, None)
+    return _run(logits, targets, return_preds, None)
 
 
 class SegMetricsTracker:
@@ -133,7 +125,7 @@ class SegMetricsTracker:
         if logits.shape[0] == 0:
             return
         if supported(logits, targets, C) and self.state.is_contiguous():
-            _launch(logits, targets, False, self.state)
+            _run(logits, targets, False, self.state)
         else:
             _eager_accumulate(self.state, _eager_counts(logits, targets, C, False), logits.shape[2] * logits.shape[3])
 

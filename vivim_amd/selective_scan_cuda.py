@@ -6,23 +6,12 @@ signatures, argument checks and return lists, running the gfx950 kernels through
 `fwd_lean` is ours: the forward for a call no backward follows.  Same kernels and bits as `fwd`, but neither the
 checkpoint tensor `x` nor (when z is given) the ungated `out` is allocated or written.
 """
-import ctypes
-
 import torch
 
 from . import _lib
+from ._lib import ITYPE, check, ptr
 
-_ITYPE = {torch.float32: _lib.F32, torch.float16: _lib.F16, torch.bfloat16: _lib.BF16}
 last_workspace_bytes = {}     # what the last fwd / bwd call asked for (tools/kbench.py derives the token-axis cut from it)
-
-
-def _check(cond, msg):
-    if not cond:
-        raise RuntimeError(msg)
-
-
-def _ptr(t):
-    return None if t is None else t.data_ptr()
 
 
 def chunk_len(P):
@@ -32,41 +21,41 @@ def chunk_len(P):
 
 def _common_checks(u, delta, A, B, C, D_, z_, delta_bias_):
     """selective_scan.cpp:233-304 / 352-438."""
-    _check(u.dtype in _ITYPE, "selective_scan not implemented for input type '%s'" % u.dtype)
-    _check(A.dtype == torch.float32,
+    check(u.dtype in ITYPE, "selective_scan not implemented for input type '%s'" % u.dtype)
+    check(A.dtype == torch.float32,
            "selective_scan not implemented for weight type '%s' (real fp32 A only)" % A.dtype)
     var_B, var_C = B.dim() >= 3, C.dim() >= 3
-    _check(delta.dtype == u.dtype, "delta must have the dtype of u")
-    _check(B.dtype == (u.dtype if var_B else A.dtype), "B has the wrong dtype")
-    _check(C.dtype == (u.dtype if var_C else A.dtype), "C has the wrong dtype")
+    check(delta.dtype == u.dtype, "delta must have the dtype of u")
+    check(B.dtype == (u.dtype if var_B else A.dtype), "B has the wrong dtype")
+    check(C.dtype == (u.dtype if var_C else A.dtype), "C has the wrong dtype")
     for name, t in (("u", u), ("delta", delta), ("A", A), ("B", B), ("C", C)):
-        _check(t.is_cuda, f"{name} must be a CUDA/HIP tensor")
-    _check(u.dim() == 3, "u must be (batch, dim, seqlen)")
-    _check(u.stride(-1) == 1 and delta.stride(-1) == 1, "u and delta must have stride(-1) == 1")
+        check(t.is_cuda, f"{name} must be a CUDA/HIP tensor")
+    check(u.dim() == 3, "u must be (batch, dim, seqlen)")
+    check(u.stride(-1) == 1 and delta.stride(-1) == 1, "u and delta must have stride(-1) == 1")
     batch, dim, seqlen = u.shape
     dstate = A.shape[1]
     n_groups = B.shape[1] if var_B else 1
-    _check(dstate <= 256, "selective_scan only supports state dimension <= 256")
-    _check(tuple(delta.shape) == (batch, dim, seqlen), "delta must have shape (batch, dim, seqlen)")
-    _check(tuple(A.shape) == (dim, dstate), "A must have shape (dim, dstate)")
+    check(dstate <= 256, "selective_scan only supports state dimension <= 256")
+    check(tuple(delta.shape) == (batch, dim, seqlen), "delta must have shape (batch, dim, seqlen)")
+    check(tuple(A.shape) == (dim, dstate), "A must have shape (dim, dstate)")
     if var_B:
-        _check(B.dim() == 4 and tuple(B.shape) == (batch, n_groups, dstate, seqlen),
+        check(B.dim() == 4 and tuple(B.shape) == (batch, n_groups, dstate, seqlen),
                "B must have shape (batch, n_groups, dstate, seqlen)")
-        _check(B.stride(-1) == 1, "B must have stride(-1) == 1")
+        check(B.stride(-1) == 1, "B must have stride(-1) == 1")
     else:
-        _check(tuple(B.shape) == (dim, dstate), "B must have shape (dim, dstate)")
+        check(tuple(B.shape) == (dim, dstate), "B must have shape (dim, dstate)")
     if var_C:
-        _check(C.dim() == 4 and tuple(C.shape) == (batch, n_groups, dstate, seqlen),
+        check(C.dim() == 4 and tuple(C.shape) == (batch, n_groups, dstate, seqlen),
                "C must have shape (batch, n_groups, dstate, seqlen)")
-        _check(C.stride(-1) == 1, "C must have stride(-1) == 1")
+        check(C.stride(-1) == 1, "C must have stride(-1) == 1")
     else:
-        _check(tuple(C.shape) == (dim, dstate), "C must have shape (dim, dstate)")
+        check(tuple(C.shape) == (dim, dstate), "C must have shape (dim, dstate)")
     for name, t in (("D", D_), ("delta_bias", delta_bias_)):
         if t is not None:
-            _check(t.dtype == torch.float32 and t.is_cuda and t.stride(-1) == 1 and tuple(t.shape) == (dim,),
+            check(t.dtype == torch.float32 and t.is_cuda and t.stride(-1) == 1 and tuple(t.shape) == (dim,),
                    f"{name} must be a contiguous fp32 CUDA tensor of shape (dim,)")
     if z_ is not None:
-        _check(z_.dtype == u.dtype and z_.is_cuda and z_.stride(-1) == 1
+        check(z_.dtype == u.dtype and z_.is_cuda and z_.stride(-1) == 1
                and tuple(z_.shape) == (batch, dim, seqlen), "z must match u (dtype, shape, stride(-1) == 1)")
     return batch, dim, seqlen, dstate, n_groups, var_B, var_C
 
@@ -74,7 +63,7 @@ def _common_checks(u, delta, A, B, C, D_, z_, delta_bias_):
 def _fill_fwd(P, u, delta, A, B, C, D_, z_, delta_bias_, delta_softplus, dims):
     batch, dim, seqlen, dstate, n_groups, var_B, var_C = dims
     P.batch, P.dim, P.seqlen, P.dstate, P.n_groups = batch, dim, seqlen, dstate, n_groups
-    P.itype = _ITYPE[u.dtype]
+    P.itype = ITYPE[u.dtype]
     P.is_variable_B, P.is_variable_C = int(var_B), int(var_C)
     P.delta_softplus = int(bool(delta_softplus))
     P.u_batch_stride, P.u_d_stride = u.stride(0), u.stride(1)
@@ -89,7 +78,7 @@ def _fill_fwd(P, u, delta, A, B, C, D_, z_, delta_bias_, delta_softplus, dims):
     else:
         P.C_batch_stride, P.C_group_stride, P.C_dstate_stride = 0, C.stride(0), C.stride(1)
     P.u, P.delta, P.A, P.B, P.C = u.data_ptr(), delta.data_ptr(), A.data_ptr(), B.data_ptr(), C.data_ptr()
-    P.D, P.delta_bias, P.z = _ptr(D_), _ptr(delta_bias_), _ptr(z_)
+    P.D, P.delta_bias, P.z = ptr(D_), ptr(delta_bias_), ptr(z_)
     if z_ is not None:
         P.z_batch_stride, P.z_d_stride = z_.stride(0), z_.stride(1)
 
@@ -109,13 +98,9 @@ def fwd(u, delta, A, B, C, D_, z_, delta_bias_, delta_softplus):
     if out_z is not None:
         P.out_z = out_z.data_ptr()
         P.out_z_batch_stride, P.out_z_d_stride = out_z.stride(0), out_z.stride(1)
-    ws_bytes = _lib.lib().vivim_scan_fwd_workspace_bytes(P)
-    last_workspace_bytes["fwd"] = ws_bytes
-    if ws_bytes:
-        workspace = _lib.empty((ws_bytes,), torch.uint8, u.device)
-        P.workspace, P.workspace_bytes = workspace.data_ptr(), ws_bytes
-    with torch.cuda.device(u.device):
-        _lib.call("vivim_selective_scan_fwd", P, torch.cuda.current_stream().cuda_stream)
+    last_workspace_bytes["fwd"], workspace = _lib.workspace("vivim_scan_fwd_workspace_bytes", P, u.device)
+    P.workspace, P.workspace_bytes = ptr(workspace), last_workspace_bytes["fwd"]
+    _lib.launch("vivim_selective_scan_fwd", P, u.device)
     return [out, x] + ([out_z] if out_z is not None else [])
 
 
@@ -134,13 +119,9 @@ def fwd_lean(u, delta, A, B, C, D_, z_, delta_bias_, delta_softplus, return_last
         P.out = result.data_ptr()
         P.out_batch_stride, P.out_d_stride = result.stride(0), result.stride(1)
     last_state = _lib.empty((batch, dim, dstate), torch.float32, u.device) if return_last_state else None
-    ws_bytes = _lib.lib().vivim_scan_fwd_workspace_bytes(P)
-    last_workspace_bytes["fwd"] = ws_bytes
-    if ws_bytes:
-        workspace = _lib.empty((ws_bytes,), torch.uint8, u.device)
-        P.workspace, P.workspace_bytes = workspace.data_ptr(), ws_bytes
-    with torch.cuda.device(u.device):
-        _lib.call_lean_fwd(P, _ptr(last_state), torch.cuda.current_stream().cuda_stream)
+    last_workspace_bytes["fwd"], workspace = _lib.workspace("vivim_scan_fwd_workspace_bytes", P, u.device)
+    P.workspace, P.workspace_bytes = ptr(workspace), last_workspace_bytes["fwd"]
+    _lib.launch("vivim_selective_scan_fwd_lean", P, u.device, ptr(last_state))
     return [result] + ([last_state] if return_last_state else [])
 
 
@@ -149,27 +130,27 @@ def bwd(u, delta, A, B, C, D_, z_, delta_bias_, dout, x_, out_, dz_, delta_softp
     selective_scan.cpp:338-492."""
     dims = _common_checks(u, delta, A, B, C, D_, z_, delta_bias_)
     batch, dim, seqlen, dstate, n_groups, var_B, var_C = dims
-    _check(dout.dtype == u.dtype and dout.is_cuda and dout.stride(-1) == 1
+    check(dout.dtype == u.dtype and dout.is_cuda and dout.stride(-1) == 1
            and tuple(dout.shape) == (batch, dim, seqlen), "dout must match u (dtype, shape, stride(-1) == 1)")
     P = _lib.SsmBwdParams()
     _fill_fwd(P.f, u, delta, A, B, C, D_, z_, delta_bias_, delta_softplus, dims)
     ck = chunk_len(P.f)
     n_chunks = (seqlen + ck - 1) // ck
     if n_chunks > 1:
-        _check(x_ is not None, "x (scan checkpoints) is required when seqlen spans several chunks")
+        check(x_ is not None, "x (scan checkpoints) is required when seqlen spans several chunks")
     if x_ is not None:
-        _check(x_.dtype == torch.float32 and x_.is_cuda and x_.is_contiguous()
+        check(x_.dtype == torch.float32 and x_.is_cuda and x_.is_contiguous()
                and tuple(x_.shape) == (batch, dim, n_chunks, dstate),
                "x must be the contiguous fp32 (batch, dim, n_chunks, dstate) tensor returned by fwd")
     has_z = z_ is not None
     out_z = None
     dz = None
     if has_z:
-        _check(out_ is not None, "out is required when z is given")
-        _check(out_.dtype == u.dtype and out_.is_cuda and out_.stride(-1) == 1
+        check(out_ is not None, "out is required when z is given")
+        check(out_.dtype == u.dtype and out_.is_cuda and out_.stride(-1) == 1
                and tuple(out_.shape) == (batch, dim, seqlen), "out must match u (dtype, shape, stride(-1) == 1)")
         if dz_ is not None:
-            _check(dz_.dtype == u.dtype and dz_.is_cuda and dz_.stride(-1) == 1
+            check(dz_.dtype == u.dtype and dz_.is_cuda and dz_.stride(-1) == 1
                    and tuple(dz_.shape) == (batch, dim, seqlen), "dz must match u (dtype, shape, stride(-1) == 1)")
             dz = dz_
         else:
@@ -188,7 +169,7 @@ def bwd(u, delta, A, B, C, D_, z_, delta_bias_, dout, x_, out_, dz_, delta_softp
     dD = acc[nB + nC + nA:nB + nC + nA + dim] if D_ is not None else None
     ddelta_bias = acc[nB + nC + nA + dim:] if delta_bias_ is not None else None
 
-    P.f.x = _ptr(x_)
+    P.f.x = ptr(x_)
     if has_z:
         P.f.out = out_.data_ptr()
         P.f.out_batch_stride, P.f.out_d_stride = out_.stride(0), out_.stride(1)
@@ -210,21 +191,16 @@ def bwd(u, delta, A, B, C, D_, z_, delta_bias_, dout, x_, out_, dz_, delta_softp
     else:
         P.dB_batch_stride, P.dB_group_stride, P.dB_dstate_stride = 0, dB.stride(0), dB.stride(1)
         P.dC_batch_stride, P.dC_group_stride, P.dC_dstate_stride = 0, dC.stride(0), dC.stride(1)
-    P.dD, P.ddelta_bias = _ptr(dD), _ptr(ddelta_bias)
-    ws_bytes = _lib.lib().vivim_scan_bwd_workspace_bytes(P.f)
-    last_workspace_bytes["bwd"] = ws_bytes
-    if ws_bytes:
-        workspace = _lib.empty((ws_bytes,), torch.uint8, u.device)   # torch caching allocator: no sync
-        P.workspace, P.workspace_bytes = workspace.data_ptr(), ws_bytes
-    with torch.cuda.device(u.device):
-        if _lib.deterministic():                                     # fixed-order slot reduction, no float atomics
-            det_bytes = _lib.lib().vivim_scan_bwd_det_call_workspace_bytes(ctypes.byref(P))
-            last_workspace_bytes["bwd_det"] = det_bytes
-            det_ws = _lib.empty((det_bytes,), torch.uint8, u.device)
-            _lib.call_det("vivim_selective_scan_bwd_det", P, det_ws.data_ptr(), det_bytes,
-                          torch.cuda.current_stream().cuda_stream)
-        else:
-            _lib.call("vivim_selective_scan_bwd", P, torch.cuda.current_stream().cuda_stream)
+    P.dD, P.ddelta_bias = ptr(dD), ptr(ddelta_bias)
+    # torch caching allocator: no sync
+    last_workspace_bytes["bwd"], workspace = _lib.workspace("vivim_scan_bwd_workspace_bytes", P.f, u.device)
+    P.workspace, P.workspace_bytes = ptr(workspace), last_workspace_bytes["bwd"]
+    if _lib.deterministic():                                         # fixed-order slot reduction, no float atomics
+        det_bytes, det_ws = _lib.workspace("vivim_scan_bwd_det_call_workspace_bytes", P, u.device)
+        last_workspace_bytes["bwd_det"] = det_bytes
+        _lib.launch("vivim_selective_scan_bwd_det", P, u.device, ptr(det_ws), det_bytes)
+    else:
+        _lib.launch("vivim_selective_scan_bwd", P, u.device)
     if var_B and var_C and B.dtype != torch.float32:
         dBC = acc[:nB + nC].to(B.dtype)
         dB_out, dC_out = dBC[:nB].view(B.shape), dBC[nB:].view(C.shape)

@@ -23,8 +23,8 @@ import torch
 import torch.nn.functional as F
 
 from . import _lib
+from ._lib import ITYPE
 
-_ITYPE = {torch.float32: _lib.F32, torch.float16: _lib.F16, torch.bfloat16: _lib.BF16}
 _I31 = 2 ** 31 - 1
 
 
@@ -62,7 +62,7 @@ def _blocks(N, C, H, W, OH, OW, layout):
 
 
 def supported(x, size):
-    if not (torch.is_tensor(x) and x.is_cuda and x.dim() == 4 and x.dtype in _ITYPE and len(size) == 2):
+    if not (torch.is_tensor(x) and x.is_cuda and x.dim() == 4 and x.dtype in ITYPE and len(size) == 2):
         return False
     N, C, H, W = x.shape
     OH, OW = int(size[0]), int(size[1])
@@ -81,20 +81,11 @@ def _empty(N, C, H, W, layout, like):
     return _lib.empty((N, C, H, W), like.dtype, like.device)
 
 
-def _launch(name, P, dev):
-    # host-paced like the step: no device context manager when the tensor's device is already the current one
-    if dev.index == torch.cuda.current_device():
-        _lib.call(name, P, torch.cuda.current_stream().cuda_stream)
-    else:
-        with torch.cuda.device(dev):
-            _lib.call(name, P, torch.cuda.current_stream().cuda_stream)
-
-
 def _params(shape, size, layout, dtype):
     P = _lib.UpsampleParams()
     P.batch, P.channels, P.in_h, P.in_w = shape
     P.out_h, P.out_w = size
-    P.itype, P.layout = _ITYPE[dtype], layout
+    P.itype, P.layout = ITYPE[dtype], layout
     return P
 
 
@@ -110,7 +101,7 @@ class _BilinearUpsample(torch.autograd.Function):
         P = _params(ctx.shape, size, layout, x.dtype)
         P.x_batch_stride, P.y_batch_stride = x.stride(0), y.stride(0)
         P.x, P.y = x.data_ptr(), y.data_ptr()
-        _launch("vivim_upsample_bilinear2d_fwd", P, x.device)
+        _lib.launch("vivim_upsample_bilinear2d_fwd", P, x.device)
         return y
 
     @staticmethod
@@ -125,7 +116,7 @@ class _BilinearUpsample(torch.autograd.Function):
         P = _params(ctx.shape, ctx.size, ctx.layout, dy.dtype)
         P.x_batch_stride, P.y_batch_stride = dx.stride(0), dy.stride(0)
         P.dy, P.dx = dy.data_ptr(), dx.data_ptr()
-        _launch("vivim_upsample_bilinear2d_bwd", P, dy.device)
+        _lib.launch("vivim_upsample_bilinear2d_bwd", P, dy.device)
         return dx, None
 
 
@@ -133,7 +124,7 @@ def bilinear_upsample(x, size):
     """F.interpolate(x, size=size, mode="bilinear", align_corners=False) through csrc/upsample.hip where `supported` says so
     (after making a tensor of neither layout contiguous in its suggested format), and that very call otherwise."""
     size = (int(size[0]), int(size[1]))
-    if torch.is_tensor(x) and x.is_cuda and x.dim() == 4 and x.dtype in _ITYPE and not os.environ.get("VIVIM_NO_UPSAMPLE"):
+    if torch.is_tensor(x) and x.is_cuda and x.dim() == 4 and x.dtype in ITYPE and not os.environ.get("VIVIM_NO_UPSAMPLE"):
         if torch.is_autocast_enabled():                  # autocast's fp32 list holds upsample_bilinear2d: same dtypes as ATen
             x = x.float()
         if not _dense(x, _layout(x)):

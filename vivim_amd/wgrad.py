@@ -36,9 +36,5 @@ def wgrad_nt(a, b):
     P.b_group_stride, P.b_row_stride = b.stride(0), b.stride(1)
     P.out_group_stride, P.out_row_stride = M * N, N
     P.a, P.b, P.out = a.data_ptr(), b.data_ptr(), out.data_ptr()
-    if a.device.index == torch.cuda.current_device():
-        _lib.call("vivim_wgrad_nt", P, torch.cuda.current_stream().cuda_stream)
-    else:
-        with torch.cuda.device(a.device):
-            _lib.call("vivim_wgrad_nt", P, torch.cuda.current_stream().cuda_stream)
+    _lib.launch("vivim_wgrad_nt", P, a.device)
     return out
