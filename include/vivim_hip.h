@@ -417,6 +417,36 @@ typedef struct {
     void *dx;                                        /* backward output */
 } vivim_upsample_params;
 
+/* ---- Eval-mode decode head: upsample, add, ReLU and the class projection in one kernel (csrc/decode_head.hip; opt-in in Vivim) --
+ * With BatchNorm's running statistics, linear_fuse and the per-stage projections folded into the maps m_s (vivim_amd/decode_head.py):
+ *   h[k]      = max(0, bias[k] + sum over maps s of  l0h * (l0w * m_s[i0h][i0w][k] + l1w * m_s[i0h][i1w][k])
+ *                                                  + l1h * (l0w * m_s[i1h][i0w][k] + l1w * m_s[i1h][i1w][k]))        fp32
+ *   logits[c] = b_out[c] + sum over k of w_out[c][k] * h[k]                                        fp32, rounded once to itype
+ * per output pixel, the taps (i0, i1, l0, l1) per axis being those of the bilinear upsampling above (in_h = map_h[s],
+ * out_h = out_h, likewise for w).  A map of the output's own size is read with one tap of weight 1.
+ * maps[s]: (batch, map_h[s], map_w[s], hidden) MEMORY, each image dense (channels-last), n_maps of them (1..4); logits:
+ * (batch, classes, out_h, out_w), each image contiguous planes.  Batch strides are free, in elements, and at least one image.
+ * bias (hidden), w_out (classes, hidden) and b_out (classes; NULL: zeros) are contiguous fp32.
+ * 16-byte accesses to the maps when hidden is a whole number of them and every map's base and batch stride are 16-byte
+ * aligned, element accesses otherwise (element-size alignment is the only requirement).
+ * Determinism: no atomics and no workspace; every logit is reduced by one wave in a fixed order.
+ * Limits: 1 <= classes <= 8 and 1 <= hidden <= 1024 (bias and w_out live in LDS), else VIVIM_ERR_INVALID; a map larger than
+ * the output on an axis returns VIVIM_ERR_UNSUPPORTED; an image of any map or of the logits and the number of workgroups
+ * (batch * ceil(out_h / 8) * ceil(out_w / 8)) must fit 31 bits, else VIVIM_ERR_INVALID.
+ * This struct has no vivim_sizeof row: the caller sets struct_bytes = sizeof(vivim_decode_head_params) and any other value is
+ * refused with VIVIM_ERR_INVALID. */
+typedef struct {
+    int32_t struct_bytes;                            /* sizeof(vivim_decode_head_params) as the caller compiled it */
+    int32_t batch, hidden, classes, n_maps, out_h, out_w;
+    int32_t itype;                                   /* maps and logits: vivim_dtype_t */
+    int32_t map_h[4], map_w[4];
+    int64_t map_batch_stride[4];                     /* in elements */
+    int64_t logits_batch_stride;
+    const void *maps[4];
+    const void *bias, *w_out, *b_out;                /* fp32 */
+    void *logits;
+} vivim_decode_head_params;
+
 int vivim_abi_version(void);
 const char *vivim_last_error(void);
 
@@ -479,6 +509,7 @@ int vivim_seg_metrics(const vivim_seg_metrics_params *p, void *stream);
 size_t vivim_seg_metrics_workspace_bytes(const vivim_seg_metrics_params *p);   /* from batch, classes, pixels, itype; 0 on bad sizes */
 int vivim_upsample_bilinear2d_fwd(const vivim_upsample_params *p, void *stream);   /* reads x, writes y */
 int vivim_upsample_bilinear2d_bwd(const vivim_upsample_params *p, void *stream);   /* reads dy, writes dx */
+int vivim_decode_head_fwd(const vivim_decode_head_params *p, void *stream);        /* reads the maps, writes logits */
 
 /* Deterministic backward (for torch.use_deterministic_algorithms).  Same parameters, checks and results as
  * vivim_selective_scan_bwd, and the same kernel family, but every gradient that the default call adds up across

@@ -17,4 +17,7 @@ def __getattr__(name):
     if name == "bilinear_upsample":                    # the decode head's upsampling (upsample.py), likewise
         from . import upsample
         return upsample.bilinear_upsample
+    if name in ("fused_decode_head", "fold_decode_head"):     # the eval-mode decode head (decode_head.py), likewise
+        from . import decode_head
+        return getattr(decode_head, name)
     raise AttributeError(f"module {__name__!r} has no attribute {name!r}")

@@ -156,6 +156,15 @@ class UpsampleParams(ctypes.Structure):
                 + [(n, vp) for n in ("x", "y", "dy", "dx")])
 
 
+class DecodeHeadParams(ctypes.Structure):
+    """No vivim_sizeof row (and not in STRUCTS): the caller states its sizeof in struct_bytes and the entry point refuses
+    any other value."""
+    _fields_ = ([(n, i32) for n in ("struct_bytes", "batch", "hidden", "classes", "n_maps", "out_h", "out_w", "itype")]
+                + [("map_h", i32 * 4), ("map_w", i32 * 4), ("map_batch_stride", i64 * 4), ("logits_batch_stride", i64),
+                   ("maps", vp * 4)]
+                + [(n, vp) for n in ("bias", "w_out", "b_out", "logits")])
+
+
 # The structs in vivim_sizeof order.
 STRUCTS = (SsmFwdParams, SsmBwdParams, ConvFwdParams, ConvBwdParams, DwConvParams, DwConvWgradParams, DirParams,
            ConvUpdateParams, StateUpdateParams, LayerNormParams, WgradNtParams, AddLayerNormParams, SegLossParams,
@@ -216,6 +225,7 @@ ENTRY_POINTS = {
     "vivim_seg_metrics_workspace_bytes": _query(SegMetricsParams),
     "vivim_upsample_bilinear2d_fwd": _kernel(UpsampleParams),
     "vivim_upsample_bilinear2d_bwd": _kernel(UpsampleParams),
+    "vivim_decode_head_fwd": Entry(None, (ctypes.POINTER(DecodeHeadParams),), True, _int),
 }
 EXPORTS = tuple(ENTRY_POINTS)
 
@@ -274,6 +284,10 @@ def algorithmic_bytes(name, P):
             return n * (2 * _ISIZE[P.itype] + _ISIZE[P.btype] + _ISIZE[P.otype]) + 8 * P.batch * P.seqlen + 8 * P.channels
         res = (_ISIZE[P.itype] if P.dres else 0) + (_ISIZE[P.otype] if P.dy else 0) + (_ISIZE[P.btype] if P.dbranch else 0)
         return n * (2 * _ISIZE[P.itype] + res) + 8 * P.batch * P.seqlen + 12 * P.channels   # x_new, dx + what is present
+    if name.startswith("vivim_decode_head"):                            # the maps once, the logits once, bias + w_out + b_out
+        px = sum(P.map_h[s] * P.map_w[s] for s in range(P.n_maps))
+        return (P.batch * (px * P.hidden + P.classes * P.out_h * P.out_w) * _ISIZE[P.itype]
+                + 4 * (P.hidden + P.classes * P.hidden + P.classes))
     if name.startswith("vivim_upsample"):                               # the small and the large tensor once, either direction
         return P.batch * P.channels * (P.in_h * P.in_w + P.out_h * P.out_w) * _ISIZE[P.itype]
     if name.startswith("vivim_seg_metrics"):                            # logits, labels, the prediction map if wanted, the counts

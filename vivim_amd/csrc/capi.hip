@@ -45,6 +45,9 @@ bool seg_metrics_dispatch(const vivim_seg_metrics_params&, hipStream_t);        
 size_t seg_metrics_workspace_bytes(const vivim_seg_metrics_params&);
 bool upsample_dispatch(const vivim_upsample_params&, bool bwd, hipStream_t);      // upsample.hip
 int64_t upsample_blocks(const vivim_upsample_params&, bool bwd);
+bool decode_head_dispatch(const vivim_decode_head_params&, hipStream_t);          // decode_head.hip
+int64_t decode_head_blocks(const vivim_decode_head_params&);
+int decode_head_max_hidden();
 }  // namespace vivim
 
 static thread_local char g_err[512] = "";
@@ -595,6 +598,47 @@ int vivim_upsample_bilinear2d_bwd(const vivim_upsample_params* p, void* stream) 
     if (!vivim::upsample_dispatch(*p, true, as_stream(stream)))
         return fail(VIVIM_ERR_UNSUPPORTED, "upsample_bilinear2d_bwd not implemented for type %d", p->itype);
     return after_launch("upsample_bilinear2d_bwd");
+}
+
+// every refusal of the fused decode head, before any launch
+static int check_decode_head(const vivim_decode_head_params* p) {
+    VCHECK(p != nullptr);
+    if (p->struct_bytes != (int32_t)sizeof(vivim_decode_head_params))
+        return fail(VIVIM_ERR_INVALID, "decode_head_fwd: struct_bytes = %d, this library's vivim_decode_head_params has %zu", p->struct_bytes,
+                    sizeof(vivim_decode_head_params));
+    VCHECK(dtype_ok(p->itype));
+    VCHECK(p->batch > 0 && p->hidden > 0 && p->classes > 0 && p->out_h > 0 && p->out_w > 0);
+    VCHECK(p->n_maps >= 1 && p->n_maps <= 4);
+    VCHECK(p->classes <= 8);
+    if (p->hidden > vivim::decode_head_max_hidden())
+        return fail(VIVIM_ERR_INVALID, "decode_head_fwd: hidden = %d: bias and w_out are kept in LDS, which holds up to %d channels",
+                    p->hidden, vivim::decode_head_max_hidden());
+    const uintptr_t ib = p->itype == VIVIM_F32 ? 4 : 2;
+    // the kernel indexes inside an image, and builds its grid, with 32-bit integers
+    VCHECK((int64_t)p->classes * p->out_h * p->out_w <= INT32_MAX);
+    for (int s = 0; s < p->n_maps; ++s) {
+        VCHECK(p->map_h[s] > 0 && p->map_w[s] > 0);
+        if (p->map_h[s] > p->out_h || p->map_w[s] > p->out_w)
+            return fail(VIVIM_ERR_UNSUPPORTED, "decode_head_fwd: map %d is (%d, %d), the output (%d, %d): upsampling only", s, p->map_h[s],
+                        p->map_w[s], p->out_h, p->out_w);
+        VCHECK((int64_t)p->hidden * p->map_h[s] * p->map_w[s] <= INT32_MAX);
+    }
+    for (int s = 0; s < p->n_maps; ++s) VCHECK(p->maps[s] != nullptr && aligned(p->maps[s], ib));
+    VCHECK(p->bias != nullptr && aligned(p->bias, 4));
+    VCHECK(p->w_out != nullptr && aligned(p->w_out, 4));
+    VCHECK(aligned(p->b_out, 4));                                   // NULL: zeros
+    VCHECK(p->logits != nullptr && aligned(p->logits, ib));
+    for (int s = 0; s < p->n_maps; ++s) VCHECK(p->map_batch_stride[s] >= (int64_t)p->hidden * p->map_h[s] * p->map_w[s]);
+    VCHECK(p->logits_batch_stride >= (int64_t)p->classes * p->out_h * p->out_w);
+    VCHECK(vivim::decode_head_blocks(*p) <= INT32_MAX);
+    return VIVIM_OK;
+}
+
+int vivim_decode_head_fwd(const vivim_decode_head_params* p, void* stream) {
+    if (int rc = check_decode_head(p)) return rc;
+    if (!vivim::decode_head_dispatch(*p, as_stream(stream)))
+        return fail(VIVIM_ERR_UNSUPPORTED, "decode_head_fwd not implemented for type %d", p->itype);
+    return after_launch("decode_head_fwd");
 }
 
 }  // extern "C"

@@ -1,7 +1,7 @@
 // upsample.hip -- bilinear 2-D upsampling (align_corners = False, no explicit scale factors) and its gradient: the decode head's
 // F.interpolate calls (include/vivim_hip.h: vivim_upsample_params; the autograd wrapper is vivim_amd/upsample.py).
 //
-// One tap function, up_tap, turns an output index into (i0, i1, l0, l1) with ATen's fp32 arithmetic.  The forward reads four
+// One tap function, up_tap (up_tap.cuh), turns an output index into (i0, i1, l0, l1) with ATen's fp32 arithmetic.  The forward reads four
 // inputs through it; the backward is the same map transposed in GATHER form: a dx element looks at every output index that can
 // tap it (up_window: a contiguous run, sized from the exact rational bounds plus two indices of slack for the fp32 rounding of
 // the tap), recomputes that output's taps with up_tap itself and adds l0 where i0 is its own index and l1 where i1 is (at the
@@ -16,6 +16,7 @@
 // Every grid is one-dimensional (blockIdx.x decoded on the scalar unit), so N * C planes are not bound by the y / z limits.
 #include "common.cuh"
 #include "seg_load.cuh"
+#include "up_tap.cuh"
 
 namespace vivim {
 
@@ -25,23 +26,6 @@ constexpr int kUpTileW = 64;
 constexpr int kUpTileH = 4;          // planes backward: 64 input columns x 4 input rows per workgroup
 constexpr int kUpLdsW = 512;         // planes backward: output columns per LDS chunk
 
-struct UpTap {
-    int i0, i1;
-    float l0, l1;
-};
-
-// ATen's area_pixel_compute_source_index and the index / lambda lines after it, per axis, in fp32.  The fma is spelled out so
-// that every kernel below forms the same src whatever the compiler would contract: forward and backward are exact transposes.
-__device__ __forceinline__ UpTap up_tap(int o, float r, int n_in) {
-    float src = fmaf(r, (float)o + 0.5f, -0.5f);
-    src = src < 0.0f ? 0.0f : src;
-    UpTap t;
-    t.i0 = min((int)src, n_in - 1);              // src < n_in - 0.5 for r <= 1: the min never binds, it keeps a read in range
-    t.i1 = t.i0 + (t.i0 < n_in - 1 ? 1 : 0);
-    t.l1 = src - (float)t.i0;
-    t.l0 = 1.0f - t.l1;
-    return t;
-}
 __device__ __forceinline__ bool up_hits(const UpTap& t, int i) { return t.i0 == i || t.i1 == i; }
 __device__ __forceinline__ float up_weight(const UpTap& t, int i) { return (t.i0 == i ? t.l0 : 0.0f) + (t.i1 == i ? t.l1 : 0.0f); }
 

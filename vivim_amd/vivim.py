@@ -19,6 +19,10 @@ Differences from the reference, all additive:
   * `Vivim(..., fused_upsample=True)` takes the decode head's bilinear upsampling (the per-stage features, the logits and the
     edge map) through csrc/upsample.hip, whose gather-form backward is bit-repeatable and runs under
     torch.use_deterministic_algorithms(True) (upsample.py); off by default, `VIVIM_NO_UPSAMPLE=1` opts out again.
+  * `Vivim(..., fused_decode_head=True)` runs the decode head of an eval-mode, no-grad forward as four folded projections and
+    one kernel (csrc/decode_head.hip, decode_head.py): BatchNorm's running statistics, linear_fuse and the projections fold
+    into four small matrices, the upsampling, the ReLU and `out` happen on chip.  Off by default, `VIVIM_NO_FUSED_HEAD=1` opts
+    out again; training, grad mode and anything the kernel does not take run the stock path unchanged.
   * timm is not required: DropPath / trunc_normal_ are the torch equivalents.
 """
 import math
@@ -29,6 +33,7 @@ import torch
 import torch.nn as nn
 import torch.nn.functional as F
 
+from . import decode_head as _dh
 from . import dwconv as _dw
 from . import layernorm as _ln
 from . import upsample as _up
@@ -330,9 +335,10 @@ class Vivim(nn.Module):
                  drop_path_rate=0.2, layer_scale_init_value=1e-6, hidden_size: int = 768, norm_name="instance",
                  conv_block: bool = True, res_block: bool = True, spatial_dims=2, with_edge=False,
                  dropout_rate=0.3, backbone=None, mamba_kwargs=None, fast_backbone_dwconv=False,
-                 fused_upsample=False) -> None:
+                 fused_upsample=False, fused_decode_head=False) -> None:
         super().__init__()
         self.fused_upsample = fused_upsample
+        self.fused_decode_head = fused_decode_head
         self.hidden_size = hidden_size
         self.in_chans, self.out_chans = in_chans, out_chans
         self.depths, self.feat_size = depths, feat_size
@@ -363,6 +369,11 @@ class Vivim(nn.Module):
         return dec.linear_c if hasattr(dec, "linear_c") else dec.linear_projections
 
     def decode(self, encoder_hidden_states, bz, nf):
+        if (self.fused_decode_head and not os.environ.get("VIVIM_NO_FUSED_HEAD")
+                and _dh.applies(self, encoder_hidden_states)):
+            # eval, no grad: the whole head below is linear up to the ReLU -- folded projections and one kernel (the per-map
+            # coin flips of the stock path are not drawn: in eval mode they only choose between two identities)
+            return _dh.eval_decode(self, encoder_hidden_states)
         batch_size = encoder_hidden_states[-1].shape[0]
         size0 = encoder_hidden_states[0].shape[2:]
         feats = ()
