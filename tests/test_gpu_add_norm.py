@@ -1,4 +1,4 @@
-"""csrc/add_layernorm.hip: the residual add fused with the LayerNorm that follows it (vivim_amd/layernorm.py: add_layer_norm_cm,
+"""csrc/layernorm.hip with the add: the residual add fused with the LayerNorm that follows it (vivim_amd/layernorm.py: add_layer_norm_cm,
 add_cm; MambaLayer(fused_add_norm=True)) against an fp64 reference built from the same rounded inputs."""
 import pytest
 import torch

@@ -36,7 +36,7 @@ int ssm_bwd_det_dispatch(const vivim_ssm_bwd_params&, void* det_ws, size_t det_w
 bool layernorm_dispatch(const vivim_layernorm_params&, bool bwd, hipStream_t);   // layernorm.hip
 size_t layernorm_bwd_workspace_bytes(const vivim_layernorm_params&);
 bool wgrad_nt_dispatch(const vivim_wgrad_nt_params&, hipStream_t);                 // wgrad.hip
-bool add_layernorm_dispatch(const vivim_add_layernorm_params&, bool bwd, hipStream_t);   // add_layernorm.hip
+bool add_layernorm_dispatch(const vivim_add_layernorm_params&, bool bwd, hipStream_t);   // layernorm.hip, with the residual add
 size_t add_layernorm_bwd_workspace_bytes(const vivim_add_layernorm_params&);
 size_t scan_fwd_workspace_bytes(const vivim_ssm_fwd_params&);
 bool seg_loss_dispatch(const vivim_seg_loss_params&, bool bwd, hipStream_t);       // seg_loss.hip

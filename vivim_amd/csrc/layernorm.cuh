@@ -1,6 +1,6 @@
-// layernorm.cuh -- what the channel-major LayerNorm kernels (layernorm.hip) and their residual-add variants
-// (add_layernorm.hip) share: the tile deal over the XCDs, the channel-major tile load, the per-token sum, the LDS sizes and
-// the host-side tile choice.
+// layernorm.cuh -- the pieces the channel-major LayerNorm family (layernorm.hip: plain, residual-add + norm, add alone) is
+// built from: the tile deal over the XCDs, the channel-major tile load, the token-major read and write, the rounding to x's
+// type, the per-token sum and the LDS sizes.
 #pragma once
 #include "common.cuh"
 
@@ -55,6 +55,51 @@ __device__ __forceinline__ void ln_load_cm(float* tile, const T* __restrict__ xb
     }
 }
 
+// v as x's type will hold it.  The fp32 sum is a value of its own (the empty asm): left alone, hipcc folds the f16 case into
+// v_fma_mixlo_f16, which rounds the exact fma straight to f16 -- one ulp away from "fp32, then x's type" (what torch's adds and
+// the bf16 path give) wherever the fp32 sum lands on an f16 midpoint, 3.4 % of the elements at s = 4 / 3.
+template <typename T> __device__ __forceinline__ float ln_round(float v) {
+    asm volatile("" : "+v"(v));
+    return to_f32<T>(from_f32<T>(v));
+}
+template <> __device__ __forceinline__ float ln_round<float>(float v) { return v; }
+
+// f(channel, token of the tile, value) for every element of the tile, read token-major: 64 consecutive channels of a token per
+// instruction, eight in flight; tokens beyond the row's end (>= nt) come as 0
+template <typename T, int TT, typename F>
+__device__ __forceinline__ void ln_read_tm(const T* __restrict__ base, int64_t token_stride, int C, int nt, int lane, F&& f) {
+    int tt = 0, c = lane;
+    while (c >= C) { c -= C; ++tt; }
+    while (tt < TT) {
+        float v[8];
+        int ct[8], tk[8];
+#pragma unroll
+        for (int i = 0; i < 8; ++i) {
+            ct[i] = c; tk[i] = tt;
+            v[i] = tt < nt ? to_f32<T>(base[(int64_t)tt * token_stride + c]) : 0.0f;
+            c += kWave;
+            while (c >= C) { c -= C; ++tt; }
+        }
+#pragma unroll
+        for (int i = 0; i < 8; ++i)
+            if (tk[i] < TT) f(ct[i], tk[i], v[i]);
+    }
+}
+
+// out[tt][c] = f(channel, token) for the tile's nt tokens, written token-major: 64 consecutive channels of a token per instruction
+template <typename T, typename F>
+__device__ __forceinline__ void ln_write_tm(T* __restrict__ base, int64_t token_stride, int C, int nt, int lane, F&& f) {
+    int tt = 0, c = lane;
+    while (c >= C) { c -= C; ++tt; }
+    const int iters = (nt * C + kWave - 1) / kWave;
+#pragma unroll 4
+    for (int k = 0; k < iters; ++k) {
+        if (tt < nt) base[(int64_t)tt * token_stride + c] = from_f32<T>(f(c, tt));
+        c += kWave;
+        while (c >= C) { c -= C; ++tt; }
+    }
+}
+
 // sum over the 64 / TT channel parts of a token (lanes t, t + TT, t + 2 TT, ...)
 template <int TT>
 __device__ __forceinline__ float ln_parts_sum(float v) {
@@ -65,9 +110,5 @@ __device__ __forceinline__ float ln_parts_sum(float v) {
 
 static inline size_t ln_fwd_smem(int C, int TT) { return ((size_t)C * (TT + 1) + 2 * TT + 2 * C) * sizeof(float); }
 static inline size_t ln_bwd_smem(int C, int TT) { return ((size_t)2 * C * (TT + 1) + 4 * TT + C) * sizeof(float); }
-
-// layernorm.hip
-int layernorm_tile_tokens(const vivim_layernorm_params& p);       // from batch, seqlen, channels, itype (and VIVIM_LN_TT)
-void ln_reduce_launch(const float* ws, int ntiles, int C, float* dweight, float* dbias, hipStream_t stream);
 
 }  // namespace vivim

@@ -1,5 +1,7 @@
 // layernorm.hip -- LayerNorm over the channel axis of a CHANNEL-major token tensor, forward and backward (SURVEY.md 8f row 4:
-// the two nn.LayerNorms around the Mamba call, modeling/vivim.py:155-156).
+// the two nn.LayerNorms around the Mamba call, modeling/vivim.py:155-156), and the same kernels with the residual add of
+// MambaLayer in front of the norm (include/vivim_hip.h: vivim_add_layernorm_params).  One kernel family: ADD and NORM are
+// template parameters, the plain LayerNorm is the instantiation without the add.
 //
 // MambaLayer holds its activations as (B, C, nf*H*W) and hands the norm the transposed VIEW (B, L, C) with strides
 // (C*L, 1, L) (modeling/vivim.py:151-155).  The ATen path first makes that view contiguous (one full copy kernel) and then
@@ -18,12 +20,22 @@
 // TT is 32, 16 or 8: the largest that still gives a couple of thousand waves and fits the LDS.  Waves are numbered so that the
 // tiles an XCD works on are neighbours in memory (pieces shorter than a 128-byte line meet in one L2).
 // HBM-bound: forward reads x once and writes y once; backward reads dy and x once and writes dx once.
-#include "layernorm.cuh"     // the tile deal, the channel-major load and the sizes shared with add_layernorm.hip
+//
+// ADD: a branch (out_proj of the Mamba block, fc2 of the Mlp) comes back TOKEN-major, so `x + drop_path(branch)` is a DropPath
+// multiply plus a mixed-layout strided add, and the norm reads the sum straight back from HBM.  Here the wave adds s[b] * branch,
+// read as 64 consecutive channels of a token, to its tile of x, rounds once to x's type IN the tile, writes x_new channel-major
+// and y = LayerNorm(x_new as stored) from it.  The backward needs no more LDS than the plain one's two tiles: it computes dx in
+// place of the dy tile while it sweeps channel-major (adding dres, the gradient that reaches x_new from later in the network,
+// and writing dx), then writes the same tile out token-major as dbranch = s[b] * dx.
+// Add-only mode (no weight, NORM = false): the forward stops after x_new, the backward is the scaled transposed copy of dres.
+#include "layernorm.cuh"
 
 namespace vivim {
 
-template <typename TI, typename TO, int TT>
-__global__ void __launch_bounds__(kWave) ln_cm_fwd_kernel(const vivim_layernorm_params p, const int ntiles, const int tpb) {
+// TI: x / x_new, TB: branch, TO: y.  ADD = false: the plain LayerNorm of x (the host passes it as vivim_add_layernorm_params
+// with x_new = x; TB is TI).  NORM = false: the add alone.
+template <typename TI, typename TB, typename TO, int TT, bool ADD, bool NORM>
+__global__ void __launch_bounds__(kWave) ln_cm_fwd_kernel(const vivim_add_layernorm_params p, const int ntiles, const int tpb) {
     extern __shared__ __attribute__((aligned(16))) float ln_smem[];
     constexpr int PAD = TT + 1, P = kWave / TT;
     const int C = p.channels, L = p.seqlen, lane = threadIdx.x;
@@ -32,12 +44,40 @@ __global__ void __launch_bounds__(kWave) ln_cm_fwd_kernel(const vivim_layernorm_
     float* tile = ln_smem;                             // [C][TT + 1]
     float* stat = tile + C * PAD;                      // [2][TT]: mean, rstd
     float* gb = stat + 2 * TT;                         // [2][C]: weight, bias (a global load per output element would serialise the store loop)
-    for (int c = lane; c < C; c += kWave) {
-        gb[c] = p.weight ? static_cast<const float*>(p.weight)[c] : 1.0f;
-        gb[C + c] = p.bias ? static_cast<const float*>(p.bias)[c] : 0.0f;
+    if constexpr (NORM) {
+        for (int c = lane; c < C; c += kWave) {        // a null weight: gain 1 in the plain mode (with the add it selects NORM = false)
+            gb[c] = ADD || p.weight ? static_cast<const float*>(p.weight)[c] : 1.0f;
+            gb[C + c] = p.bias ? static_cast<const float*>(p.bias)[c] : 0.0f;
+        }
     }
+    const float s = ADD && p.scale ? static_cast<const float*>(p.scale)[b] : 1.0f;
+    const int nt = min(TT, L - t0);
     ln_load_cm<TI, TT>(tile, static_cast<const TI*>(p.x) + (int64_t)b * p.x_batch_stride, p.x_c_stride, C, t0, L, lane);
     wave_lds_fence();
+    if constexpr (ADD) {
+        // x_new = x + s * branch: one fma in f32, rounded once to x's type; the tile holds x_new as it will be stored
+        ln_read_tm<TB, TT>(static_cast<const TB*>(p.branch) + (int64_t)b * p.branch_batch_stride + (int64_t)t0 * p.branch_token_stride,
+                           p.branch_token_stride, C, nt, lane, [&](int c, int tt, float v) {
+                               float* q = tile + c * PAD + tt;
+                               *q = ln_round<TI>(fmaf(s, v, *q));
+                           });
+        wave_lds_fence();
+        // x_new: channel-major, 16-byte vectors along the tokens
+        constexpr int E = LnVec<TI>::E;
+        constexpr int VPR = TT / E;
+        TI* __restrict__ xnb = static_cast<TI*>(p.x_new) + (int64_t)b * p.x_new_batch_stride;
+        const int nvec = C * VPR;
+        for (int idx = lane; idx < nvec; idx += kWave) {
+            const int c = idx / VPR, v = idx - c * VPR;
+            const int tg = t0 + v * E;
+            if (tg >= L) continue;
+            typename LnVec<TI>::U u;
+#pragma unroll
+            for (int e = 0; e < E; ++e) u.e[e] = from_f32<TI>(tile[c * PAD + v * E + e]);
+            *reinterpret_cast<typename LnVec<TI>::vec*>(xnb + (int64_t)c * p.x_new_c_stride + tg) = u.v;
+        }
+    }
+    if constexpr (!NORM) return;
     const int t = lane % TT, part = lane / TT;
     const float pivot = tile[t];                       // channel 0 of the token
     float s1 = 0.0f, s2 = 0.0f;
@@ -62,61 +102,36 @@ __global__ void __launch_bounds__(kWave) ln_cm_fwd_kernel(const vivim_layernorm_
         }
     }
     wave_lds_fence();
-    TO* __restrict__ yb = static_cast<TO*>(p.y) + (int64_t)b * p.y_batch_stride + (int64_t)t0 * p.y_token_stride;
-    const int nt = min(TT, L - t0);
-    int tt = 0, c = lane;                              // token-major: the wave writes 64 consecutive channels of one token
-    while (c >= C) { c -= C; ++tt; }
-    const int iters = (nt * C + kWave - 1) / kWave;
-#pragma unroll 4
-    for (int k = 0; k < iters; ++k) {
-        if (tt < nt) {
-            const float v = (tile[c * PAD + tt] - stat[tt]) * stat[TT + tt] * gb[c] + gb[C + c];
-            yb[(int64_t)tt * p.y_token_stride + c] = from_f32<TO>(v);
-        }
-        c += kWave;
-        while (c >= C) { c -= C; ++tt; }
-    }
+    ln_write_tm<TO>(static_cast<TO*>(p.y) + (int64_t)b * p.y_batch_stride + (int64_t)t0 * p.y_token_stride, p.y_token_stride, C, nt, lane,
+                    [&](int c, int tt) { return (tile[c * PAD + tt] - stat[tt]) * stat[TT + tt] * gb[c] + gb[C + c]; });
 }
 
-template <typename TI, typename TO, int TT>
-__global__ void __launch_bounds__(kWave) ln_cm_bwd_kernel(const vivim_layernorm_params p, const int ntiles, const int tpb) {
+template <typename TI, typename TB, typename TO, int TT, bool ADD>
+__global__ void __launch_bounds__(kWave) ln_cm_bwd_kernel(const vivim_add_layernorm_params p, const int ntiles, const int tpb) {
     extern __shared__ __attribute__((aligned(16))) float ln_smem[];
     constexpr int PAD = TT + 1, P = kWave / TT;
     const int C = p.channels, L = p.seqlen, lane = threadIdx.x;
     int b, t0;
     if (!ln_tile(ntiles, tpb, TT, b, t0)) return;
     const int tile_id = b * tpb + t0 / TT;
-    float* xt = ln_smem;                               // [C][TT + 1]: x
-    float* gt = xt + C * PAD;                          // [C][TT + 1]: dy
+    float* xt = ln_smem;                               // [C][TT + 1]: x_new
+    float* gt = xt + C * PAD;                          // [C][TT + 1]: dy, then (ADD) dx
     float* stat = gt + C * PAD;                        // [4][TT]: mean, rstd, S1 / C, S2 / C
     float* gam = stat + 4 * TT;                        // [C]: weight
     const int nt = min(TT, L - t0);
-    for (int c = lane; c < C; c += kWave) gam[c] = p.weight ? static_cast<const float*>(p.weight)[c] : 1.0f;
-    // dy: token-major reads (64 consecutive channels of a token per instruction), transposed into the tile; eight in flight
-    {
-        const TO* __restrict__ dyb = static_cast<const TO*>(p.dy) + (int64_t)b * p.y_batch_stride + (int64_t)t0 * p.y_token_stride;
-        int tt = 0, c = lane;
-        while (c >= C) { c -= C; ++tt; }
-        while (tt < TT) {
-            float v[8];
-            int ct[8], tk[8];
-#pragma unroll
-            for (int i = 0; i < 8; ++i) {
-                ct[i] = c; tk[i] = tt;
-                v[i] = tt < nt ? to_f32<TO>(dyb[(int64_t)tt * p.y_token_stride + c]) : 0.0f;
-                c += kWave;
-                while (c >= C) { c -= C; ++tt; }
-            }
-#pragma unroll
-            for (int i = 0; i < 8; ++i)
-                if (tk[i] < TT) gt[ct[i] * PAD + tk[i]] = v[i];
-        }
+    for (int c = lane; c < C; c += kWave) gam[c] = ADD || p.weight ? static_cast<const float*>(p.weight)[c] : 1.0f;
+    if (!ADD || p.dy) {                                // with the add, dy may be absent (only dres arrives)
+        ln_read_tm<TO, TT>(static_cast<const TO*>(p.dy) + (int64_t)b * p.y_batch_stride + (int64_t)t0 * p.y_token_stride, p.y_token_stride,
+                           C, nt, lane, [&](int c, int tt, float v) { gt[c * PAD + tt] = v; });
+    } else {
+        for (int i = lane; i < C * PAD; i += kWave) gt[i] = 0.0f;
     }
-    ln_load_cm<TI, TT>(xt, static_cast<const TI*>(p.x) + (int64_t)b * p.x_batch_stride, p.x_c_stride, C, t0, L, lane);
+    ln_load_cm<TI, TT>(xt, static_cast<const TI*>(p.x_new) + (int64_t)b * p.x_new_batch_stride, p.x_new_c_stride, C, t0, L, lane);
     const int t = lane % TT, part = lane / TT;
     const bool tok = t0 + t < L;
     const float mean = tok ? static_cast<const float*>(p.mean)[(int64_t)b * L + t0 + t] : 0.0f;
     const float rstd = tok ? static_cast<const float*>(p.rstd)[(int64_t)b * L + t0 + t] : 0.0f;
+    const float s = ADD && p.scale ? static_cast<const float*>(p.scale)[b] : 1.0f;
     wave_lds_fence();
     // per-token S1 = sum_c dy gamma, S2 = sum_c dy gamma xhat
     float s1 = 0.0f, s2 = 0.0f;
@@ -150,27 +165,87 @@ __global__ void __launch_bounds__(kWave) ln_cm_bwd_kernel(const vivim_layernorm_
             row[c] = dw;
             row[C + c] = db;
         }
+        if constexpr (ADD) wave_lds_fence();           // the sweep below overwrites the dy tile
     }
-    // dx = rstd * (dy gamma - S1 / C - xhat S2 / C), channel-major with 16-byte vectors along the tokens
+    // dx = rstd * (dy gamma - S1 / C - xhat S2 / C) (+ dres), channel-major with 16-byte vectors along the tokens.  The one place
+    // where the two modes keep separate bodies: the add wants eight dres vectors per lane in flight, and the same batched sweep with
+    // the dres loads compiled out costs the plain mode registers and occupancy (fp32 TT 32: 92 -> 98 VGPRs, 5 -> 4 waves; bf16 -> f32
+    // TT 16: 72 -> 91, 7 -> 5), so that one goes vector by vector.
     constexpr int E = LnVec<TI>::E;
     constexpr int VPR = TT / E;
     TI* __restrict__ dxb = static_cast<TI*>(p.dx) + (int64_t)b * p.dx_batch_stride;
     const int nvec = C * VPR;
-    for (int idx = lane; idx < nvec; idx += kWave) {
-        const int c = idx / VPR, v = idx - c * VPR;
-        const int tg = t0 + v * E;
-        if (tg >= L) continue;
-        const float g = gam[c];
-        typename LnVec<TI>::U u;
+    if constexpr (!ADD) {
+        for (int idx = lane; idx < nvec; idx += kWave) {
+            const int c = idx / VPR, v = idx - c * VPR;
+            const int tg = t0 + v * E;
+            if (tg >= L) continue;
+            const float g = gam[c];
+            typename LnVec<TI>::U u;
 #pragma unroll
-        for (int e = 0; e < E; ++e) {
-            const int k = v * E + e;
-            const float r = stat[TT + k];
-            const float xh = (xt[c * PAD + k] - stat[k]) * r;
-            u.e[e] = from_f32<TI>(r * (gt[c * PAD + k] * g - stat[2 * TT + k] - xh * stat[3 * TT + k]));
+            for (int e = 0; e < E; ++e) {
+                const int k = v * E + e;
+                const float r = stat[TT + k];
+                const float xh = (xt[c * PAD + k] - stat[k]) * r;
+                u.e[e] = from_f32<TI>(r * (gt[c * PAD + k] * g - stat[2 * TT + k] - xh * stat[3 * TT + k]));
+            }
+            *reinterpret_cast<typename LnVec<TI>::vec*>(dxb + (int64_t)c * p.dx_c_stride + tg) = u.v;
         }
-        *reinterpret_cast<typename LnVec<TI>::vec*>(dxb + (int64_t)c * p.dx_c_stride + tg) = u.v;
+    } else {
+        // the f32 value replaces dy in the tile for the token-major pass below
+        const TI* __restrict__ drb = static_cast<const TI*>(p.dres) + (int64_t)b * p.dres_batch_stride;
+        const bool has_res = p.dres != nullptr;
+        for (int base = 0; base < nvec; base += kWave * 8) {
+            typename LnVec<TI>::U r8[8];
+#pragma unroll
+            for (int i = 0; i < 8; ++i) {
+                const int idx = base + i * kWave + lane;
+                const int c = idx / VPR, v = idx - c * VPR;
+                const int tg = t0 + v * E;
+                r8[i].v = typename LnVec<TI>::vec{0u, 0u, 0u, 0u};
+                if (has_res && idx < nvec && tg < L) r8[i].v = *reinterpret_cast<const typename LnVec<TI>::vec*>(drb + (int64_t)c * p.dres_c_stride + tg);
+            }
+#pragma unroll
+            for (int i = 0; i < 8; ++i) {
+                const int idx = base + i * kWave + lane;
+                const int c = idx / VPR, v = idx - c * VPR;
+                const int tg = t0 + v * E;
+                if (idx >= nvec || tg >= L) continue;
+                const float g = gam[c];
+                typename LnVec<TI>::U u;
+#pragma unroll
+                for (int e = 0; e < E; ++e) {
+                    const int k = v * E + e;
+                    const float r = stat[TT + k];
+                    const float xh = (xt[c * PAD + k] - stat[k]) * r;
+                    const float d = r * (gt[c * PAD + k] * g - stat[2 * TT + k] - xh * stat[3 * TT + k]) + to_f32<TI>(r8[i].e[e]);
+                    gt[c * PAD + k] = d;
+                    u.e[e] = from_f32<TI>(d);
+                }
+                *reinterpret_cast<typename LnVec<TI>::vec*>(dxb + (int64_t)c * p.dx_c_stride + tg) = u.v;
+            }
+        }
+        if (!p.dbranch) return;
+        wave_lds_fence();
+        ln_write_tm<TB>(static_cast<TB*>(p.dbranch) + (int64_t)b * p.dbranch_batch_stride + (int64_t)t0 * p.dbranch_token_stride,
+                        p.dbranch_token_stride, C, nt, lane, [&](int c, int tt) { return s * gt[c * PAD + tt]; });
     }
+}
+
+// add-only backward: dbranch[b][t][c] = s[b] * dres[b][c][t]
+template <typename TI, typename TB, int TT>
+__global__ void __launch_bounds__(kWave) add_cm_bwd_kernel(const vivim_add_layernorm_params p, const int ntiles, const int tpb) {
+    extern __shared__ __attribute__((aligned(16))) float ln_smem[];
+    constexpr int PAD = TT + 1;
+    const int C = p.channels, L = p.seqlen, lane = threadIdx.x;
+    int b, t0;
+    if (!ln_tile(ntiles, tpb, TT, b, t0)) return;
+    float* tile = ln_smem;                             // [C][TT + 1]
+    const float s = p.scale ? static_cast<const float*>(p.scale)[b] : 1.0f;
+    ln_load_cm<TI, TT>(tile, static_cast<const TI*>(p.dres) + (int64_t)b * p.dres_batch_stride, p.dres_c_stride, C, t0, L, lane);
+    wave_lds_fence();
+    ln_write_tm<TB>(static_cast<TB*>(p.dbranch) + (int64_t)b * p.dbranch_batch_stride + (int64_t)t0 * p.dbranch_token_stride,
+                    p.dbranch_token_stride, C, min(TT, L - t0), lane, [&](int c, int tt) { return s * tile[c * PAD + tt]; });
 }
 
 // dweight[c] += sum over the workspace rows of column c, dbias[c] += ... of column C + c.  grid (ceil(2C / 64), row groups),
@@ -194,8 +269,8 @@ __global__ void __launch_bounds__(256) ln_reduce_kernel(const float* __restrict_
 }
 
 // tokens per wave: the largest of 32 / 16 / 8 that leaves a couple of thousand waves and at most 64 KB of LDS per wave
-// (VIVIM_LN_TT overrides, for the tests and for tuning)
-int layernorm_tile_tokens(const vivim_layernorm_params& p) {
+// (VIVIM_LN_TT overrides, for the tests and for tuning); from batch, seqlen, channels and itype
+static int layernorm_tile_tokens(const vivim_add_layernorm_params& p) {
     const char* e = getenv("VIVIM_LN_TT");
     const int forced = e ? atoi(e) : 0;
     const int vec = p.itype == VIVIM_F32 ? 4 : 8;
@@ -206,51 +281,97 @@ int layernorm_tile_tokens(const vivim_layernorm_params& p) {
     }
     return 8;
 }
-size_t layernorm_bwd_workspace_bytes(const vivim_layernorm_params& p) {
+size_t add_layernorm_bwd_workspace_bytes(const vivim_add_layernorm_params& p) {
     const int TT = layernorm_tile_tokens(p);
     return (size_t)p.batch * ((p.seqlen + TT - 1) / TT) * 2 * p.channels * sizeof(float);
 }
 
-void ln_reduce_launch(const float* ws, int ntiles, int C, float* dweight, float* dbias, hipStream_t stream) {
+static void ln_reduce_launch(const float* ws, int ntiles, int C, float* dweight, float* dbias, hipStream_t stream) {
     hipLaunchKernelGGL(ln_reduce_kernel, dim3((2 * C + kWave - 1) / kWave, std::min(128, std::max(1, ntiles / 32))), dim3(256), 0, stream,
                        ws, ntiles, C, dweight, dbias);
 }
 
-template <typename TI, typename TO, int TT>
-static void ln_launch_tt(const vivim_layernorm_params& p, bool bwd, hipStream_t stream) {
+template <typename TI, typename TB, typename TO, int TT, bool ADD, bool NORM>
+static void ln_launch_tt(const vivim_add_layernorm_params& p, bool bwd, hipStream_t stream) {
     const int tpb = (p.seqlen + TT - 1) / TT, ntiles = p.batch * tpb;
     const dim3 grid((unsigned)((ntiles + 7) / 8 * 8)), block(kWave);
-    if (!bwd) {
-        hipLaunchKernelGGL((ln_cm_fwd_kernel<TI, TO, TT>), grid, block, ln_fwd_smem(p.channels, TT), stream, p, ntiles, tpb);
-        return;
+    if constexpr (!NORM) {                             // the add alone: one tile, no statistics
+        const size_t smem = (size_t)p.channels * (TT + 1) * sizeof(float);
+        if (!bwd) hipLaunchKernelGGL((ln_cm_fwd_kernel<TI, TB, TO, TT, ADD, false>), grid, block, smem, stream, p, ntiles, tpb);
+        else hipLaunchKernelGGL((add_cm_bwd_kernel<TI, TB, TT>), grid, block, smem, stream, p, ntiles, tpb);
+    } else if (!bwd) {
+        hipLaunchKernelGGL((ln_cm_fwd_kernel<TI, TB, TO, TT, ADD, true>), grid, block, ln_fwd_smem(p.channels, TT), stream, p, ntiles, tpb);
+    } else {
+        hipLaunchKernelGGL((ln_cm_bwd_kernel<TI, TB, TO, TT, ADD>), grid, block, ln_bwd_smem(p.channels, TT), stream, p, ntiles, tpb);
+        if (p.workspace && (p.dweight || p.dbias))
+            ln_reduce_launch(static_cast<const float*>(p.workspace), ntiles, p.channels, static_cast<float*>(p.dweight),
+                             static_cast<float*>(p.dbias), stream);
     }
-    hipLaunchKernelGGL((ln_cm_bwd_kernel<TI, TO, TT>), grid, block, ln_bwd_smem(p.channels, TT), stream, p, ntiles, tpb);
-    if (p.workspace && (p.dweight || p.dbias))
-        ln_reduce_launch(static_cast<const float*>(p.workspace), ntiles, p.channels, static_cast<float*>(p.dweight),
-                         static_cast<float*>(p.dbias), stream);
 }
-template <typename TI, typename TO>
-static void ln_launch(const vivim_layernorm_params& p, bool bwd, hipStream_t stream) {
+template <typename TI, typename TB, typename TO, bool ADD, bool NORM>
+static void ln_launch(const vivim_add_layernorm_params& p, bool bwd, hipStream_t stream) {
     switch (layernorm_tile_tokens(p)) {
-        case 32: ln_launch_tt<TI, TO, 32>(p, bwd, stream); break;
-        case 16: ln_launch_tt<TI, TO, 16>(p, bwd, stream); break;
-        default: ln_launch_tt<TI, TO, 8>(p, bwd, stream); break;
+        case 32: ln_launch_tt<TI, TB, TO, 32, ADD, NORM>(p, bwd, stream); break;
+        case 16: ln_launch_tt<TI, TB, TO, 16, ADD, NORM>(p, bwd, stream); break;
+        default: ln_launch_tt<TI, TB, TO, 8, ADD, NORM>(p, bwd, stream); break;
     }
 }
 
+template <typename TI, typename TB>
+static bool aln_pair(const vivim_add_layernorm_params& p, bool bwd, hipStream_t stream) {
+    if (!p.weight) { ln_launch<TI, TB, TI, true, false>(p, bwd, stream); return true; }   // add-only: no y, its type does not matter
+    // the output / incoming-gradient side is f32 (what autocast makes of layer_norm) or the input's own type
+    if (p.otype == VIVIM_F32) { ln_launch<TI, TB, float, true, true>(p, bwd, stream); return true; }
+    if (p.otype == p.itype) { ln_launch<TI, TB, TI, true, true>(p, bwd, stream); return true; }
+    return false;
+}
+
+bool add_layernorm_dispatch(const vivim_add_layernorm_params& p, bool bwd, hipStream_t stream) {
+    if (p.channels > kLnMaxC) return false;
+    if (p.btype == p.itype) {
+        switch (p.itype) {
+            case VIVIM_F32: return aln_pair<float, float>(p, bwd, stream);
+            case VIVIM_F16: return aln_pair<f16_t, f16_t>(p, bwd, stream);
+            case VIVIM_BF16: return aln_pair<bf16_t, bf16_t>(p, bwd, stream);
+        }
+    } else if (p.itype == VIVIM_F32) {                 // an f32 residual stream with an autocast branch
+        switch (p.btype) {
+            case VIVIM_F16: return aln_pair<float, f16_t>(p, bwd, stream);
+            case VIVIM_BF16: return aln_pair<float, bf16_t>(p, bwd, stream);
+        }
+    }
+    return false;
+}
+
+// The plain LayerNorm as the family sees it: x_new is x itself, no branch, no dres, no dbranch.
+static vivim_add_layernorm_params ln_plain(const vivim_layernorm_params& p) {
+    vivim_add_layernorm_params q = {};
+    q.batch = p.batch; q.seqlen = p.seqlen; q.channels = p.channels;
+    q.itype = q.btype = p.itype; q.otype = p.otype; q.eps = p.eps;
+    q.x_batch_stride = q.x_new_batch_stride = p.x_batch_stride; q.x_c_stride = q.x_new_c_stride = p.x_c_stride;
+    q.y_batch_stride = p.y_batch_stride; q.y_token_stride = p.y_token_stride;
+    q.dx_batch_stride = p.dx_batch_stride; q.dx_c_stride = p.dx_c_stride;
+    q.x = p.x; q.x_new = const_cast<void*>(p.x); q.weight = p.weight; q.bias = p.bias;
+    q.y = p.y; q.mean = p.mean; q.rstd = p.rstd;
+    q.dy = p.dy; q.dx = p.dx; q.dweight = p.dweight; q.dbias = p.dbias; q.workspace = p.workspace;
+    return q;
+}
+size_t layernorm_bwd_workspace_bytes(const vivim_layernorm_params& p) { return add_layernorm_bwd_workspace_bytes(ln_plain(p)); }
+
 bool layernorm_dispatch(const vivim_layernorm_params& p, bool bwd, hipStream_t stream) {
     if (p.channels > kLnMaxC) return false;
+    const vivim_add_layernorm_params q = ln_plain(p);
     // the output / incoming-gradient side is f32 (what autocast makes of layer_norm) or the input's own type
     if (p.otype == VIVIM_F32) {
         switch (p.itype) {
-            case VIVIM_F32: ln_launch<float, float>(p, bwd, stream); return true;
-            case VIVIM_F16: ln_launch<f16_t, float>(p, bwd, stream); return true;
-            case VIVIM_BF16: ln_launch<bf16_t, float>(p, bwd, stream); return true;
+            case VIVIM_F32: ln_launch<float, float, float, false, true>(q, bwd, stream); return true;
+            case VIVIM_F16: ln_launch<f16_t, f16_t, float, false, true>(q, bwd, stream); return true;
+            case VIVIM_BF16: ln_launch<bf16_t, bf16_t, float, false, true>(q, bwd, stream); return true;
         }
     } else if (p.otype == p.itype) {
         switch (p.itype) {
-            case VIVIM_F16: ln_launch<f16_t, f16_t>(p, bwd, stream); return true;
-            case VIVIM_BF16: ln_launch<bf16_t, bf16_t>(p, bwd, stream); return true;
+            case VIVIM_F16: ln_launch<f16_t, f16_t, f16_t, false, true>(q, bwd, stream); return true;
+            case VIVIM_BF16: ln_launch<bf16_t, bf16_t, bf16_t, false, true>(q, bwd, stream); return true;
         }
     }
     return false;

@@ -7,7 +7,7 @@ The transpose the ATen path does with a copy kernel in front of its row kernel i
 `supported(x, weight)` says whether the fast path applies; the caller falls back to F.layer_norm otherwise (other layouts:
 the ATen kernel is already the right one for token-major rows).
 
-The residual add in front of the norm, fused with it (csrc/add_layernorm.hip; vivim_add_layernorm_params) -- MambaLayer's
+The residual add in front of the norm, fused with it (the same kernel family; vivim_add_layernorm_params) -- MambaLayer's
 `x + drop_path(branch)` followed by norm2, and the layer's last add (MambaLayer(fused_add_norm=True)):
 
     add_layer_norm_cm(x, branch, weight, bias, eps, scale=None) -> (x_new, y)
@@ -52,17 +52,44 @@ def _params(x, out_dtype, eps):
     return P
 
 
+def _norm_forward(P, x, weight, bias, out_dtype):
+    """The norm's side of a forward call (the same fields in both structs): a fresh y and the mean / rstd pair."""
+    B, L, C = x.shape
+    y = _lib.empty((B, L, C), out_dtype, x.device)
+    stats = _lib.empty((2, B, L), torch.float32, x.device)                  # mean, rstd
+    P.y_batch_stride, P.y_token_stride = L * C, C
+    P.weight, P.bias = weight.data_ptr(), ptr(bias)
+    P.y, P.mean = y.data_ptr(), stats.data_ptr()
+    P.rstd = P.mean + 4 * B * L
+    return y, stats
+
+
+def _norm_backward(P, query, dy, weight, stats, out_dtype, has_bias):
+    """The norm's side of a backward call (P has its sizes and types): weight, mean / rstd and, where dy arrives, dy in the
+    kernel's dtype and layout, zeroed dweight / dbias and the workspace `query` sizes.  -> (dwb, what must outlive the launch)"""
+    B, L, C = P.batch, P.seqlen, P.channels
+    P.weight, P.mean = weight.data_ptr(), stats.data_ptr()
+    P.rstd = P.mean + 4 * B * L
+    if dy is None:
+        return None, None
+    if dy.dtype != out_dtype:
+        dy = dy.to(out_dtype)
+    if dy.stride(2) != 1 or dy.stride(1) < C:
+        dy = dy.contiguous()
+    P.dy, P.y_batch_stride, P.y_token_stride = dy.data_ptr(), dy.stride(0), dy.stride(1)
+    dwb = _lib.zeros(2 * C, stats.device)                                   # dweight, dbias: one zero fill
+    P.dweight = dwb.data_ptr()
+    P.dbias = P.dweight + 4 * C if has_bias else None
+    ws = _lib.workspace(query, P, stats.device)[1]
+    P.workspace = ptr(ws)                                                   # per-tile dweight / dbias partial sums
+    return dwb, (dy, ws)
+
+
 class _LayerNormCM(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, weight, bias, eps, out_dtype):
-        B, L, C = x.shape
-        y = _lib.empty((B, L, C), out_dtype, x.device)
-        stats = _lib.empty((2, B, L), torch.float32, x.device)              # mean, rstd
         P = _params(x, out_dtype, eps)
-        P.y_batch_stride, P.y_token_stride = L * C, C
-        P.weight, P.bias = weight.data_ptr(), ptr(bias)
-        P.y, P.mean = y.data_ptr(), stats.data_ptr()
-        P.rstd = P.mean + 4 * B * L
+        y, stats = _norm_forward(P, x, weight, bias, out_dtype)
         _lib.launch("vivim_layernorm_cm_fwd", P, x.device)
         ctx.save_for_backward(x, weight, stats)
         ctx.eps, ctx.has_bias, ctx.out_dtype = eps, bias is not None, out_dtype
@@ -72,22 +99,11 @@ class _LayerNormCM(torch.autograd.Function):
     def backward(ctx, dy):
         x, weight, stats = ctx.saved_tensors
         B, L, C = x.shape
-        if dy.dtype != ctx.out_dtype:
-            dy = dy.to(ctx.out_dtype)
-        if dy.stride(2) != 1 or dy.stride(1) < C:
-            dy = dy.contiguous()
         # dx in x's own layout: (B, C, L) memory seen as (B, L, C)
         dx = _lib.empty((B, C, L), x.dtype, x.device).transpose(1, 2)
-        dwb = _lib.zeros(2 * C, x.device)                                    # dweight, dbias: one zero fill
         P = _params(x, ctx.out_dtype, ctx.eps)
-        P.y_batch_stride, P.y_token_stride = dy.stride(0), dy.stride(1)
-        P.dx_batch_stride, P.dx_c_stride = C * L, L
-        P.weight, P.mean = weight.data_ptr(), stats.data_ptr()
-        P.rstd = P.mean + 4 * B * L
-        P.dy, P.dx, P.dweight = dy.data_ptr(), dx.data_ptr(), dwb.data_ptr()
-        P.dbias = P.dweight + 4 * C if ctx.has_bias else None
-        ws = _lib.workspace("vivim_layernorm_bwd_workspace_bytes", P, x.device)[1]
-        P.workspace = ptr(ws)                                                # per-tile dweight / dbias partial sums
+        P.dx, P.dx_batch_stride, P.dx_c_stride = dx.data_ptr(), C * L, L
+        dwb, _alive = _norm_backward(P, "vivim_layernorm_bwd_workspace_bytes", dy, weight, stats, ctx.out_dtype, ctx.has_bias)
         _lib.launch("vivim_layernorm_cm_bwd", P, x.device)
         return dx, dwb[:C], (dwb[C:] if ctx.has_bias else None), None, None
 
@@ -157,16 +173,10 @@ def _add_forward(x, branch, scale, P):
 class _AddLayerNormCM(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, branch, weight, bias, scale, eps, out_dtype):
-        B, L, C = x.shape
         P = _add_params(x, branch, scale)
         P.otype, P.eps = ITYPE[out_dtype], eps
         x_new = _add_forward(x, branch, scale, P)
-        y = _lib.empty((B, L, C), out_dtype, x.device)
-        stats = _lib.empty((2, B, L), torch.float32, x.device)              # mean, rstd
-        P.y_batch_stride, P.y_token_stride = L * C, C
-        P.weight, P.bias = weight.data_ptr(), ptr(bias)
-        P.y, P.mean = y.data_ptr(), stats.data_ptr()
-        P.rstd = P.mean + 4 * B * L
+        y, stats = _norm_forward(P, x, weight, bias, out_dtype)
         _lib.launch("vivim_add_layernorm_cm_fwd", P, x.device)
         ctx.save_for_backward(x_new, weight, stats, scale)
         ctx.eps, ctx.has_bias, ctx.out_dtype, ctx.branch_dtype = eps, bias is not None, out_dtype, branch.dtype
@@ -184,20 +194,8 @@ class _AddLayerNormCM(torch.autograd.Function):
         P.itype, P.btype, P.otype = ITYPE[x_new.dtype], ITYPE[ctx.branch_dtype], ITYPE[ctx.out_dtype]
         P.scale = ptr(scale)
         P.x_new_batch_stride, P.x_new_c_stride = x_new.stride(0), x_new.stride(2)
-        P.x_new, P.weight, P.mean = x_new.data_ptr(), weight.data_ptr(), stats.data_ptr()
-        P.rstd = P.mean + 4 * B * L
-        dwb = None
-        if dy is not None:
-            if dy.dtype != ctx.out_dtype:
-                dy = dy.to(ctx.out_dtype)
-            if dy.stride(2) != 1 or dy.stride(1) < C:
-                dy = dy.contiguous()
-            P.dy, P.y_batch_stride, P.y_token_stride = dy.data_ptr(), dy.stride(0), dy.stride(1)
-            dwb = _lib.zeros(2 * C, x_new.device)                            # dweight, dbias: one zero fill
-            P.dweight = dwb.data_ptr()
-            P.dbias = P.dweight + 4 * C if ctx.has_bias else None
-            ws = _lib.workspace("vivim_add_layernorm_bwd_workspace_bytes", P, x_new.device)[1]
-            P.workspace = ptr(ws)                                            # per-tile dweight / dbias partial sums
+        P.x_new = x_new.data_ptr()
+        dwb, _alive = _norm_backward(P, "vivim_add_layernorm_bwd_workspace_bytes", dy, weight, stats, ctx.out_dtype, ctx.has_bias)
         if dres is not None:
             dres = _as_cm(dres, x_new)
             P.dres, P.dres_batch_stride, P.dres_c_stride = dres.data_ptr(), dres.stride(0), dres.stride(2)

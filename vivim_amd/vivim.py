@@ -175,7 +175,7 @@ class MambaLayer(nn.Module):
         x_flat = x.reshape(B, C, nf * H * W).transpose(-1, -2)          # frame-major tokens (vivim.py:151-153)
         branch = self.mamba(self._norm(self.norm1, x_flat), nframes=nf)
         if self.fused_add_norm and self._add_norm_applies(x_flat, branch, self.norm2.weight):
-            # residual add + norm2 as one kernel (csrc/add_layernorm.hip): the channel-major stream and the token-major branch
+            # residual add + norm2 as one kernel (csrc/layernorm.hip, ADD): the channel-major stream and the token-major branch
             # meet in the kernel's LDS tile, DropPath is a per-sample factor inside it, and the sum is normalised before it
             # leaves the chip; the layer's last add is the same kernel without the norm, and its result is (B, C, L) memory
             # again, so the final reshape is a view
