@@ -447,6 +447,42 @@ typedef struct {
     void *logits;
 } vivim_decode_head_params;
 
+/* ---- LayerNorm over the channels of TOKEN-major rows (csrc/token_layernorm.hip; the SegFormer blocks' norms, opt-in in Vivim) --
+ * x is `rows` rows of `channels` elements, channel stride 1, one row stride (a (B, N, C) tensor whose leading dimensions collapse).
+ *   forward : y[r][c] = (x[r][c] - mean[r]) * rstd[r] * weight[c] + bias[c]     fp32, rounded once to otype
+ *             mean[r] = sum_c x[r][c] / channels, rstd[r] = 1 / sqrt(sum_c (x[r][c] - mean[r])^2 / channels + eps): the mean first,
+ *             then the squared differences from it, on the row held in registers (never E[x^2] - mean^2).  mean / rstd are
+ *             written when both are given; both NULL is the call no backward follows.
+ *   backward: dx[r][c] = rstd[r] * (g - mean_c(g) - xhat * mean_c(g * xhat)), g = dy * weight, xhat = (x - mean) * rstd, in itype;
+ *             dweight[c] = sum_r dy * xhat, dbias[c] = sum_r dy: WRITTEN, not added to (no pre-zeroing), either may be NULL.
+ * Determinism: no atomics.  Every workgroup of the backward stores its partial dweight / dbias sums into its own slot of
+ * `workspace` and a second kernel on the same stream adds the slots in slot order, so the results are a function of the inputs
+ * and the shape alone.  Workspace, required when dweight or dbias is given (vivim_token_layernorm_bwd_workspace_bytes):
+ *     min(1024, ceil(rows / 4)) slots * 2 * channels * sizeof(float)  bytes, 4-byte aligned; contents undefined afterwards.
+ * Types: x, dx: itype; y, dy: otype; weight, bias, mean, rstd, dweight, dbias: fp32.  otype == itype, otype == VIVIM_F32, or
+ * itype == VIVIM_F32 with an f16 / bf16 otype (the consumer's autocast cast done in the kernel); any other pair and
+ * channels > 1024 return VIVIM_ERR_UNSUPPORTED.  Row strides are in elements and at least `channels`.
+ * 16-byte accesses when channels is a whole number of 16-byte pieces of itype and every address and row stride of the call is
+ * 16-byte aligned; element accesses otherwise (element-size alignment is then the only requirement).
+ * This struct has no vivim_sizeof row: the caller sets struct_bytes = sizeof(vivim_token_layernorm_params) and any other value
+ * is refused with VIVIM_ERR_INVALID. */
+typedef struct {
+    int32_t struct_bytes;                            /* sizeof(vivim_token_layernorm_params) as the caller compiled it */
+    int32_t rows, channels;
+    int32_t itype, otype;                            /* vivim_dtype_t */
+    float eps;
+    int64_t x_row_stride, y_row_stride;              /* in elements; channel stride 1 everywhere */
+    int64_t dy_row_stride, dx_row_stride;
+    const void *x;
+    const void *weight, *bias;                       /* (channels) f32; bias NULL is 0 */
+    void *y;                                         /* forward output */
+    void *mean, *rstd;                               /* (rows) f32: written by the forward (or both NULL), read by the backward */
+    const void *dy;                                  /* backward input */
+    void *dx;                                        /* backward outputs */
+    void *dweight, *dbias;                           /* (channels) f32, written; or NULL */
+    void *workspace;                                 /* backward scratch (see above) */
+} vivim_token_layernorm_params;
+
 int vivim_abi_version(void);
 const char *vivim_last_error(void);
 
@@ -510,6 +546,9 @@ size_t vivim_seg_metrics_workspace_bytes(const vivim_seg_metrics_params *p);   /
 int vivim_upsample_bilinear2d_fwd(const vivim_upsample_params *p, void *stream);   /* reads x, writes y */
 int vivim_upsample_bilinear2d_bwd(const vivim_upsample_params *p, void *stream);   /* reads dy, writes dx */
 int vivim_decode_head_fwd(const vivim_decode_head_params *p, void *stream);        /* reads the maps, writes logits */
+int vivim_token_layernorm_fwd(const vivim_token_layernorm_params *p, void *stream);   /* reads x, writes y (+ mean, rstd) */
+int vivim_token_layernorm_bwd(const vivim_token_layernorm_params *p, void *stream);   /* writes dx (+ dweight, dbias) */
+size_t vivim_token_layernorm_bwd_workspace_bytes(const vivim_token_layernorm_params *p);   /* from rows, channels; 0 on bad sizes */
 
 /* Deterministic backward (for torch.use_deterministic_algorithms).  Same parameters, checks and results as
  * vivim_selective_scan_bwd, and the same kernel family, but every gradient that the default call adds up across

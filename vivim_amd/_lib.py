@@ -165,6 +165,13 @@ class DecodeHeadParams(ctypes.Structure):
                 + [(n, vp) for n in ("bias", "w_out", "b_out", "logits")])
 
 
+class TokenLayerNormParams(ctypes.Structure):
+    """As DecodeHeadParams: no vivim_sizeof row, not in STRUCTS, its sizeof stated in struct_bytes."""
+    _fields_ = ([(n, i32) for n in ("struct_bytes", "rows", "channels", "itype", "otype")] + [("eps", ctypes.c_float)]
+                + [(n, i64) for n in ("x_row_stride", "y_row_stride", "dy_row_stride", "dx_row_stride")]
+                + [(n, vp) for n in ("x", "weight", "bias", "y", "mean", "rstd", "dy", "dx", "dweight", "dbias", "workspace")])
+
+
 # The structs in vivim_sizeof order.
 STRUCTS = (SsmFwdParams, SsmBwdParams, ConvFwdParams, ConvBwdParams, DwConvParams, DwConvWgradParams, DirParams,
            ConvUpdateParams, StateUpdateParams, LayerNormParams, WgradNtParams, AddLayerNormParams, SegLossParams,
@@ -226,6 +233,9 @@ ENTRY_POINTS = {
     "vivim_upsample_bilinear2d_fwd": _kernel(UpsampleParams),
     "vivim_upsample_bilinear2d_bwd": _kernel(UpsampleParams),
     "vivim_decode_head_fwd": Entry(None, (ctypes.POINTER(DecodeHeadParams),), True, _int),
+    "vivim_token_layernorm_fwd": Entry(None, (ctypes.POINTER(TokenLayerNormParams),), True, _int),
+    "vivim_token_layernorm_bwd": Entry(None, (ctypes.POINTER(TokenLayerNormParams),), True, _int),
+    "vivim_token_layernorm_bwd_workspace_bytes": Entry(None, (ctypes.POINTER(TokenLayerNormParams),), False, _size),
 }
 EXPORTS = tuple(ENTRY_POINTS)
 
@@ -284,6 +294,12 @@ def algorithmic_bytes(name, P):
             return n * (2 * _ISIZE[P.itype] + _ISIZE[P.btype] + _ISIZE[P.otype]) + 8 * P.batch * P.seqlen + 8 * P.channels
         res = (_ISIZE[P.itype] if P.dres else 0) + (_ISIZE[P.otype] if P.dy else 0) + (_ISIZE[P.btype] if P.dbranch else 0)
         return n * (2 * _ISIZE[P.itype] + res) + 8 * P.batch * P.seqlen + 12 * P.channels   # x_new, dx + what is present
+    if name.startswith("vivim_token_layernorm"):                        # x, y + mean, rstd | x, dy, dx + mean, rstd, weight + dweight, dbias
+        n = P.rows * P.channels
+        stats = 8 * P.rows if P.mean else 0
+        if name.endswith("fwd"):
+            return n * (_ISIZE[P.itype] + _ISIZE[P.otype]) + stats
+        return n * (2 * _ISIZE[P.itype] + _ISIZE[P.otype]) + stats + 12 * P.channels
     if name.startswith("vivim_decode_head"):                            # the maps once, the logits once, bias + w_out + b_out
         px = sum(P.map_h[s] * P.map_w[s] for s in range(P.n_maps))
         return (P.batch * (px * P.hidden + P.classes * P.out_h * P.out_w) * _ISIZE[P.itype]

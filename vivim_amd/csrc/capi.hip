@@ -48,6 +48,9 @@ int64_t upsample_blocks(const vivim_upsample_params&, bool bwd);
 bool decode_head_dispatch(const vivim_decode_head_params&, hipStream_t);          // decode_head.hip
 int64_t decode_head_blocks(const vivim_decode_head_params&);
 int decode_head_max_hidden();
+bool token_layernorm_dispatch(const vivim_token_layernorm_params&, bool bwd, hipStream_t);   // token_layernorm.hip
+bool token_layernorm_pair_ok(int itype, int otype);
+size_t token_layernorm_bwd_workspace_bytes(const vivim_token_layernorm_params&);
 }  // namespace vivim
 
 static thread_local char g_err[512] = "";
@@ -639,6 +642,65 @@ int vivim_decode_head_fwd(const vivim_decode_head_params* p, void* stream) {
     if (!vivim::decode_head_dispatch(*p, as_stream(stream)))
         return fail(VIVIM_ERR_UNSUPPORTED, "decode_head_fwd not implemented for type %d", p->itype);
     return after_launch("decode_head_fwd");
+}
+
+// every refusal the forward and the backward of the token-major LayerNorm share, before any launch
+static int check_token_layernorm(const vivim_token_layernorm_params* p, const char* fn) {
+    VCHECK(p != nullptr);
+    if (p->struct_bytes != (int32_t)sizeof(vivim_token_layernorm_params))
+        return fail(VIVIM_ERR_INVALID, "%s: struct_bytes = %d, this library's vivim_token_layernorm_params has %zu", fn, p->struct_bytes,
+                    sizeof(vivim_token_layernorm_params));
+    VCHECK(dtype_ok(p->itype) && dtype_ok(p->otype));
+    VCHECK(p->rows > 0);
+    if (p->channels < 1)
+        return fail(VIVIM_ERR_INVALID, "%s: channels = %d: a row has at least one channel", fn, p->channels);
+    if (p->channels > 1024)
+        return fail(VIVIM_ERR_UNSUPPORTED, "%s: channels = %d: a row of more than 1024 channels does not fit the lanes' registers", fn,
+                    p->channels);
+    if (!vivim::token_layernorm_pair_ok(p->itype, p->otype))
+        return fail(VIVIM_ERR_UNSUPPORTED, "%s: input type %d with output type %d is not built (the same type, an f32 output, or an f32 input)",
+                    fn, p->itype, p->otype);
+    VCHECK(p->x != nullptr && aligned(p->x, p->itype == VIVIM_F32 ? 4 : 2));
+    VCHECK(p->weight != nullptr && aligned(p->weight, 4));
+    if (p->x_row_stride < p->channels)
+        return fail(VIVIM_ERR_INVALID, "%s: x_row_stride = %lld is less than the %d channels of a row", fn, (long long)p->x_row_stride,
+                    p->channels);
+    return VIVIM_OK;
+}
+
+int vivim_token_layernorm_fwd(const vivim_token_layernorm_params* p, void* stream) {
+    if (int rc = check_token_layernorm(p, "token_layernorm_fwd")) return rc;
+    VCHECK(p->y != nullptr && aligned(p->y, p->otype == VIVIM_F32 ? 4 : 2));
+    VCHECK(aligned(p->bias, 4));                                     // NULL: zeros
+    VCHECK((p->mean == nullptr) == (p->rstd == nullptr) && aligned(p->mean, 4) && aligned(p->rstd, 4));
+    if (p->y_row_stride < p->channels)
+        return fail(VIVIM_ERR_INVALID, "token_layernorm_fwd: y_row_stride = %lld is less than the %d channels of a row",
+                    (long long)p->y_row_stride, p->channels);
+    if (!vivim::token_layernorm_dispatch(*p, false, as_stream(stream)))
+        return fail(VIVIM_ERR_UNSUPPORTED, "token_layernorm_fwd not implemented for input type %d / output type %d", p->itype, p->otype);
+    return after_launch("token_layernorm_fwd");
+}
+
+size_t vivim_token_layernorm_bwd_workspace_bytes(const vivim_token_layernorm_params* p) {
+    return p && p->rows > 0 && p->channels > 0 && p->channels <= 1024 ? vivim::token_layernorm_bwd_workspace_bytes(*p) : 0;
+}
+
+int vivim_token_layernorm_bwd(const vivim_token_layernorm_params* p, void* stream) {
+    if (int rc = check_token_layernorm(p, "token_layernorm_bwd")) return rc;
+    VCHECK(p->dy != nullptr && aligned(p->dy, p->otype == VIVIM_F32 ? 4 : 2));
+    VCHECK(p->dx != nullptr && aligned(p->dx, p->itype == VIVIM_F32 ? 4 : 2));
+    VCHECK(p->mean != nullptr && p->rstd != nullptr && aligned(p->mean, 4) && aligned(p->rstd, 4));
+    VCHECK(aligned(p->dweight, 4) && aligned(p->dbias, 4) && aligned(p->workspace, 4));
+    if (p->dy_row_stride < p->channels || p->dx_row_stride < p->channels)
+        return fail(VIVIM_ERR_INVALID, "token_layernorm_bwd: dy_row_stride = %lld / dx_row_stride = %lld is less than the %d channels of a row",
+                    (long long)p->dy_row_stride, (long long)p->dx_row_stride, p->channels);
+    if ((p->dweight || p->dbias) && !p->workspace)
+        return fail(VIVIM_ERR_INVALID, "token_layernorm_bwd: dweight / dbias need the workspace (vivim_token_layernorm_bwd_workspace_bytes)");
+    vivim_token_layernorm_params q = *p;
+    if (!q.dweight && !q.dbias) q.workspace = nullptr;               // nothing to sum: the kernel stores no slot
+    if (!vivim::token_layernorm_dispatch(q, true, as_stream(stream)))
+        return fail(VIVIM_ERR_UNSUPPORTED, "token_layernorm_bwd not implemented for input type %d / output type %d", p->itype, p->otype);
+    return after_launch("token_layernorm_bwd");
 }
 
 }  // extern "C"

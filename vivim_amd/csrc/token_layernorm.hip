@@ -1,0 +1,295 @@
+// token_layernorm.hip -- LayerNorm over the channels of TOKEN-major rows, forward and backward (include/vivim_hip.h:
+// vivim_token_layernorm_params): the layernorm_before / layernorm_after of the SegFormer blocks, (B, N, C) contiguous with
+// C = 64 / 128 / 320 / 512.  layernorm.hip is the family for channel-major views; this is the one for rows.
+//
+// G = 8 / 16 / 32 / 64 lanes own one row, a wave carries 64 / G rows, and every lane holds K chunks of E consecutive channels of
+// its row in registers (chunk j of the row belongs to lane j % G, slot j / G: consecutive lanes read consecutive chunks).  E is
+// one 16-byte vector of x (4 f32, 8 f16 / bf16) when the channel count, the row strides and the addresses allow it -- at C = 64
+// bf16 one wave instruction then reads 8 rows = 1 KB contiguous -- and 1 otherwise (odd C, odd offsets): the same kernels with
+// lanes striding over the channels.  G, K and E are template parameters, so the row is never indexed at run time (no scratch).
+// Row sums are xor butterflies over the lane offsets < G: every lane of a row ends with the same bits.
+// Forward: the mean first, then the sum of squared differences from it on the row in registers (a row with a mean far from 0
+// loses nothing to cancellation), one rounding to the output type.
+// Backward: dx per row as above; a wave walks its row groups with its dweight / dbias partial sums in registers, folds them over
+// the lanes that own the same channels (offsets >= G), then over the workgroup's waves through LDS in wave order, and stores
+// ONE slot of the workspace.  A second kernel adds the slots in slot order and WRITES dweight / dbias: no atomics, no pre-zeroed
+// outputs, the same bits every run.
+// Rows past `rows` and chunks past C are neither read nor written.
+// HBM-bound: the forward reads x and writes y once; the backward reads x and dy and writes dx once.
+#include <algorithm>
+#include "common.cuh"
+
+namespace vivim {
+
+constexpr int kTlnWaves = 4;          // waves per workgroup
+constexpr int kTlnMaxSlots = 1024;    // workgroups of the backward = slots of its workspace
+constexpr int kTlnRedWaves = 16;      // waves of the slot-sum kernel: each adds a contiguous run of slots
+
+template <int G>
+__device__ __forceinline__ float tln_row_sum(float v) {
+#pragma unroll
+    for (int off = 1; off < G; off <<= 1) v += __shfl_xor(v, off, kWave);
+    return v;
+}
+
+template <typename T, int E>
+__device__ __forceinline__ void tln_load(const T* __restrict__ q, bool pred, float (&v)[E]) {
+    const RawK<T, E> r = load_vec<T, E>(q, pred);
+    unpack<T, E>(r, v);
+}
+
+template <typename TI, typename TO, int G, int K, int E>
+__global__ void __launch_bounds__(kWave * kTlnWaves) tln_fwd_kernel(const vivim_token_layernorm_params p) {
+    constexpr int RPW = kWave / G;
+    const int lane = threadIdx.x & (kWave - 1), wave = threadIdx.x / kWave;
+    const int sub = lane % G, rl = lane / G;
+    const int C = p.channels;
+    const float* __restrict__ wp = static_cast<const float*>(p.weight);
+    const float* __restrict__ bp = static_cast<const float*>(p.bias);
+    float w[K][E], b[K][E];
+    bool cv[K];
+#pragma unroll
+    for (int k = 0; k < K; ++k) {
+        const int c0 = (sub + k * G) * E;
+        cv[k] = c0 < C;                                  // E > 1: C is a whole number of chunks
+        tln_load<float, E>(wp + c0, cv[k], w[k]);
+        tln_load<float, E>(bp + c0, cv[k] && bp != nullptr, b[k]);
+    }
+    const float inv_c = 1.0f / (float)C;
+    const int64_t rows = p.rows, ngroups = (rows + RPW - 1) / RPW;
+    const TI* __restrict__ x = static_cast<const TI*>(p.x);
+    TO* __restrict__ y = static_cast<TO*>(p.y);
+    float* __restrict__ meanp = static_cast<float*>(p.mean);
+    float* __restrict__ rstdp = static_cast<float*>(p.rstd);
+    for (int64_t g = (int64_t)blockIdx.x * kTlnWaves + wave; g < ngroups; g += (int64_t)gridDim.x * kTlnWaves) {
+        const int64_t r = g * RPW + rl;
+        const bool ok = r < rows;
+        const TI* __restrict__ xr = x + r * p.x_row_stride;
+        float v[K][E];
+#pragma unroll
+        for (int k = 0; k < K; ++k) tln_load<TI, E>(xr + (sub + k * G) * E, ok && cv[k], v[k]);
+        float s = 0.0f;
+#pragma unroll
+        for (int k = 0; k < K; ++k)
+#pragma unroll
+            for (int e = 0; e < E; ++e) s += v[k][e];    // what was not loaded is 0
+        const float mean = tln_row_sum<G>(s) * inv_c;
+        float q = 0.0f;
+#pragma unroll
+        for (int k = 0; k < K; ++k)
+#pragma unroll
+            for (int e = 0; e < E; ++e) {
+                const float d = cv[k] ? v[k][e] - mean : 0.0f;
+                v[k][e] = d;
+                q = fmaf(d, d, q);
+            }
+        const float rstd = rsqrtf(tln_row_sum<G>(q) * inv_c + p.eps);
+        TO* __restrict__ yr = y + r * p.y_row_stride;
+#pragma unroll
+        for (int k = 0; k < K; ++k) {
+            float o[E];
+#pragma unroll
+            for (int e = 0; e < E; ++e) o[e] = fmaf(v[k][e] * rstd, w[k][e], b[k][e]);
+            store_vec<TO, E>(yr + (sub + k * G) * E, ok && cv[k], o);
+        }
+        if (sub == 0 && ok && meanp != nullptr) {
+            meanp[r] = mean;
+            rstdp[r] = rstd;
+        }
+    }
+}
+
+// grid: the slots.  Every workgroup stores its slot (zeros when it had no row), so the slot sum never reads what nobody wrote.
+template <typename TI, typename TO, int G, int K, int E>
+__global__ void __launch_bounds__(kWave * kTlnWaves) tln_bwd_kernel(const vivim_token_layernorm_params p) {
+    constexpr int RPW = kWave / G, CH = G * K * E;
+    __shared__ float red[kTlnWaves][2][CH];
+    const int lane = threadIdx.x & (kWave - 1), wave = threadIdx.x / kWave;
+    const int sub = lane % G, rl = lane / G;
+    const int C = p.channels;
+    const float* __restrict__ wp = static_cast<const float*>(p.weight);
+    float w[K][E], dw[K][E], db[K][E];
+    bool cv[K];
+#pragma unroll
+    for (int k = 0; k < K; ++k) {
+        const int c0 = (sub + k * G) * E;
+        cv[k] = c0 < C;
+        tln_load<float, E>(wp + c0, cv[k], w[k]);
+#pragma unroll
+        for (int e = 0; e < E; ++e) dw[k][e] = db[k][e] = 0.0f;
+    }
+    const float inv_c = 1.0f / (float)C;
+    const int64_t rows = p.rows, ngroups = (rows + RPW - 1) / RPW;
+    const TI* __restrict__ x = static_cast<const TI*>(p.x);
+    const TO* __restrict__ dy = static_cast<const TO*>(p.dy);
+    TI* __restrict__ dx = static_cast<TI*>(p.dx);
+    const float* __restrict__ meanp = static_cast<const float*>(p.mean);
+    const float* __restrict__ rstdp = static_cast<const float*>(p.rstd);
+    for (int64_t g = (int64_t)blockIdx.x * kTlnWaves + wave; g < ngroups; g += (int64_t)gridDim.x * kTlnWaves) {
+        const int64_t r = g * RPW + rl;
+        const bool ok = r < rows;
+        const TI* __restrict__ xr = x + r * p.x_row_stride;
+        const TO* __restrict__ gr = dy + r * p.dy_row_stride;
+        float v[K][E], gy[K][E];
+#pragma unroll
+        for (int k = 0; k < K; ++k) {
+            tln_load<TI, E>(xr + (sub + k * G) * E, ok && cv[k], v[k]);
+            tln_load<TO, E>(gr + (sub + k * G) * E, ok && cv[k], gy[k]);
+        }
+        const float mean = ok ? meanp[r] : 0.0f;
+        const float rstd = ok ? rstdp[r] : 0.0f;
+        float s1 = 0.0f, s2 = 0.0f;
+#pragma unroll
+        for (int k = 0; k < K; ++k)
+#pragma unroll
+            for (int e = 0; e < E; ++e) {
+                const float xh = cv[k] ? (v[k][e] - mean) * rstd : 0.0f;      // 0 for a row past the end too (rstd 0, x 0)
+                const float gw = gy[k][e] * w[k][e];
+                v[k][e] = xh;
+                s1 += gw;
+                s2 = fmaf(gw, xh, s2);
+                dw[k][e] = fmaf(gy[k][e], xh, dw[k][e]);
+                db[k][e] += gy[k][e];
+                gy[k][e] = gw;
+            }
+        s1 = tln_row_sum<G>(s1) * inv_c;
+        s2 = tln_row_sum<G>(s2) * inv_c;
+        TI* __restrict__ dxr = dx + r * p.dx_row_stride;
+#pragma unroll
+        for (int k = 0; k < K; ++k) {
+            float o[E];
+#pragma unroll
+            for (int e = 0; e < E; ++e) o[e] = rstd * (gy[k][e] - s1 - v[k][e] * s2);
+            store_vec<TI, E>(dxr + (sub + k * G) * E, ok && cv[k], o);
+        }
+    }
+    if (p.workspace == nullptr) return;                  // neither dweight nor dbias is wanted (the same in every thread)
+    // the rows of the wave that share a channel, then the workgroup's waves in wave order, then this workgroup's slot
+#pragma unroll
+    for (int k = 0; k < K; ++k)
+#pragma unroll
+        for (int e = 0; e < E; ++e) {
+#pragma unroll
+            for (int off = G; off < kWave; off <<= 1) {
+                dw[k][e] += __shfl_xor(dw[k][e], off, kWave);
+                db[k][e] += __shfl_xor(db[k][e], off, kWave);
+            }
+            if (rl == 0) {
+                red[wave][0][(sub + k * G) * E + e] = dw[k][e];
+                red[wave][1][(sub + k * G) * E + e] = db[k][e];
+            }
+        }
+    __syncthreads();
+    float* __restrict__ slot = static_cast<float*>(p.workspace) + (int64_t)blockIdx.x * 2 * C;
+    for (int i = threadIdx.x; i < 2 * CH; i += kWave * kTlnWaves) {
+        const int which = i / CH, c = i - which * CH;
+        if (c >= C) continue;
+        float s = red[0][which][c];
+#pragma unroll
+        for (int wv = 1; wv < kTlnWaves; ++wv) s += red[wv][which][c];
+        slot[which * C + c] = s;
+    }
+}
+
+// dweight[c] = sum over the slots of column c, dbias[c] = ... of column C + c, in slot order: wave w of a workgroup adds the w-th
+// run of ceil(nslots / 16) slots, wave 0 then adds the sixteen runs in run order.  grid: ceil(2C / 64), lane = column.
+__global__ void __launch_bounds__(kWave * kTlnRedWaves) tln_slot_sum_kernel(const float* __restrict__ ws, int nslots, int C,
+                                                                            float* __restrict__ dweight, float* __restrict__ dbias) {
+    __shared__ float part[kTlnRedWaves][kWave];
+    const int lane = threadIdx.x & (kWave - 1), wave = threadIdx.x / kWave;
+    const int col = blockIdx.x * kWave + lane;
+    const int per = (nslots + kTlnRedWaves - 1) / kTlnRedWaves;
+    const int s0 = wave * per, s1 = min(s0 + per, nslots);
+    float s = 0.0f;
+    if (col < 2 * C) {
+#pragma unroll 8
+        for (int i = s0; i < s1; ++i) s += ws[(int64_t)i * 2 * C + col];
+    }
+    part[wave][lane] = s;
+    __syncthreads();
+    if (wave != 0 || col >= 2 * C) return;
+    s = part[0][lane];
+#pragma unroll
+    for (int wv = 1; wv < kTlnRedWaves; ++wv) s += part[wv][lane];
+    if (col < C) { if (dweight) dweight[col] = s; }
+    else if (dbias) dbias[col - C] = s;
+}
+
+static int tln_isize(int t) { return t == VIVIM_F32 ? 4 : 2; }
+
+int token_layernorm_slots(const vivim_token_layernorm_params& p) {
+    return (int)std::min<int64_t>(kTlnMaxSlots, ((int64_t)p.rows + 3) / 4);
+}
+size_t token_layernorm_bwd_workspace_bytes(const vivim_token_layernorm_params& p) {
+    return (size_t)token_layernorm_slots(p) * 2 * p.channels * sizeof(float);
+}
+
+// 16-byte accesses: whole vectors of x per row, and every address and row stride of this call on a 16-byte boundary
+static bool tln_vector_path(const vivim_token_layernorm_params& p, bool bwd) {
+    const int isz = tln_isize(p.itype), osz = tln_isize(p.otype);
+    auto a16 = [](const void* q) { return reinterpret_cast<uintptr_t>(q) % 16 == 0; };
+    auto s16 = [](int64_t stride, int size) { return stride * size % 16 == 0; };
+    if (p.channels % (16 / isz) != 0 || !a16(p.x) || !s16(p.x_row_stride, isz) || !a16(p.weight)) return false;
+    if (!bwd) return a16(p.y) && s16(p.y_row_stride, osz) && a16(p.bias);
+    return a16(p.dy) && s16(p.dy_row_stride, osz) && a16(p.dx) && s16(p.dx_row_stride, isz);
+}
+
+template <typename TI, typename TO, int G, int K, int E>
+static void tln_launch_gk(const vivim_token_layernorm_params& p, bool bwd, hipStream_t stream) {
+    const int64_t ngroups = ((int64_t)p.rows + kWave / G - 1) / (kWave / G);
+    const int64_t wgs = (ngroups + kTlnWaves - 1) / kTlnWaves;
+    const dim3 block(kWave * kTlnWaves);
+    if (!bwd) {
+        hipLaunchKernelGGL((tln_fwd_kernel<TI, TO, G, K, E>), dim3((unsigned)std::min<int64_t>(wgs, 2048)), block, 0, stream, p);
+        return;
+    }
+    const int nslots = (int)std::min<int64_t>(wgs, token_layernorm_slots(p));     // wgs <= ceil(rows / 4)
+    hipLaunchKernelGGL((tln_bwd_kernel<TI, TO, G, K, E>), dim3((unsigned)nslots), block, 0, stream, p);
+    if (p.workspace != nullptr)
+        hipLaunchKernelGGL(tln_slot_sum_kernel, dim3((unsigned)((2 * p.channels + kWave - 1) / kWave)), dim3(kWave * kTlnRedWaves), 0, stream,
+                           static_cast<const float*>(p.workspace), nslots, p.channels, static_cast<float*>(p.dweight),
+                           static_cast<float*>(p.dbias));
+}
+
+// the smallest lane group, then the fewest chunks per lane, that hold a row
+template <typename TI, typename TO>
+static void tln_launch(const vivim_token_layernorm_params& p, bool bwd, hipStream_t stream) {
+    constexpr int EV = 16 / (int)sizeof(TI);
+    if (tln_vector_path(p, bwd)) {
+        const int n = p.channels / EV;
+        if (n <= 8) tln_launch_gk<TI, TO, 8, 1, EV>(p, bwd, stream);
+        else if (n <= 16) tln_launch_gk<TI, TO, 16, 1, EV>(p, bwd, stream);
+        else if (n <= 32) tln_launch_gk<TI, TO, 32, 1, EV>(p, bwd, stream);
+        else if (n <= 64) tln_launch_gk<TI, TO, 64, 1, EV>(p, bwd, stream);
+        else if (n <= 128) tln_launch_gk<TI, TO, 64, 2, EV>(p, bwd, stream);
+        else if constexpr (EV == 4) tln_launch_gk<TI, TO, 64, 4, EV>(p, bwd, stream);     // 1024 channels are 128 vectors of a 16-bit row
+    } else {
+        const int n = p.channels;
+        if (n <= 8) tln_launch_gk<TI, TO, 8, 1, 1>(p, bwd, stream);
+        else if (n <= 64) tln_launch_gk<TI, TO, 64, 1, 1>(p, bwd, stream);
+        else if (n <= 128) tln_launch_gk<TI, TO, 64, 2, 1>(p, bwd, stream);
+        else if (n <= 256) tln_launch_gk<TI, TO, 64, 4, 1>(p, bwd, stream);
+        else if (n <= 512) tln_launch_gk<TI, TO, 64, 8, 1>(p, bwd, stream);
+        else tln_launch_gk<TI, TO, 64, 16, 1>(p, bwd, stream);
+    }
+}
+
+bool token_layernorm_pair_ok(int itype, int otype) {
+    return otype == itype || otype == VIVIM_F32 || itype == VIVIM_F32;
+}
+
+bool token_layernorm_dispatch(const vivim_token_layernorm_params& p, bool bwd, hipStream_t stream) {
+    if (p.channels < 1 || p.channels > 1024 || !token_layernorm_pair_ok(p.itype, p.otype)) return false;
+    switch (p.itype * 3 + p.otype) {
+        case VIVIM_F32 * 3 + VIVIM_F32: tln_launch<float, float>(p, bwd, stream); return true;
+        case VIVIM_F32 * 3 + VIVIM_F16: tln_launch<float, f16_t>(p, bwd, stream); return true;
+        case VIVIM_F32 * 3 + VIVIM_BF16: tln_launch<float, bf16_t>(p, bwd, stream); return true;
+        case VIVIM_F16 * 3 + VIVIM_F32: tln_launch<f16_t, float>(p, bwd, stream); return true;
+        case VIVIM_F16 * 3 + VIVIM_F16: tln_launch<f16_t, f16_t>(p, bwd, stream); return true;
+        case VIVIM_BF16 * 3 + VIVIM_F32: tln_launch<bf16_t, float>(p, bwd, stream); return true;
+        case VIVIM_BF16 * 3 + VIVIM_BF16: tln_launch<bf16_t, bf16_t>(p, bwd, stream); return true;
+    }
+    return false;
+}
+
+}  // namespace vivim

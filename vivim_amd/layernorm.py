@@ -15,7 +15,15 @@ The residual add in front of the norm, fused with it (the same kernel family; vi
                                             f32 x: the autocast case); scale: (B,) f32 per-sample DropPath factor or None
                                             x_new = x + scale[b] * branch in x's dtype and layout, y = layer_norm(x_new)
     add_cm(x, branch, scale=None) -> x_new  the add alone
-`add_norm_supported(x, branch, weight)` says whether they apply; the caller keeps its composition of torch ops otherwise."""
+`add_norm_supported(x, branch, weight)` says whether they apply; the caller keeps its composition of torch ops otherwise.
+
+LayerNorm of TOKEN-major rows (csrc/token_layernorm.hip; vivim_token_layernorm_params) -- the norms of the SegFormer blocks:
+
+    layer_norm_tm(x, weight, bias, eps, out_dtype=None)   x: (..., C) with unit channel stride whose leading dimensions collapse to
+                                            one row stride -> x's shape, contiguous, in out_dtype (None: what F.layer_norm returns)
+`tm_supported(x, weight, bias)` says whether it applies.  No atomics: it also runs under torch.use_deterministic_algorithms."""
+import ctypes
+
 import torch
 
 from . import _lib
@@ -108,9 +116,11 @@ class _LayerNormCM(torch.autograd.Function):
         return dx, dwb[:C], (dwb[C:] if ctx.has_bias else None), None, None
 
 
-def layer_norm_cm(x, weight, bias, eps=1e-5):
-    """F.layer_norm(x, (C,), weight, bias, eps) for a channel-major x; output dtype as ATen's under the ambient autocast state."""
-    out_dtype = torch.float32 if torch.is_autocast_enabled() else x.dtype
+def layer_norm_cm(x, weight, bias, eps=1e-5, out_dtype=None):
+    """F.layer_norm(x, (C,), weight, bias, eps) for a channel-major x; output dtype as ATen's under the ambient autocast state,
+    or `out_dtype` (f32 or x's own: what the kernels write)."""
+    if out_dtype is None:
+        out_dtype = torch.float32 if torch.is_autocast_enabled() else x.dtype
     return _LayerNormCM.apply(x, weight, bias, eps, out_dtype)
 
 
@@ -251,3 +261,128 @@ def add_cm(x, branch, scale=None):
     """x + scale[:, None, None] * branch in x's dtype and (channel-major) layout."""
     _check_scale(scale, x)
     return _AddCM.apply(x, branch, scale)
+
+
+# ---- token-major rows (csrc/token_layernorm.hip)
+TM_MAX_C = 1024
+
+
+def _rows(x):
+    """(rows, row stride in elements) of x seen as rows of x.shape[-1] channels, or None when its leading dimensions do not
+    collapse to one stride."""
+    if x.dim() == 0 or x.numel() == 0:
+        return None
+    C = x.shape[-1]
+    if x.dim() == 1:
+        return 1, C
+    rows, stride = x.shape[-2], x.stride(-2)
+    for d in range(x.dim() - 3, -1, -1):
+        if x.shape[d] == 1:
+            continue
+        if rows == 1:
+            stride = x.stride(d)
+        elif x.stride(d) != stride * rows:
+            return None
+        rows *= x.shape[d]
+    return (rows, stride) if rows > 1 else (1, C)
+
+
+def tm_pair_ok(in_dtype, out_dtype):
+    """The (x, y) dtype pairs the kernels are built for: the same, an f32 output, or an f32 input (the autocast case)."""
+    return in_dtype in ITYPE and out_dtype in ITYPE and (out_dtype == in_dtype or torch.float32 in (in_dtype, out_dtype))
+
+
+def tm_rows(x, weight, bias=None):
+    """(rows, row stride) when layer_norm_tm takes these tensors, else None."""
+    if not (x.is_cuda and x.dtype in ITYPE and x.dim() >= 1 and x.stride(-1) == 1 and 1 <= x.shape[-1] <= TM_MAX_C):
+        return None
+    if weight is None:
+        return None
+    for t in (weight, bias):
+        if t is not None and not (t.dtype == torch.float32 and t.device == x.device and t.shape == (x.shape[-1],)
+                                  and t.is_contiguous()):
+            return None
+    rs = _rows(x)
+    return rs if rs is not None and rs[1] >= x.shape[-1] and rs[0] < 2 ** 31 else None
+
+
+def tm_supported(x, weight, bias=None):
+    """Whether layer_norm_tm takes these tensors.  True under torch.use_deterministic_algorithms as well: the kernels have no
+    atomics."""
+    return tm_rows(x, weight, bias) is not None
+
+
+def tm_worthwhile(x):
+    """Where the token-major kernels repay the host time of a Python autograd node (profiles/r08_layernorm_tm.txt): from 2^21
+    elements up.  The kernels of one forward + backward take 15-22 us of GPU time against ATen's 20-170 at the bench's four
+    stage shapes, but back to back the call costs 71-79 us of host time against ATen's 47-62, and the train step is
+    host-paced: only where ATen's own kernels take longer than that -- (61440, 64): 0.44-0.50x ATen's time per call; (15360, 128),
+    1.97 M elements: 1.07-1.81x -- does the call come out ahead."""
+    return x.numel() >= 1 << 21
+
+
+def tm_workspace_slots(rows):
+    """Slots of the backward's workspace, 2 * C floats each (include/vivim_hip.h; vivim_token_layernorm_bwd_workspace_bytes)."""
+    return min(1024, (rows + 3) // 4)
+
+
+class _LayerNormTM(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x, weight, bias, eps, out_dtype, need_stats, rs):
+        rows, C = rs[0], x.shape[-1]
+        P = _lib.TokenLayerNormParams()
+        P.struct_bytes = ctypes.sizeof(_lib.TokenLayerNormParams)
+        P.rows, P.channels, P.itype, P.otype, P.eps = rows, C, ITYPE[x.dtype], ITYPE[out_dtype], eps
+        P.x, P.x_row_stride = x.data_ptr(), rs[1]
+        y = _lib.empty(tuple(x.shape), out_dtype, x.device)
+        P.y, P.y_row_stride = y.data_ptr(), C
+        P.weight, P.bias = weight.data_ptr(), ptr(bias)
+        stats = None
+        if need_stats:                                                      # mean, rstd: only for a call a backward may follow
+            stats = _lib.empty((2, rows), torch.float32, x.device)
+            P.mean = stats.data_ptr()
+            P.rstd = P.mean + 4 * rows
+        _lib.launch("vivim_token_layernorm_fwd", P, x.device)
+        ctx.save_for_backward(x, weight, stats)
+        ctx.P, ctx.has_bias, ctx.out_dtype = P, bias is not None, out_dtype  # the backward fills in its own fields of P
+        return y
+
+    @staticmethod
+    def backward(ctx, dy):
+        x, weight, stats = ctx.saved_tensors
+        P, C = ctx.P, x.shape[-1]
+        if dy.dtype != ctx.out_dtype:
+            dy = dy.to(ctx.out_dtype)
+        rs = _rows(dy) if dy.stride(-1) == 1 else None
+        if rs is None or rs[1] < C:
+            dy = dy.contiguous()
+            rs = (P.rows, C)
+        dx = _lib.empty(tuple(x.shape), x.dtype, x.device)
+        P.dy, P.dy_row_stride, P.dx, P.dx_row_stride = dy.data_ptr(), rs[1], dx.data_ptr(), C
+        need_w, need_b = ctx.needs_input_grad[1], ctx.has_bias and ctx.needs_input_grad[2]
+        dwb = ws = None
+        P.dweight = P.dbias = P.workspace = None
+        if need_w or need_b:
+            dwb = _lib.empty((2, C), torch.float32, x.device)               # written by the slot sum: no zero fill
+            P.dweight = dwb.data_ptr() if need_w else None
+            P.dbias = dwb.data_ptr() + 4 * C if need_b else None
+            ws = _lib.empty((tm_workspace_slots(P.rows) * 2 * C,), torch.float32, x.device)   # one slot of partial sums per workgroup
+            P.workspace = ws.data_ptr()
+        _lib.launch("vivim_token_layernorm_bwd", P, x.device)
+        return dx, (dwb[0] if need_w else None), (dwb[1] if need_b else None), None, None, None, None
+
+
+def layer_norm_tm(x, weight, bias, eps=1e-5, out_dtype=None, rows=None):
+    """F.layer_norm(x, (C,), weight, bias, eps) for token-major rows.  out_dtype None: ATen's dtype -- f32 under autocast (layer_norm
+    is on its fp32 list), x's own otherwise; a 16-bit out_dtype with an f32 x is the cast the consumer's autocast would add, done
+    where the value is rounded anyway.  `rows`: what tm_rows(x, weight, bias) returned, from a caller that has just asked."""
+    if out_dtype is None:
+        out_dtype = torch.float32 if torch.is_autocast_enabled() else x.dtype
+    if rows is None:
+        rows = tm_rows(x, weight, bias)
+        if rows is None:
+            raise ValueError("layer_norm_tm: unsupported tensors (tm_supported)")
+    if not tm_pair_ok(x.dtype, out_dtype):
+        raise ValueError(f"layer_norm_tm: {x.dtype} rows with a {out_dtype} output are not built")
+    need_stats = torch.is_grad_enabled() and (x.requires_grad or weight.requires_grad or (bias is not None and bias.requires_grad))
+    return _LayerNormTM.apply(x, weight, bias, eps, out_dtype, need_stats, rows)

@@ -23,6 +23,11 @@ Differences from the reference, all additive:
     one kernel (csrc/decode_head.hip, decode_head.py): BatchNorm's running statistics, linear_fuse and the projections fold
     into four small matrices, the upsampling, the ReLU and `out` happen on chip.  Off by default, `VIVIM_NO_FUSED_HEAD=1` opts
     out again; training, grad mode and anything the kernel does not take run the stock path unchanged.
+  * `mamba_block(..., fast_backbone_layernorm=True)` (also on Vivim and train_step.build_model) takes the LayerNorms of the
+    SegFormer patch embeddings and blocks through the library, by the layout each is handed: a channel-major view (the
+    patch-embedding norms read `conv_out.flatten(2).transpose(1, 2)`) through csrc/layernorm.hip, token-major rows (the blocks'
+    layernorm_before / layernorm_after, and the sequence-reduction norms when their conv returns channels-last memory) through
+    csrc/token_layernorm.hip; under autocast the norms inside the blocks write the autocast dtype their consumers would cast to.  Same Parameters, state-dict keys unchanged; off by default, `VIVIM_NO_FUSED_LAYERNORM=1` opts out again.
   * timm is not required: DropPath / trunc_normal_ are the torch equivalents.
 """
 import math
@@ -255,6 +260,53 @@ def _swap_backbone_droppath(module):
     return n
 
 
+class _BackboneLayerNorm(nn.LayerNorm):
+    """nn.LayerNorm evaluated by the library where it has a kernel for the layout: a channel-major view (the patch-embedding norms
+    read `conv_out.flatten(2).transpose(1, 2)`; so do the sequence-reduction norms unless their conv returns channels-last memory)
+    takes csrc/layernorm.hip, token-major rows (the blocks' norms) take csrc/token_layernorm.hip, anything else ATen.  `low_precision_out`: every consumer of this norm is a Linear or a
+    Conv that autocast casts anyway, so under CUDA autocast the kernel rounds its fp32 result to the autocast dtype itself."""
+    low_precision_out = False
+
+    @classmethod
+    def adopt(cls, norm, low_precision_out):
+        """A _BackboneLayerNorm holding `norm`'s own Parameters."""
+        new = cls(norm.normalized_shape, eps=norm.eps, elementwise_affine=False)
+        new.elementwise_affine = norm.elementwise_affine
+        new.weight, new.bias = norm.weight, norm.bias
+        new.low_precision_out = low_precision_out
+        new.train(norm.training)
+        return new
+
+    def forward(self, x):
+        w, b = self.weight, self.bias
+        if os.environ.get("VIVIM_NO_FUSED_LAYERNORM") or w is None or len(self.normalized_shape) != 1:
+            return super().forward(x)
+        low = torch.get_autocast_dtype("cuda") if self.low_precision_out and x.is_cuda and torch.is_autocast_enabled("cuda") else None
+        if _ln.supported(x, w) and _ln.worthwhile(x):
+            # the cm kernels write f32 or x's own type: a 16-bit output only where x (the conv's output) already has it
+            return _ln.layer_norm_cm(x, w, b, self.eps, out_dtype=low if low == x.dtype else None)
+        rows = _ln.tm_rows(x, w, b)                      # tm_supported, keeping what it worked out
+        if rows is not None and _ln.tm_worthwhile(x):
+            return _ln.layer_norm_tm(x, w, b, self.eps, out_dtype=low if low is not None and _ln.tm_pair_ok(x.dtype, low) else None,
+                                     rows=rows)
+        return super().forward(x)
+
+
+def _swap_backbone_layernorm(encoder):
+    """Replace every nn.LayerNorm under the patch embeddings and the blocks of an _Encoder by a _BackboneLayerNorm with the same
+    Parameters (the stage norms in `encoder.layer_norm` are never called: left alone).  The norms inside the blocks --
+    layernorm_before / layernorm_after (layer_norm_1 / layer_norm_2 in transformers 4.x) and the sequence-reduction norm -- feed
+    Linears and Convs only: low_precision_out."""
+    n = 0
+    for root, low in ((encoder.patch_embeddings, False), (encoder.block, True)):
+        for m in root.modules():
+            for name, child in list(m.named_children()):
+                if isinstance(child, nn.LayerNorm) and not isinstance(child, _BackboneLayerNorm):
+                    setattr(m, name, _BackboneLayerNorm.adopt(child, low))
+                    n += 1
+    return n
+
+
 class _Encoder(nn.Module):
     """Holds the SegFormer encoder pieces under the reference's attribute names."""
 
@@ -276,12 +328,14 @@ class mamba_block(nn.Module):
 
     def __init__(self, backbone, in_chans=1, depths=[2, 2, 2, 2], dims=[64, 128, 320, 512],
                  drop_path_rate=0.0, layer_scale_init_value=1e-6, out_indices=[0, 1, 2, 3], mamba_kwargs=None,
-                 fast_backbone_dwconv=False):
+                 fast_backbone_dwconv=False, fast_backbone_layernorm=False):
         super().__init__()
         self.downsample_layers = _Encoder(backbone)
         if fast_backbone_dwconv:
             _swap_backbone_dwconv(self.downsample_layers)
             _swap_backbone_droppath(self.downsample_layers)
+        if fast_backbone_layernorm:
+            _swap_backbone_layernorm(self.downsample_layers)
         dp_rates = [x.item() for x in torch.linspace(0, drop_path_rate, sum(depths))]
         mk = mamba_kwargs or {}
         self.stages = nn.ModuleList()
@@ -335,7 +389,7 @@ class Vivim(nn.Module):
                  drop_path_rate=0.2, layer_scale_init_value=1e-6, hidden_size: int = 768, norm_name="instance",
                  conv_block: bool = True, res_block: bool = True, spatial_dims=2, with_edge=False,
                  dropout_rate=0.3, backbone=None, mamba_kwargs=None, fast_backbone_dwconv=False,
-                 fused_upsample=False, fused_decode_head=False) -> None:
+                 fused_upsample=False, fused_decode_head=False, fast_backbone_layernorm=False) -> None:
         super().__init__()
         self.fused_upsample = fused_upsample
         self.fused_decode_head = fused_decode_head
@@ -351,7 +405,8 @@ class Vivim(nn.Module):
             backbone = SegformerForSemanticSegmentation.from_pretrained("nvidia/segformer-b3-finetuned-ade-512-512")
         self.encoder = mamba_block(backbone, in_chans, depths=depths, dims=feat_size,
                                    drop_path_rate=drop_path_rate, mamba_kwargs=mamba_kwargs,
-                                   fast_backbone_dwconv=fast_backbone_dwconv)
+                                   fast_backbone_dwconv=fast_backbone_dwconv,
+                                   fast_backbone_layernorm=fast_backbone_layernorm)
         self.decoder = backbone.decode_head
         self.feature_dropout = nn.Dropout2d(dropout_rate)
         self.out = nn.Conv2d(768, out_chans, kernel_size=1)
