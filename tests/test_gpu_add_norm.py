@@ -1,9 +1,13 @@
 """csrc/layernorm.hip with the add: the residual add fused with the LayerNorm that follows it (vivim_amd/layernorm.py: add_layer_norm_cm,
-add_cm; MambaLayer(fused_add_norm=True)) against an fp64 reference built from the same rounded inputs."""
+add_cm; MambaLayer(fused_add_norm=True)) against an fp64 reference built from the same rounded inputs.  Per TOKEN (tests/fp64_bounds.py,
+the bounds of test_gpu_layernorm_tm.py): y fp32 < 2e-6 + 4 * 2^-24 * |mean_r| / std_r, 16-bit that plus one rounding (2^-8 bf16, 2^-11
+fp16); dx, dbranch fp32 < 1e-5, 16-bit one rounding more; dweight, dbias < 1e-4 over the vector; x_new within one rounding of the
+rounded reference; on benign, shifted, outlier-channel and constant rows of x_new.  And one Frobenius norm per tensor at larger sizes."""
 import pytest
 import torch
 import torch.nn.functional as F
 
+import fp64_bounds as fb
 from conftest import rel_err
 
 pytestmark = pytest.mark.gpu
@@ -112,6 +116,73 @@ def test_add_layer_norm_against_fp64(B, C, L, xdt, bdt, autocast, tile, cuda, mo
     if scale is not None:                                                          # the dropped sample, exactly
         z = B // 2
         assert torch.equal(x_new[z], x[z]) and not bool(br.grad[z].any())
+
+
+_FAM = {}
+
+
+def _family_inputs(B, C, L, xdt, bdt, ydt, family, scaled):
+    """CPU tensors: x holds the family's rows, the branch is small (zero for the constant rows) so that x_new = x + s * branch
+    keeps the pattern; the reference and the bounds see x_new as the op's contract rounds it."""
+    key = (B, C, L, xdt, bdt, ydt, family, scaled)
+    if key not in _FAM:
+        gen = torch.Generator().manual_seed(C + L)
+        x = fb.channel_major(fb.ln_family(family, B, C, L, gen).to(xdt))
+        br = (torch.randn(B, L, C, generator=gen) * (0.0 if family == "const" else 0.01)).to(bdt)
+        w, b = torch.randn(C, generator=gen) * 0.5 + 1.0, torch.randn(C, generator=gen) * 0.3
+        scale = None
+        if scaled:                                                                 # DropPath at keep 0.75; with B > 1 one sample dropped
+            scale = torch.full((B,), 1 / 0.75)
+            if B > 1:
+                scale[B // 2] = 0.0
+        gres = fb.channel_major(torch.randn(B, L, C, generator=gen).to(xdt))
+        gy = torch.randn(B, L, C, generator=gen).to(ydt)
+        ref = _reference(key, x, br, w, b, scale, gres, gy)
+        rows = ref["x_new"]
+        ref = dict(ref, mean=rows.mean(dim=-1), var=rows.var(dim=-1, unbiased=False))
+        _FAM[key] = (x, br, w, b, scale, gres, gy, ref)
+    return _FAM[key]
+
+
+@pytest.mark.parametrize("B,C,L", fb.LN_SHAPES)
+@pytest.mark.parametrize("xdt,bdt", PAIRS, ids=fb.name)
+@pytest.mark.parametrize("autocast", [False, True])
+@pytest.mark.parametrize("tile", [None, "8", "16", "32"])
+def test_add_layer_norm_per_token_against_fp64(B, C, L, xdt, bdt, autocast, tile, cuda, monkeypatch):
+    """Every input family of fp64_bounds.LN_FAMILIES as rows of x_new, with and without the per-sample scale, every tile length:
+    x_new, y, dx, dbranch, dweight, dbias and the saved mean / rstd against fp64, per token.  The add mode shares the plain mode's
+    statistics: with the one-sweep variance its fp32-output rows with the outlier in channel 0 missed y's bound in the same way."""
+    from vivim_amd import layernorm as ln
+    _set_tile(monkeypatch, tile)
+    ydt = F32 if autocast else xdt
+    to_cm = lambda t: t.transpose(1, 2).to(cuda).transpose(1, 2)                   # keeps the channel-major strides
+    for family in fb.LN_FAMILIES:
+        worst = {}
+        for scaled in (True, False):
+            x, br, w, b, scale, gres, gy, ref = _family_inputs(B, C, L, xdt, bdt, ydt, family, scaled)
+            xg, bg = to_cm(x).requires_grad_(True), br.to(cuda).requires_grad_(True)
+            wg, biasg = w.to(cuda).requires_grad_(True), b.to(cuda).requires_grad_(True)
+            sg = None if scale is None else scale.to(cuda)
+            assert ln.add_norm_supported(xg, bg, wg)
+            with torch.autocast("cuda", dtype=torch.bfloat16, enabled=autocast):
+                x_new, y = ln.add_layer_norm_cm(xg, bg, wg, biasg, 1e-5, sg)
+            assert y.dtype == ydt and y.is_contiguous() and x_new.dtype == xdt and x_new.stride() == xg.stride()
+            stats = y.grad_fn.saved_tensors[2]                                     # (2, B, L): mean, rstd as the backward will read them
+            torch.autograd.backward([x_new, y], [to_cm(gres), gy.to(cuda)])
+            tag = f"{family} {(B, C, L)} {fb.name(xdt)}+{fb.name(bdt)}->{fb.name(ydt)} TT={tile} scale={scaled}"
+            got = {"y": y, "dx": xg.grad, "dw": wg.grad, "db": biasg.grad, "mean": stats[0], "rstd": stats[1]}
+            extra = {"x_new": fb.row_ratio(x_new, ref["x_new"], 2e-6 if xdt == F32 else fb.U_ROUND[xdt]),
+                     "dbranch": fb.row_ratio(bg.grad, ref["dbranch"], fb.ln_grad_bound(bdt))}
+            print(f"{tag}: x_new={extra['x_new']:.3f} dbranch={extra['dbranch']:.3f} (err / bound)")
+            for k, v in extra.items():
+                worst[k] = max(worst.get(k, 0.0), v)
+            fb.ln_check(tag, got, ref, ref["x_new"], 1e-5, b, ydt, xdt, worst)
+            assert extra["x_new"] <= 1.0 and extra["dbranch"] <= 1.0, (tag, extra)
+            if scaled and B > 1:                                                   # the dropped sample, exactly
+                z = B // 2
+                assert torch.equal(x_new[z], xg[z]) and not bool(bg.grad[z].any())
+        for k, v in worst.items():
+            fb.log_ratio(f"add_layer_norm_cm TT={tile} {family} {k}", ydt if k == "y" else bdt if k == "dbranch" else xdt, (B, C, L), v)
 
 
 @pytest.mark.parametrize("xdt,bdt", PAIRS)

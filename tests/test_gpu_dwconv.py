@@ -1,11 +1,16 @@
 """GPU: token-major depthwise conv kernels (csrc/dwconv.hip) against the op they replace --
 the reference's nn.Conv3d(groups=C) on the transposed view (modeling/vivim.py:57-68) -- evaluated by PyTorch in
 fp32 (floating-point kernel: a torch fp32 reference is the oracle here).  Tolerance: rel-err <= 1e-3 for 16-bit
-I/O against the rounded fp32 result, <= 2e-5 for fp32 I/O."""
+I/O against the rounded fp32 result, <= 2e-5 for fp32 I/O.
+Per ELEMENT against the fp64 convolution (tests/fp64_bounds.py; rigorous for fp32 accumulation in any order, gamma_n = n 2^-24 /
+(1 - n 2^-24)): y, dx within gamma_28 * (sum_taps |w| |x| + |b|) + u_out * |ref| * (1 + 2^-20), u_out 2^-24 / 2^-11 / 2^-8 for fp32 /
+fp16 / bf16; dweight within gamma_(n + 64) * sum_tokens |dy| |x_shifted|, dbias within gamma_(n + 64) * sum |dy|, n = B D H W.
+The GELU-epilogue variants stay norm-wise: a per-element bound there needs an error model of erff / __expf nobody has measured."""
 import pytest
 import torch
 import torch.nn.functional as F
 
+import fp64_bounds as fb
 from conftest import rel_err
 
 pytestmark = pytest.mark.gpu
@@ -47,6 +52,62 @@ def test_dwconv_matches_torch(dtype, B, D, H, W, C, k3, cuda):
     assert rel_err(got[1].float(), x.grad.to(dtype).float()) < tol
     assert rel_err(got[2], w.grad) < (1e-4 if dtype == torch.float32 else 2e-3)
     assert rel_err(got[3], b.grad) < (1e-4 if dtype == torch.float32 else 2e-3)
+
+
+# (B, D, H, W, C) at the kernels' tiling edges: 4 positions along W per thread, 32 tiles per workgroup, 32 (fp32) or 64 (16-bit)
+# channels per forward block, 128 per weight-gradient block; B = 2 where a halo leaking into the neighbouring sample would show
+_EDGE = [(2, 1, 1, 1, 8), (2, 3, 2, 3, 8), (1, 2, 5, 7, 24), (2, 3, 3, 5, 72), (1, 1, 9, 4, 40), (2, 2, 3, 9, 136), (1, 5, 6, 6, 8)]
+_EDGE_CASES = ([s + (True, "plain") for s in _EDGE] + [s + (False, "plain") for s in _EDGE if s[1] == 1]
+               + [(2, 3, 3, 5, 72, True, "strided")])
+
+
+@pytest.mark.parametrize("dtype", [torch.float32, torch.bfloat16, torch.float16], ids=fb.name)
+@pytest.mark.parametrize("B,D,H,W,C,k3,layout", _EDGE_CASES)
+def test_dwconv_per_element_against_fp64(dtype, B, D, H, W, C, k3, layout, cuda):
+    """Forward, dx, dweight and dbias per element against fp64 within the rounding-error bound of fp32 accumulation, with and without
+    bias, the weight and bias gradients also through the fixed-order entry point (torch.use_deterministic_algorithms).  `strided`:
+    x a batch-strided view (three spare tokens behind each sample), which supported() accepts."""
+    from vivim_amd.dwconv import depthwise_conv_tokens, supported
+    gen = torch.Generator().manual_seed(B * 100 + C + D * H * W)
+    L = D * H * W
+    x = torch.randn(B, L, C, generator=gen).to(dtype)
+    w = torch.randn(*((C, 1, 3, 3, 3) if k3 else (C, 1, 3, 3)), generator=gen) * 0.3
+    bias = torch.randn(C, generator=gen)
+    dy = torch.randn(B, L, C, generator=gen).to(dtype)
+    if layout == "strided":
+        big = torch.full((B, L + 3, C), 1e4, dtype=dtype, device=cuda)               # a leak from behind a sample is far outside
+        big[:, :L] = x.to(cuda)
+        xdev = big[:, :L]
+        assert xdev.stride(0) == (L + 3) * C > L * C
+    else:
+        xdev = x.to(cuda)
+    worst = {}
+    for b in (bias, None):
+        ref, bound = fb.dwconv_reference(x, w, b, dy, (D, H, W))
+        for det in (False, True):
+            xg, wg = xdev.detach().requires_grad_(True), w.to(cuda).requires_grad_(True)
+            bg = None if b is None else b.to(cuda).requires_grad_(True)
+            assert supported(xg, wg)
+            torch.use_deterministic_algorithms(det)
+            try:
+                y = depthwise_conv_tokens(xg, wg, bg, D, H, W)
+                y.backward(dy.to(cuda))
+            finally:
+                torch.use_deterministic_algorithms(False)
+            assert y.dtype == dtype and y.shape == (B, L, C) and xg.grad.dtype == dtype
+            r = {"y": fb.elem_ratio(y, ref["y"], bound["y"]), "dx": fb.elem_ratio(xg.grad, ref["dx"], bound["dx"]),
+                 "dweight": fb.elem_ratio(wg.grad, ref["dw"], bound["dw"])}
+            if b is not None:
+                r["dbias"] = fb.elem_ratio(bg.grad, ref["db"], bound["db"])
+            print(f"{(B, D, H, W, C)} {fb.name(dtype)} k3={k3} {layout} bias={b is not None} det={det}: "
+                  + " ".join(f"{k}={v:.3f}" for k, v in r.items()) + " (err / bound)")
+            for k, v in r.items():
+                worst[k] = max(worst.get(k, 0.0), v)
+            assert all(v <= 1.0 for v in r.values()), r
+    if layout == "strided":
+        assert bool((big[:, L:] == 1e4).all())                                       # nothing written between the samples
+    for k, v in worst.items():
+        fb.log_ratio(f"dwconv {'3d' if k3 else '2d'} {layout} {k}", torch.float32 if k in ("dweight", "dbias") else dtype, (B, D, H, W, C), v)
 
 
 @pytest.mark.parametrize("dtype", [torch.float32, torch.bfloat16, torch.float16])

@@ -1,9 +1,13 @@
-"""csrc/layernorm.hip (the LayerNorms around the Mamba call, modeling/vivim.py:155-156) against
-torch.nn.functional.layer_norm in fp32 -- the operator the reference uses there; through the C ABI (vivim_amd/layernorm.py)."""
+"""csrc/layernorm.hip (the LayerNorms around the Mamba call, modeling/vivim.py:155-156) through the C ABI
+(vivim_amd/layernorm.py).  Per TOKEN against F.layer_norm in fp64 on the CPU (tests/fp64_bounds.py, the bounds of
+test_gpu_layernorm_tm.py): y fp32 < 2e-6 + 4 * 2^-24 * |mean_r| / std_r, 16-bit that plus one rounding (2^-8 bf16, 2^-11 fp16);
+dx fp32 < 1e-5, 16-bit one rounding more; dweight, dbias < 1e-4 over the vector; on benign, shifted, outlier-channel and constant rows.
+And, at the bench's sizes, one Frobenius norm against fp32 F.layer_norm -- the operator the reference uses there."""
 import pytest
 import torch
 import torch.nn.functional as F
 
+import fp64_bounds as fb
 from conftest import rel_err
 
 pytestmark = pytest.mark.gpu
@@ -50,6 +54,51 @@ def test_layer_norm_channel_major(B, C, L, dtype, autocast, tile, cuda, monkeypa
     gx_tol = 4e-3 if dtype != torch.float32 else 1e-5
     assert rel_err(x.grad.float(), x32.grad.to(dtype).float()) < gx_tol
     assert rel_err(w.grad, w32.grad) < 1e-4 and rel_err(b.grad, b32.grad) < 1e-4
+
+
+_REF = {}
+
+
+@pytest.mark.parametrize("B,C,L", fb.LN_SHAPES)
+@pytest.mark.parametrize("itype,otype", [(fb.F32, fb.F32), (fb.BF16, fb.BF16), (fb.F16, fb.F16), (fb.BF16, fb.F32), (fb.F16, fb.F32)],
+                         ids=fb.name)
+@pytest.mark.parametrize("tile", [None, "8", "16", "32"])
+def test_layer_norm_cm_per_token_against_fp64(B, C, L, itype, otype, tile, cuda, monkeypatch):
+    """Every input family of fp64_bounds.LN_FAMILIES, with and without bias, every tile length (the chain of the per-token sums is
+    C * TT / 64 long): y, dx, dweight, dbias and the saved mean / rstd against fp64, per token.  An fp32 y from 16-bit rows is the
+    autocast case.  Before the statistics took their second sweep over the tile, the fp32-output rows with the outlier in channel 0
+    missed y's bound at every C >= 64 (the figures are in profiles/r09_layernorm_stats.txt)."""
+    from vivim_amd import layernorm as ln
+    if tile is None:
+        monkeypatch.delenv("VIVIM_LN_TT", raising=False)
+    else:
+        monkeypatch.setenv("VIVIM_LN_TT", tile)
+    for family in fb.LN_FAMILIES:
+        worst = {}
+        for has_bias in (True, False):
+            key = (B, C, L, itype, otype, family, has_bias)
+            if key not in _REF:
+                gen = torch.Generator().manual_seed(C + L)
+                x = fb.channel_major(fb.ln_family(family, B, C, L, gen).to(itype))
+                w = torch.randn(C, generator=gen) * 0.5 + 1.0
+                b = torch.randn(C, generator=gen) * 0.3 if has_bias else None
+                dy = torch.randn(B, L, C, generator=gen).to(otype)
+                _REF[key] = (x, w, b, dy, fb.ln_reference(x, w, b, dy, 1e-5))
+            x, w, b, dy, ref = _REF[key]
+            xg = x.transpose(1, 2).to(cuda).transpose(1, 2).requires_grad_(True)
+            wg = w.to(cuda).requires_grad_(True)
+            bg = None if b is None else b.to(cuda).requires_grad_(True)
+            assert ln.supported(xg, wg) and xg.stride() == (C * L, 1, L)
+            y = ln.layer_norm_cm(xg, wg, bg, 1e-5, out_dtype=otype)
+            assert y.dtype == otype and y.shape == (B, L, C) and y.is_contiguous()
+            stats = y.grad_fn.saved_tensors[2]                                  # (2, B, L): mean, rstd as the backward will read them
+            y.backward(dy.to(cuda))
+            assert xg.grad.dtype == itype and xg.grad.stride() == xg.stride()
+            got = {"y": y, "dx": xg.grad, "dw": wg.grad, "db": None if bg is None else bg.grad, "mean": stats[0], "rstd": stats[1]}
+            fb.ln_check(f"{family} {(B, C, L)} {fb.name(itype)}->{fb.name(otype)} TT={tile} bias={has_bias}", got, ref, x, 1e-5, b,
+                        otype, itype, worst)
+        for k, v in worst.items():
+            fb.log_ratio(f"layer_norm_cm TT={tile} {family} {k}", otype if k == "y" else itype, (B, C, L), v)
 
 
 def test_layer_norm_no_bias_and_unsupported_layouts(cuda):

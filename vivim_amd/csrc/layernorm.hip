@@ -11,8 +11,8 @@
 // barrier anywhere (the first version of this file had six in the forward and eight in the backward and spent its time in
 // them: 15-21 us for the 4-10 MB of stages 2 / 3).  The wave reads every channel's TT-token piece with 16-byte vectors
 // (coalesced along the tokens), keeps the tile in its LDS as f32 [channel][TT + 1], takes the per-token sums with lanes =
-// (token, channel part) -- one sweep, shifted by the token's first channel so that sum and sum of squares do not cancel --
-// and writes the normalised rows token-major (coalesced along the channels) in the dtype autocast would give them.  The
+// (token, channel part) -- two sweeps of the LDS tile: the mean around the token's first channel, then sum and sum of squares
+// around that mean, so that neither a common shift nor an outlier channel cancels -- and writes the normalised rows token-major (coalesced along the channels) in the dtype autocast would give them.  The
 // backward does the same in the other direction: dy arrives token-major, dx leaves channel-major (the layout of the
 // residual stream it is added to).  dweight / dbias: the wave leaves its tile's partial sums as one row of a workspace and a
 // second small kernel adds the rows up (two launches, no same-address atomic traffic from thousands of waves; the only
@@ -79,19 +79,27 @@ __global__ void __launch_bounds__(kWave) ln_cm_fwd_kernel(const vivim_add_layern
     }
     if constexpr (!NORM) return;
     const int t = lane % TT, part = lane / TT;
-    const float pivot = tile[t];                       // channel 0 of the token
+    // Two sweeps over the tile.  The first takes the mean around channel 0 of the token (a shift common to all channels cancels
+    // there); the second takes sum d and sum d^2 around THAT mean, so that m * m below is a rounding-sized correction.  One
+    // sweep around channel 0 alone loses the variance when channel 0 is the outlier: m * m is then as large as s2 / C and up to
+    // C roundings land in rstd (channel 0 = 40 among randn, C = 512: 40 to 100 times the per-token bound of the tests).
+    const float pivot = tile[t];
+    const float inv_c = 1.0f / (float)C;
+    float s0 = 0.0f;
+#pragma unroll 8
+    for (int c = part; c < C; c += P) s0 += tile[c * PAD + t] - pivot;
+    const float mu = pivot + ln_parts_sum<TT>(s0) * inv_c;
     float s1 = 0.0f, s2 = 0.0f;
 #pragma unroll 8
     for (int c = part; c < C; c += P) {
-        const float d = tile[c * PAD + t] - pivot;
+        const float d = tile[c * PAD + t] - mu;
         s1 += d;
         s2 = fmaf(d, d, s2);
     }
     s1 = ln_parts_sum<TT>(s1);
     s2 = ln_parts_sum<TT>(s2);
-    const float inv_c = 1.0f / (float)C;
     const float m = s1 * inv_c;
-    const float mean = pivot + m;
+    const float mean = mu + m;
     const float rstd = rsqrtf(fmaxf(s2 * inv_c - m * m, 0.0f) + p.eps);
     if (part == 0) {
         stat[t] = mean;
