@@ -483,6 +483,51 @@ typedef struct {
     void *workspace;                                 /* backward scratch (see above) */
 } vivim_token_layernorm_params;
 
+/* ---- Residual add + LayerNorm / RMSNorm over TOKEN-major rows (csrc/token_layernorm.hip: the same kernels as above with the
+ * residual part compiled in; `hidden = drop_path(branch) + residual; LayerNorm(hidden)` of the SegFormer blocks, opt-in in Vivim) --
+ * All tensors are `rows` rows of `channels` elements, channel stride 1, one row stride each.
+ *   forward : h[r][c] = res[r][c] + scale[r / rows_per_sample] * branch[r][c]      fp32, rounded once to rtype -> res_out
+ *             res NULL: h = scale * branch (rounded to rtype when res_out is given); scale NULL: a factor of 1.
+ *             Statistics and y are taken from h AS STORED (the backward recomputes from the saved res_out):
+ *             LayerNorm (rms = 0): y = (h - mean) * rstd * weight + bias, the mean first, then the squared differences from it;
+ *             RMSNorm   (rms = 1): y = h * rstd * weight (+ bias), rstd = 1 / sqrt(sum_c h^2 / channels + eps), mean is written as 0.
+ *             weight NULL: the add alone -- res_out is written, y / mean / rstd are not touched.
+ *             mean / rstd are written when both are given; both NULL is the call no backward follows.
+ *   backward: dh = LNbwd(dy) + dres, LNbwd as vivim_token_layernorm_bwd (RMS: rstd * (g - xhat * mean_c(g * xhat)), xhat = h * rstd,
+ *             g = dy * weight); dy (gradient of y) or dres (gradient arriving at res_out) may be NULL, not both.
+ *             dres_in = dh in rtype, dbranch = scale * dh in btype (exactly 0 where scale is 0); each written when given.
+ *             dweight[c] = sum_r dy * xhat, dbias[c] = sum_r dy: WRITTEN through the slots, as above, either may be NULL.
+ *             weight NULL: the add's backward alone -- dy must be NULL, res_out / mean / rstd are not read.
+ * Types: branch, y, dy, dbranch: btype; res, res_out, dres, dres_in: rtype; scale, weight, bias, mean, rstd, dweight, dbias: fp32.
+ * (btype, rtype) is (f32, f32), (f16, f16), (bf16, bf16), (f16, f32) or (bf16, f32); any other pair and channels > 1024 return
+ * VIVIM_ERR_UNSUPPORTED.  Row strides are in elements and at least `channels`; only those of given tensors are looked at.
+ * scale is (rows / rows_per_sample) fp32; with it rows_per_sample > 0 must divide rows.
+ * Determinism and workspace: as vivim_token_layernorm_params (vivim_token_add_norm_bwd_workspace_bytes, the same formula).
+ * 16-byte accesses when channels is a whole number of 16-byte pieces of the narrower of the two types and every address and
+ * row stride of the call is 16-byte aligned, each stream checked on its own; element accesses otherwise.
+ * No vivim_sizeof row: the caller sets struct_bytes = sizeof(vivim_token_add_norm_params), any other value is refused. */
+typedef struct {
+    int32_t struct_bytes;                            /* sizeof(vivim_token_add_norm_params) as the caller compiled it */
+    int32_t rows, channels, rows_per_sample;
+    int32_t btype, rtype, otype;                     /* vivim_dtype_t; otype must equal btype */
+    int32_t rms;                                     /* 0 LayerNorm, 1 RMSNorm */
+    float eps;
+    int32_t _pad0;
+    int64_t branch_row_stride, res_row_stride, res_out_row_stride, y_row_stride;      /* in elements */
+    int64_t dy_row_stride, dres_row_stride, dres_in_row_stride, dbranch_row_stride;
+    const void *branch;                              /* forward input */
+    const void *res;                                 /* forward input or NULL */
+    const void *scale;                               /* (rows / rows_per_sample) f32 or NULL */
+    const void *weight, *bias;                       /* (channels) f32; weight NULL: the add alone; bias NULL is 0 */
+    void *res_out;                                   /* forward output; the backward reads it */
+    void *y;                                         /* forward output */
+    void *mean, *rstd;                               /* (rows) f32: written by the forward (or both NULL), read by the backward */
+    const void *dy, *dres;                           /* backward inputs; one may be NULL */
+    void *dres_in, *dbranch;                         /* backward outputs, each or NULL */
+    void *dweight, *dbias;                           /* (channels) f32, written; or NULL */
+    void *workspace;                                 /* backward scratch (see above) */
+} vivim_token_add_norm_params;
+
 int vivim_abi_version(void);
 const char *vivim_last_error(void);
 
@@ -549,6 +594,9 @@ int vivim_decode_head_fwd(const vivim_decode_head_params *p, void *stream);     
 int vivim_token_layernorm_fwd(const vivim_token_layernorm_params *p, void *stream);   /* reads x, writes y (+ mean, rstd) */
 int vivim_token_layernorm_bwd(const vivim_token_layernorm_params *p, void *stream);   /* writes dx (+ dweight, dbias) */
 size_t vivim_token_layernorm_bwd_workspace_bytes(const vivim_token_layernorm_params *p);   /* from rows, channels; 0 on bad sizes */
+int vivim_token_add_norm_fwd(const vivim_token_add_norm_params *p, void *stream);   /* writes res_out (+ y, mean, rstd) */
+int vivim_token_add_norm_bwd(const vivim_token_add_norm_params *p, void *stream);   /* writes dres_in, dbranch (+ dweight, dbias) */
+size_t vivim_token_add_norm_bwd_workspace_bytes(const vivim_token_add_norm_params *p);   /* from rows, channels; 0 on bad sizes */
 
 /* Deterministic backward (for torch.use_deterministic_algorithms).  Same parameters, checks and results as
  * vivim_selective_scan_bwd, and the same kernel family, but every gradient that the default call adds up across

@@ -1,8 +1,10 @@
 """Kernel launches of one tri-directional Mamba block (forward + backward, bf16 autocast, stage-0 shape of the bench) and of
 one whole train step, by kernel name -- the step is host-bound, so launches are what it pays for.
     python tools/launch_count.py [--dim 64] [--batch 3] [--frames 5] [--hw 4096] [--step] [--fused-loss] [--backbone-layernorm]
+                                  [--backbone-add-norm]
 --fused-loss (with --step) counts the step with train_step(fused_loss=True) as well, and the loss alone (forward + backward on
-the step's logits shape) both ways.  --backbone-layernorm (with --step) builds the model with fast_backbone_layernorm=True."""
+the step's logits shape) both ways.  --backbone-layernorm (with --step) builds the model with fast_backbone_layernorm=True,
+--backbone-add-norm with fused_backbone_add_norm=True."""
 import argparse
 import collections
 import os
@@ -45,6 +47,7 @@ def main():
     ap.add_argument("--step", action="store_true")
     ap.add_argument("--fused-loss", action="store_true")
     ap.add_argument("--backbone-layernorm", action="store_true")
+    ap.add_argument("--backbone-add-norm", action="store_true")
     a = ap.parse_args()
     dev = torch.device("cuda:0")
     from vivim_amd.mamba_simple import Mamba
@@ -59,13 +62,14 @@ def main():
     show(f"Mamba v3 block dim {a.dim} L {a.frames * a.hw} batch {a.batch}", *launches(block))
     if a.step:
         from vivim_amd import train_step as ts
-        model = ts.build_model(3, dev, fast_backbone_layernorm=a.backbone_layernorm)
+        model = ts.build_model(3, dev, fast_backbone_layernorm=a.backbone_layernorm, fused_backbone_add_norm=a.backbone_add_norm)
         opt = ts.make_optimizer(model)
         clip, onehot = ts.synthetic_batch(a.batch, a.frames, 256, 3, dev, 0)
 
         def step():
             ts.train_step(model, opt, clip, onehot, 3, torch.bfloat16)
-        show("train step" + (", fast_backbone_layernorm=True" if a.backbone_layernorm else ""), *launches(step), top=60)
+        show("train step" + (", fast_backbone_layernorm=True" if a.backbone_layernorm else "")
+             + (", fused_backbone_add_norm=True" if a.backbone_add_norm else ""), *launches(step), top=60)
         if a.fused_loss:
             from vivim_amd.seg_loss import recall_focused_loss_fused
 

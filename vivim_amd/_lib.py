@@ -172,6 +172,16 @@ class TokenLayerNormParams(ctypes.Structure):
                 + [(n, vp) for n in ("x", "weight", "bias", "y", "mean", "rstd", "dy", "dx", "dweight", "dbias", "workspace")])
 
 
+class TokenAddNormParams(ctypes.Structure):
+    """As TokenLayerNormParams: no vivim_sizeof row, not in STRUCTS, its sizeof stated in struct_bytes."""
+    _fields_ = ([(n, i32) for n in ("struct_bytes", "rows", "channels", "rows_per_sample", "btype", "rtype", "otype", "rms")]
+                + [("eps", ctypes.c_float), ("_pad0", i32)]
+                + [(n, i64) for n in ("branch_row_stride", "res_row_stride", "res_out_row_stride", "y_row_stride", "dy_row_stride",
+                                      "dres_row_stride", "dres_in_row_stride", "dbranch_row_stride")]
+                + [(n, vp) for n in ("branch", "res", "scale", "weight", "bias", "res_out", "y", "mean", "rstd", "dy", "dres",
+                                     "dres_in", "dbranch", "dweight", "dbias", "workspace")])
+
+
 # The structs in vivim_sizeof order.
 STRUCTS = (SsmFwdParams, SsmBwdParams, ConvFwdParams, ConvBwdParams, DwConvParams, DwConvWgradParams, DirParams,
            ConvUpdateParams, StateUpdateParams, LayerNormParams, WgradNtParams, AddLayerNormParams, SegLossParams,
@@ -236,6 +246,9 @@ ENTRY_POINTS = {
     "vivim_token_layernorm_fwd": Entry(None, (ctypes.POINTER(TokenLayerNormParams),), True, _int),
     "vivim_token_layernorm_bwd": Entry(None, (ctypes.POINTER(TokenLayerNormParams),), True, _int),
     "vivim_token_layernorm_bwd_workspace_bytes": Entry(None, (ctypes.POINTER(TokenLayerNormParams),), False, _size),
+    "vivim_token_add_norm_fwd": Entry(None, (ctypes.POINTER(TokenAddNormParams),), True, _int),
+    "vivim_token_add_norm_bwd": Entry(None, (ctypes.POINTER(TokenAddNormParams),), True, _int),
+    "vivim_token_add_norm_bwd_workspace_bytes": Entry(None, (ctypes.POINTER(TokenAddNormParams),), False, _size),
 }
 EXPORTS = tuple(ENTRY_POINTS)
 
@@ -294,6 +307,17 @@ def algorithmic_bytes(name, P):
             return n * (2 * _ISIZE[P.itype] + _ISIZE[P.btype] + _ISIZE[P.otype]) + 8 * P.batch * P.seqlen + 8 * P.channels
         res = (_ISIZE[P.itype] if P.dres else 0) + (_ISIZE[P.otype] if P.dy else 0) + (_ISIZE[P.btype] if P.dbranch else 0)
         return n * (2 * _ISIZE[P.itype] + res) + 8 * P.batch * P.seqlen + 12 * P.channels   # x_new, dx + what is present
+    if name.startswith("vivim_token_add_norm"):                         # every tensor that is given, once
+        n, b, r = P.rows * P.channels, _ISIZE[P.btype], _ISIZE[P.rtype]
+        stats = 8 * P.rows if P.mean and P.weight else 0
+        small = (4 * (P.rows // P.rows_per_sample) if P.scale else 0) + (4 * P.channels if P.weight else 0)
+        if name.endswith("fwd"):
+            small += 4 * P.channels if P.weight and P.bias else 0
+            return n * (b + (r if P.res else 0) + (r if P.res_out else 0) + (b if P.weight else 0)) + stats + small
+        norm = bool(P.weight and P.dy)                                  # else the saved row and the statistics are not read
+        small += (4 * P.channels if norm and P.dweight else 0) + (4 * P.channels if norm and P.dbias else 0)
+        return (n * ((r + b if norm else 0) + (r if P.dres else 0) + (r if P.dres_in else 0) + (b if P.dbranch else 0))
+                + (stats if norm else 0) + small)
     if name.startswith("vivim_token_layernorm"):                        # x, y + mean, rstd | x, dy, dx + mean, rstd, weight + dweight, dbias
         n = P.rows * P.channels
         stats = 8 * P.rows if P.mean else 0

@@ -51,6 +51,9 @@ int decode_head_max_hidden();
 bool token_layernorm_dispatch(const vivim_token_layernorm_params&, bool bwd, hipStream_t);   // token_layernorm.hip
 bool token_layernorm_pair_ok(int itype, int otype);
 size_t token_layernorm_bwd_workspace_bytes(const vivim_token_layernorm_params&);
+bool token_add_norm_dispatch(const vivim_token_add_norm_params&, bool bwd, hipStream_t);       // the same file, with the residual add
+bool token_add_norm_pair_ok(int btype, int rtype);
+size_t token_add_norm_bwd_workspace_bytes(const vivim_token_add_norm_params&);
 }  // namespace vivim
 
 static thread_local char g_err[512] = "";
@@ -701,6 +704,105 @@ int vivim_token_layernorm_bwd(const vivim_token_layernorm_params* p, void* strea
     if (!vivim::token_layernorm_dispatch(q, true, as_stream(stream)))
         return fail(VIVIM_ERR_UNSUPPORTED, "token_layernorm_bwd not implemented for input type %d / output type %d", p->itype, p->otype);
     return after_launch("token_layernorm_bwd");
+}
+
+// every refusal the forward and the backward of the token-major residual add + norm share, before any launch
+static int check_token_add_norm(const vivim_token_add_norm_params* p, const char* fn) {
+    VCHECK(p != nullptr);
+    if (p->struct_bytes != (int32_t)sizeof(vivim_token_add_norm_params))
+        return fail(VIVIM_ERR_INVALID, "%s: struct_bytes = %d, this library's vivim_token_add_norm_params has %zu", fn, p->struct_bytes,
+                    sizeof(vivim_token_add_norm_params));
+    if (!dtype_ok(p->btype) || !dtype_ok(p->rtype) || !dtype_ok(p->otype))
+        return fail(VIVIM_ERR_INVALID, "%s: btype = %d, rtype = %d, otype = %d: a type tag is 0 (f32), 1 (f16) or 2 (bf16)", fn, p->btype,
+                    p->rtype, p->otype);
+    if (p->rows <= 0) return fail(VIVIM_ERR_INVALID, "%s: rows = %d: at least one row", fn, p->rows);
+    if (p->channels < 1)
+        return fail(VIVIM_ERR_INVALID, "%s: channels = %d: a row has at least one channel", fn, p->channels);
+    if (p->channels > 1024)
+        return fail(VIVIM_ERR_UNSUPPORTED, "%s: channels = %d: a row of more than 1024 channels does not fit the lanes' registers", fn,
+                    p->channels);
+    if (!vivim::token_add_norm_pair_ok(p->btype, p->rtype) || p->otype != p->btype)
+        return fail(VIVIM_ERR_UNSUPPORTED, "%s: branch type %d with residual type %d and output type %d is not built (one type, or an "
+                    "f16 / bf16 branch and output on an f32 residual)", fn, p->btype, p->rtype, p->otype);
+    if (p->rms != 0 && p->rms != 1) return fail(VIVIM_ERR_INVALID, "%s: rms = %d: 0 (LayerNorm) or 1 (RMSNorm)", fn, p->rms);
+    if (p->scale != nullptr && (p->rows_per_sample <= 0 || p->rows % p->rows_per_sample != 0))
+        return fail(VIVIM_ERR_INVALID, "%s: rows_per_sample = %d with scale: it must be positive and divide rows = %d", fn,
+                    p->rows_per_sample, p->rows);
+    return VIVIM_OK;
+}
+
+// one tensor of a call: required or not, element-aligned, a row stride that holds a row
+static int check_tan_tensor(const char* fn, const char* name, const void* q, bool required, int type, int64_t stride, int channels) {
+    if (q == nullptr)
+        return required ? fail(VIVIM_ERR_INVALID, "%s: %s is NULL", fn, name) : VIVIM_OK;
+    if (!aligned(q, type == VIVIM_F32 ? 4 : 2))
+        return fail(VIVIM_ERR_INVALID, "%s: %s = %p is not aligned to its element type", fn, name, q);
+    if (stride < channels)
+        return fail(VIVIM_ERR_INVALID, "%s: %s_row_stride = %lld is less than the %d channels of a row", fn, name, (long long)stride, channels);
+    return VIVIM_OK;
+}
+static int check_tan_f32(const char* fn, const char* name, const void* q, bool required) {
+    if (q == nullptr)
+        return required ? fail(VIVIM_ERR_INVALID, "%s: %s is NULL", fn, name) : VIVIM_OK;
+    return aligned(q, 4) ? VIVIM_OK : fail(VIVIM_ERR_INVALID, "%s: %s = %p is not aligned to its element type", fn, name, q);
+}
+
+int vivim_token_add_norm_fwd(const vivim_token_add_norm_params* p, void* stream) {
+    const char* fn = "token_add_norm_fwd";
+    if (int rc = check_token_add_norm(p, fn)) return rc;
+    const bool norm = p->weight != nullptr;
+    const int C = p->channels;
+    if (int rc = check_tan_tensor(fn, "branch", p->branch, true, p->btype, p->branch_row_stride, C)) return rc;
+    if (int rc = check_tan_tensor(fn, "res", p->res, false, p->rtype, p->res_row_stride, C)) return rc;
+    // the add alone writes nothing else; a residual that is read is a sum that is stored (the backward reads it)
+    if (int rc = check_tan_tensor(fn, "res_out", p->res_out, !norm || p->res != nullptr, p->rtype, p->res_out_row_stride, C)) return rc;
+    if (int rc = check_tan_f32(fn, "scale", p->scale, false)) return rc;
+    if (norm) {
+        if (int rc = check_tan_tensor(fn, "y", p->y, true, p->otype, p->y_row_stride, C)) return rc;
+        if (int rc = check_tan_f32(fn, "weight", p->weight, true)) return rc;
+        if (int rc = check_tan_f32(fn, "bias", p->bias, false)) return rc;
+        if ((p->mean == nullptr) != (p->rstd == nullptr))
+            return fail(VIVIM_ERR_INVALID, "%s: mean = %p with rstd = %p: both or neither", fn, p->mean, p->rstd);
+        if (int rc = check_tan_f32(fn, "mean", p->mean, false)) return rc;
+        if (int rc = check_tan_f32(fn, "rstd", p->rstd, false)) return rc;
+    }
+    if (!vivim::token_add_norm_dispatch(*p, false, as_stream(stream)))
+        return fail(VIVIM_ERR_UNSUPPORTED, "%s not implemented for branch type %d / residual type %d", fn, p->btype, p->rtype);
+    return after_launch(fn);
+}
+
+size_t vivim_token_add_norm_bwd_workspace_bytes(const vivim_token_add_norm_params* p) {
+    return p && p->rows > 0 && p->channels > 0 && p->channels <= 1024 ? vivim::token_add_norm_bwd_workspace_bytes(*p) : 0;
+}
+
+int vivim_token_add_norm_bwd(const vivim_token_add_norm_params* p, void* stream) {
+    const char* fn = "token_add_norm_bwd";
+    if (int rc = check_token_add_norm(p, fn)) return rc;
+    const bool norm = p->weight != nullptr;
+    const int C = p->channels;
+    if (p->dy == nullptr && p->dres == nullptr) return fail(VIVIM_ERR_INVALID, "%s: dy and dres are both NULL: nothing to propagate", fn);
+    if (!norm && p->dy != nullptr) return fail(VIVIM_ERR_INVALID, "%s: dy = %p without weight: the add alone has no y", fn, p->dy);
+    if (norm) {
+        if (int rc = check_tan_tensor(fn, "res_out", p->res_out, true, p->rtype, p->res_out_row_stride, C)) return rc;
+        if (int rc = check_tan_f32(fn, "mean", p->mean, true)) return rc;
+        if (int rc = check_tan_f32(fn, "rstd", p->rstd, true)) return rc;
+        if (int rc = check_tan_f32(fn, "weight", p->weight, true)) return rc;
+        if (int rc = check_tan_tensor(fn, "dy", p->dy, false, p->otype, p->dy_row_stride, C)) return rc;
+        if (int rc = check_tan_f32(fn, "dweight", p->dweight, false)) return rc;
+        if (int rc = check_tan_f32(fn, "dbias", p->dbias, false)) return rc;
+        if (int rc = check_tan_f32(fn, "workspace", p->workspace, false)) return rc;
+        if ((p->dweight || p->dbias) && !p->workspace)
+            return fail(VIVIM_ERR_INVALID, "%s: dweight / dbias need the workspace (vivim_token_add_norm_bwd_workspace_bytes)", fn);
+    }
+    if (int rc = check_tan_tensor(fn, "dres", p->dres, false, p->rtype, p->dres_row_stride, C)) return rc;
+    if (int rc = check_tan_tensor(fn, "dres_in", p->dres_in, false, p->rtype, p->dres_in_row_stride, C)) return rc;
+    if (int rc = check_tan_tensor(fn, "dbranch", p->dbranch, false, p->btype, p->dbranch_row_stride, C)) return rc;
+    if (int rc = check_tan_f32(fn, "scale", p->scale, false)) return rc;
+    vivim_token_add_norm_params q = *p;
+    if (!q.dweight && !q.dbias) q.workspace = nullptr;               // nothing to sum: the kernel stores no slot
+    if (!vivim::token_add_norm_dispatch(q, true, as_stream(stream)))
+        return fail(VIVIM_ERR_UNSUPPORTED, "%s not implemented for branch type %d / residual type %d", fn, p->btype, p->rtype);
+    return after_launch(fn);
 }
 
 }  // extern "C"

@@ -16,6 +16,13 @@
 // outputs, the same bits every run.
 // Rows past `rows` and chunks past C are neither read nor written.
 // HBM-bound: the forward reads x and writes y once; the backward reads x and dy and writes dx once.
+//
+// The residual add in front of the norm (vivim_token_add_norm_params) is the same kernels with ADD = true: the forward builds the
+// row as h = res + scale * branch, rounds it once to the residual type, stores it (res_out) and norms what it stored; the
+// backward adds the gradient arriving at res_out to the norm's and writes it twice, as dres_in and, times scale, as dbranch.
+// RMSNorm is a run-time flag of those launches that skips the mean.  With ADD = false all of it is compiled out: the plain
+// entry points run the arithmetic they always ran.  E is then one 16-byte vector of the NARROWER of the two types, so that the
+// wider stream moves in two 16-byte accesses per chunk.
 #include <algorithm>
 #include "common.cuh"
 
@@ -38,21 +45,37 @@ __device__ __forceinline__ void tln_load(const T* __restrict__ q, bool pred, flo
     unpack<T, E>(r, v);
 }
 
-template <typename TI, typename TO, int G, int K, int E>
-__global__ void __launch_bounds__(kWave * kTlnWaves) tln_fwd_kernel(const vivim_token_layernorm_params p) {
+// What the kernels take: either public struct, restated.  x is the norm's input (ADD: the saved res_out of the backward).
+struct TlnArgs {
+    int32_t rows, channels, rows_per_sample, rms;
+    float eps;
+    int64_t x_row_stride, y_row_stride, dy_row_stride, dx_row_stride;
+    int64_t branch_row_stride, res_row_stride, res_out_row_stride, dres_row_stride, dbranch_row_stride;
+    const void *x, *weight, *bias;
+    void *y, *mean, *rstd;
+    const void* dy;
+    void *dx, *dweight, *dbias, *workspace;
+    const void *branch, *res, *scale, *dres;         // ADD only
+    void *res_out, *dbranch;
+};
+
+template <bool ADD, typename TI, typename TO, int G, int K, int E>
+__global__ void __launch_bounds__(kWave * kTlnWaves) tln_fwd_kernel(const TlnArgs p) {
     constexpr int RPW = kWave / G;
     const int lane = threadIdx.x & (kWave - 1), wave = threadIdx.x / kWave;
     const int sub = lane % G, rl = lane / G;
     const int C = p.channels;
     const float* __restrict__ wp = static_cast<const float*>(p.weight);
     const float* __restrict__ bp = static_cast<const float*>(p.bias);
+    const bool norm = !ADD || wp != nullptr;             // ADD without a weight: the add alone
+    const bool rms = ADD && p.rms != 0;
     float w[K][E], b[K][E];
     bool cv[K];
 #pragma unroll
     for (int k = 0; k < K; ++k) {
         const int c0 = (sub + k * G) * E;
         cv[k] = c0 < C;                                  // E > 1: C is a whole number of chunks
-        tln_load<float, E>(wp + c0, cv[k], w[k]);
+        tln_load<float, E>(wp + c0, cv[k] && norm, w[k]);
         tln_load<float, E>(bp + c0, cv[k] && bp != nullptr, b[k]);
     }
     const float inv_c = 1.0f / (float)C;
@@ -64,16 +87,39 @@ __global__ void __launch_bounds__(kWave * kTlnWaves) tln_fwd_kernel(const vivim_
     for (int64_t g = (int64_t)blockIdx.x * kTlnWaves + wave; g < ngroups; g += (int64_t)gridDim.x * kTlnWaves) {
         const int64_t r = g * RPW + rl;
         const bool ok = r < rows;
-        const TI* __restrict__ xr = x + r * p.x_row_stride;
         float v[K][E];
+        if constexpr (ADD) {
+            const TO* __restrict__ br = static_cast<const TO*>(p.branch) + r * p.branch_row_stride;
+            const TI* __restrict__ rr = static_cast<const TI*>(p.res) + r * p.res_row_stride;
+            TI* __restrict__ hr = static_cast<TI*>(p.res_out) + r * p.res_out_row_stride;
+            const float* __restrict__ scp = static_cast<const float*>(p.scale);
+            const float sc = scp != nullptr && ok ? scp[(int)r / p.rows_per_sample] : 1.0f;
 #pragma unroll
-        for (int k = 0; k < K; ++k) tln_load<TI, E>(xr + (sub + k * G) * E, ok && cv[k], v[k]);
+            for (int k = 0; k < K; ++k) {
+                float bv[E];
+                tln_load<TO, E>(br + (sub + k * G) * E, ok && cv[k], bv);
+                tln_load<TI, E>(rr + (sub + k * G) * E, ok && cv[k] && p.res != nullptr, v[k]);
+#pragma unroll
+                for (int e = 0; e < E; ++e) v[k][e] = fmaf(sc, bv[e], v[k][e]);
+                if (p.res_out != nullptr) {              // the row as stored is the row that is normed
+#pragma unroll
+                    for (int e = 0; e < E; ++e) v[k][e] = to_f32<TI>(from_f32<TI>(v[k][e]));
+                    store_vec<TI, E>(hr + (sub + k * G) * E, ok && cv[k], v[k]);
+                }
+            }
+            if (!norm) continue;
+        } else {
+            const TI* __restrict__ xr = x + r * p.x_row_stride;
+#pragma unroll
+            for (int k = 0; k < K; ++k) tln_load<TI, E>(xr + (sub + k * G) * E, ok && cv[k], v[k]);
+        }
         float s = 0.0f;
 #pragma unroll
         for (int k = 0; k < K; ++k)
 #pragma unroll
             for (int e = 0; e < E; ++e) s += v[k][e];    // what was not loaded is 0
-        const float mean = tln_row_sum<G>(s) * inv_c;
+        float mean = tln_row_sum<G>(s) * inv_c;
+        if constexpr (ADD) mean = rms ? 0.0f : mean;
         float q = 0.0f;
 #pragma unroll
         for (int k = 0; k < K; ++k)
@@ -100,21 +146,23 @@ __global__ void __launch_bounds__(kWave * kTlnWaves) tln_fwd_kernel(const vivim_
 }
 
 // grid: the slots.  Every workgroup stores its slot (zeros when it had no row), so the slot sum never reads what nobody wrote.
-template <typename TI, typename TO, int G, int K, int E>
-__global__ void __launch_bounds__(kWave * kTlnWaves) tln_bwd_kernel(const vivim_token_layernorm_params p) {
+template <bool ADD, typename TI, typename TO, int G, int K, int E>
+__global__ void __launch_bounds__(kWave * kTlnWaves) tln_bwd_kernel(const TlnArgs p) {
     constexpr int RPW = kWave / G, CH = G * K * E;
     __shared__ float red[kTlnWaves][2][CH];
     const int lane = threadIdx.x & (kWave - 1), wave = threadIdx.x / kWave;
     const int sub = lane % G, rl = lane / G;
     const int C = p.channels;
     const float* __restrict__ wp = static_cast<const float*>(p.weight);
+    const bool has_dy = !ADD || (wp != nullptr && p.dy != nullptr);   // ADD without dy: dh is dres
+    const bool rms = ADD && p.rms != 0;
     float w[K][E], dw[K][E], db[K][E];
     bool cv[K];
 #pragma unroll
     for (int k = 0; k < K; ++k) {
         const int c0 = (sub + k * G) * E;
         cv[k] = c0 < C;
-        tln_load<float, E>(wp + c0, cv[k], w[k]);
+        tln_load<float, E>(wp + c0, cv[k] && has_dy, w[k]);
 #pragma unroll
         for (int e = 0; e < E; ++e) dw[k][e] = db[k][e] = 0.0f;
     }
@@ -128,16 +176,18 @@ __global__ void __launch_bounds__(kWave * kTlnWaves) tln_bwd_kernel(const vivim_
     for (int64_t g = (int64_t)blockIdx.x * kTlnWaves + wave; g < ngroups; g += (int64_t)gridDim.x * kTlnWaves) {
         const int64_t r = g * RPW + rl;
         const bool ok = r < rows;
+        const bool okn = ok && has_dy;                   // the norm's side of this row is live
         const TI* __restrict__ xr = x + r * p.x_row_stride;
         const TO* __restrict__ gr = dy + r * p.dy_row_stride;
         float v[K][E], gy[K][E];
 #pragma unroll
         for (int k = 0; k < K; ++k) {
-            tln_load<TI, E>(xr + (sub + k * G) * E, ok && cv[k], v[k]);
-            tln_load<TO, E>(gr + (sub + k * G) * E, ok && cv[k], gy[k]);
+            tln_load<TI, E>(xr + (sub + k * G) * E, okn && cv[k], v[k]);
+            tln_load<TO, E>(gr + (sub + k * G) * E, okn && cv[k], gy[k]);
         }
-        const float mean = ok ? meanp[r] : 0.0f;
-        const float rstd = ok ? rstdp[r] : 0.0f;
+        float mean = okn ? meanp[r] : 0.0f;
+        const float rstd = okn ? rstdp[r] : 0.0f;
+        if constexpr (ADD) mean = rms ? 0.0f : mean;
         float s1 = 0.0f, s2 = 0.0f;
 #pragma unroll
         for (int k = 0; k < K; ++k)
@@ -154,13 +204,33 @@ __global__ void __launch_bounds__(kWave * kTlnWaves) tln_bwd_kernel(const vivim_
             }
         s1 = tln_row_sum<G>(s1) * inv_c;
         s2 = tln_row_sum<G>(s2) * inv_c;
+        if constexpr (ADD) s1 = rms ? 0.0f : s1;
         TI* __restrict__ dxr = dx + r * p.dx_row_stride;
+        if constexpr (ADD) {
+            const TI* __restrict__ dr = static_cast<const TI*>(p.dres) + r * p.dres_row_stride;
+            TO* __restrict__ dbr = static_cast<TO*>(p.dbranch) + r * p.dbranch_row_stride;
+            const float* __restrict__ scp = static_cast<const float*>(p.scale);
+            const float sc = scp != nullptr && ok ? scp[(int)r / p.rows_per_sample] : 1.0f;
 #pragma unroll
-        for (int k = 0; k < K; ++k) {
-            float o[E];
+            for (int k = 0; k < K; ++k) {
+                float o[E], t[E];
+                tln_load<TI, E>(dr + (sub + k * G) * E, ok && cv[k] && p.dres != nullptr, o);
 #pragma unroll
-            for (int e = 0; e < E; ++e) o[e] = rstd * (gy[k][e] - s1 - v[k][e] * s2);
-            store_vec<TI, E>(dxr + (sub + k * G) * E, ok && cv[k], o);
+                for (int e = 0; e < E; ++e) {
+                    o[e] += rstd * (gy[k][e] - s1 - v[k][e] * s2);
+                    t[e] = sc * o[e];
+                }
+                store_vec<TI, E>(dxr + (sub + k * G) * E, ok && cv[k] && dx != nullptr, o);
+                store_vec<TO, E>(dbr + (sub + k * G) * E, ok && cv[k] && p.dbranch != nullptr, t);
+            }
+        } else {
+#pragma unroll
+            for (int k = 0; k < K; ++k) {
+                float o[E];
+#pragma unroll
+                for (int e = 0; e < E; ++e) o[e] = rstd * (gy[k][e] - s1 - v[k][e] * s2);
+                store_vec<TI, E>(dxr + (sub + k * G) * E, ok && cv[k], o);
+            }
         }
     }
     if (p.workspace == nullptr) return;                  // neither dweight nor dbias is wanted (the same in every thread)
@@ -217,60 +287,57 @@ __global__ void __launch_bounds__(kWave * kTlnRedWaves) tln_slot_sum_kernel(cons
 
 static int tln_isize(int t) { return t == VIVIM_F32 ? 4 : 2; }
 
-int token_layernorm_slots(const vivim_token_layernorm_params& p) {
-    return (int)std::min<int64_t>(kTlnMaxSlots, ((int64_t)p.rows + 3) / 4);
-}
+static int tln_slots(int64_t rows) { return (int)std::min<int64_t>(kTlnMaxSlots, (rows + 3) / 4); }
 size_t token_layernorm_bwd_workspace_bytes(const vivim_token_layernorm_params& p) {
-    return (size_t)token_layernorm_slots(p) * 2 * p.channels * sizeof(float);
+    return (size_t)tln_slots(p.rows) * 2 * p.channels * sizeof(float);
+}
+size_t token_add_norm_bwd_workspace_bytes(const vivim_token_add_norm_params& p) {
+    return (size_t)tln_slots(p.rows) * 2 * p.channels * sizeof(float);
 }
 
-// 16-byte accesses: whole vectors of x per row, and every address and row stride of this call on a 16-byte boundary
-static bool tln_vector_path(const vivim_token_layernorm_params& p, bool bwd) {
-    const int isz = tln_isize(p.itype), osz = tln_isize(p.otype);
-    auto a16 = [](const void* q) { return reinterpret_cast<uintptr_t>(q) % 16 == 0; };
-    auto s16 = [](int64_t stride, int size) { return stride * size % 16 == 0; };
-    if (p.channels % (16 / isz) != 0 || !a16(p.x) || !s16(p.x_row_stride, isz) || !a16(p.weight)) return false;
-    if (!bwd) return a16(p.y) && s16(p.y_row_stride, osz) && a16(p.bias);
-    return a16(p.dy) && s16(p.dy_row_stride, osz) && a16(p.dx) && s16(p.dx_row_stride, isz);
+// one stream of a call: its base, its row stride in elements and its element size.  A stream that is not given passes.
+static bool tln_s16(const void* q, int64_t stride, int size) {
+    return q == nullptr || (reinterpret_cast<uintptr_t>(q) % 16 == 0 && stride * size % 16 == 0);
 }
 
-template <typename TI, typename TO, int G, int K, int E>
-static void tln_launch_gk(const vivim_token_layernorm_params& p, bool bwd, hipStream_t stream) {
+template <bool ADD, typename TI, typename TO, int G, int K, int E>
+static void tln_launch_gk(const TlnArgs& p, bool bwd, hipStream_t stream) {
     const int64_t ngroups = ((int64_t)p.rows + kWave / G - 1) / (kWave / G);
     const int64_t wgs = (ngroups + kTlnWaves - 1) / kTlnWaves;
     const dim3 block(kWave * kTlnWaves);
     if (!bwd) {
-        hipLaunchKernelGGL((tln_fwd_kernel<TI, TO, G, K, E>), dim3((unsigned)std::min<int64_t>(wgs, 2048)), block, 0, stream, p);
+        hipLaunchKernelGGL((tln_fwd_kernel<ADD, TI, TO, G, K, E>), dim3((unsigned)std::min<int64_t>(wgs, 2048)), block, 0, stream, p);
         return;
     }
-    const int nslots = (int)std::min<int64_t>(wgs, token_layernorm_slots(p));     // wgs <= ceil(rows / 4)
-    hipLaunchKernelGGL((tln_bwd_kernel<TI, TO, G, K, E>), dim3((unsigned)nslots), block, 0, stream, p);
+    const int nslots = (int)std::min<int64_t>(wgs, tln_slots(p.rows));     // wgs <= ceil(rows / 4)
+    hipLaunchKernelGGL((tln_bwd_kernel<ADD, TI, TO, G, K, E>), dim3((unsigned)nslots), block, 0, stream, p);
     if (p.workspace != nullptr)
         hipLaunchKernelGGL(tln_slot_sum_kernel, dim3((unsigned)((2 * p.channels + kWave - 1) / kWave)), dim3(kWave * kTlnRedWaves), 0, stream,
                            static_cast<const float*>(p.workspace), nslots, p.channels, static_cast<float*>(p.dweight),
                            static_cast<float*>(p.dbias));
 }
 
-// the smallest lane group, then the fewest chunks per lane, that hold a row
-template <typename TI, typename TO>
-static void tln_launch(const vivim_token_layernorm_params& p, bool bwd, hipStream_t stream) {
-    constexpr int EV = 16 / (int)sizeof(TI);
-    if (tln_vector_path(p, bwd)) {
+// the smallest lane group, then the fewest chunks per lane, that hold a row.  `vec`: 16-byte accesses (the caller has checked
+// every stream of the call); a chunk is then one 16-byte vector of the narrower type of the call
+template <bool ADD, typename TI, typename TO>
+static void tln_launch(const TlnArgs& p, bool bwd, bool vec, hipStream_t stream) {
+    constexpr int EV = 16 / (int)(ADD && sizeof(TO) < sizeof(TI) ? sizeof(TO) : sizeof(TI));
+    if (vec) {
         const int n = p.channels / EV;
-        if (n <= 8) tln_launch_gk<TI, TO, 8, 1, EV>(p, bwd, stream);
-        else if (n <= 16) tln_launch_gk<TI, TO, 16, 1, EV>(p, bwd, stream);
-        else if (n <= 32) tln_launch_gk<TI, TO, 32, 1, EV>(p, bwd, stream);
-        else if (n <= 64) tln_launch_gk<TI, TO, 64, 1, EV>(p, bwd, stream);
-        else if (n <= 128) tln_launch_gk<TI, TO, 64, 2, EV>(p, bwd, stream);
-        else if constexpr (EV == 4) tln_launch_gk<TI, TO, 64, 4, EV>(p, bwd, stream);     // 1024 channels are 128 vectors of a 16-bit row
+        if (n <= 8) tln_launch_gk<ADD, TI, TO, 8, 1, EV>(p, bwd, stream);
+        else if (n <= 16) tln_launch_gk<ADD, TI, TO, 16, 1, EV>(p, bwd, stream);
+        else if (n <= 32) tln_launch_gk<ADD, TI, TO, 32, 1, EV>(p, bwd, stream);
+        else if (n <= 64) tln_launch_gk<ADD, TI, TO, 64, 1, EV>(p, bwd, stream);
+        else if (n <= 128) tln_launch_gk<ADD, TI, TO, 64, 2, EV>(p, bwd, stream);
+        else if constexpr (EV == 4) tln_launch_gk<ADD, TI, TO, 64, 4, EV>(p, bwd, stream);     // 1024 channels are 128 vectors of a 16-bit row
     } else {
         const int n = p.channels;
-        if (n <= 8) tln_launch_gk<TI, TO, 8, 1, 1>(p, bwd, stream);
-        else if (n <= 64) tln_launch_gk<TI, TO, 64, 1, 1>(p, bwd, stream);
-        else if (n <= 128) tln_launch_gk<TI, TO, 64, 2, 1>(p, bwd, stream);
-        else if (n <= 256) tln_launch_gk<TI, TO, 64, 4, 1>(p, bwd, stream);
-        else if (n <= 512) tln_launch_gk<TI, TO, 64, 8, 1>(p, bwd, stream);
-        else tln_launch_gk<TI, TO, 64, 16, 1>(p, bwd, stream);
+        if (n <= 8) tln_launch_gk<ADD, TI, TO, 8, 1, 1>(p, bwd, stream);
+        else if (n <= 64) tln_launch_gk<ADD, TI, TO, 64, 1, 1>(p, bwd, stream);
+        else if (n <= 128) tln_launch_gk<ADD, TI, TO, 64, 2, 1>(p, bwd, stream);
+        else if (n <= 256) tln_launch_gk<ADD, TI, TO, 64, 4, 1>(p, bwd, stream);
+        else if (n <= 512) tln_launch_gk<ADD, TI, TO, 64, 8, 1>(p, bwd, stream);
+        else tln_launch_gk<ADD, TI, TO, 64, 16, 1>(p, bwd, stream);
     }
 }
 
@@ -280,14 +347,66 @@ bool token_layernorm_pair_ok(int itype, int otype) {
 
 bool token_layernorm_dispatch(const vivim_token_layernorm_params& p, bool bwd, hipStream_t stream) {
     if (p.channels < 1 || p.channels > 1024 || !token_layernorm_pair_ok(p.itype, p.otype)) return false;
+    TlnArgs a = {};
+    a.rows = p.rows, a.channels = p.channels, a.eps = p.eps;
+    a.x_row_stride = p.x_row_stride, a.y_row_stride = p.y_row_stride, a.dy_row_stride = p.dy_row_stride, a.dx_row_stride = p.dx_row_stride;
+    a.x = p.x, a.weight = p.weight, a.bias = p.bias, a.y = p.y, a.mean = p.mean, a.rstd = p.rstd;
+    a.dy = p.dy, a.dx = p.dx, a.dweight = p.dweight, a.dbias = p.dbias, a.workspace = p.workspace;
+    // 16-byte accesses: whole vectors of x per row, and every address and row stride of this call on a 16-byte boundary
+    const int isz = tln_isize(p.itype), osz = tln_isize(p.otype);
+    bool vec = p.channels % (16 / isz) == 0 && tln_s16(p.x, p.x_row_stride, isz) && tln_s16(p.weight, 0, 4);
+    if (!bwd) vec = vec && tln_s16(p.y, p.y_row_stride, osz) && tln_s16(p.bias, 0, 4);
+    else vec = vec && tln_s16(p.dy, p.dy_row_stride, osz) && tln_s16(p.dx, p.dx_row_stride, isz);
     switch (p.itype * 3 + p.otype) {
-        case VIVIM_F32 * 3 + VIVIM_F32: tln_launch<float, float>(p, bwd, stream); return true;
-        case VIVIM_F32 * 3 + VIVIM_F16: tln_launch<float, f16_t>(p, bwd, stream); return true;
-        case VIVIM_F32 * 3 + VIVIM_BF16: tln_launch<float, bf16_t>(p, bwd, stream); return true;
-        case VIVIM_F16 * 3 + VIVIM_F32: tln_launch<f16_t, float>(p, bwd, stream); return true;
-        case VIVIM_F16 * 3 + VIVIM_F16: tln_launch<f16_t, f16_t>(p, bwd, stream); return true;
-        case VIVIM_BF16 * 3 + VIVIM_F32: tln_launch<bf16_t, float>(p, bwd, stream); return true;
-        case VIVIM_BF16 * 3 + VIVIM_BF16: tln_launch<bf16_t, bf16_t>(p, bwd, stream); return true;
+        case VIVIM_F32 * 3 + VIVIM_F32: tln_launch<false, float, float>(a, bwd, vec, stream); return true;
+        case VIVIM_F32 * 3 + VIVIM_F16: tln_launch<false, float, f16_t>(a, bwd, vec, stream); return true;
+        case VIVIM_F32 * 3 + VIVIM_BF16: tln_launch<false, float, bf16_t>(a, bwd, vec, stream); return true;
+        case VIVIM_F16 * 3 + VIVIM_F32: tln_launch<false, f16_t, float>(a, bwd, vec, stream); return true;
+        case VIVIM_F16 * 3 + VIVIM_F16: tln_launch<false, f16_t, f16_t>(a, bwd, vec, stream); return true;
+        case VIVIM_BF16 * 3 + VIVIM_F32: tln_launch<false, bf16_t, float>(a, bwd, vec, stream); return true;
+        case VIVIM_BF16 * 3 + VIVIM_BF16: tln_launch<false, bf16_t, bf16_t>(a, bwd, vec, stream); return true;
+    }
+    return false;
+}
+
+// (branch = y type, residual type): the same, or a 16-bit branch on an f32 residual stream (the autocast case)
+bool token_add_norm_pair_ok(int btype, int rtype) {
+    return rtype == btype || (rtype == VIVIM_F32 && (btype == VIVIM_F16 || btype == VIVIM_BF16));
+}
+
+bool token_add_norm_dispatch(const vivim_token_add_norm_params& p, bool bwd, hipStream_t stream) {
+    if (p.channels < 1 || p.channels > 1024 || !token_add_norm_pair_ok(p.btype, p.rtype) || p.otype != p.btype) return false;
+    TlnArgs a = {};
+    a.rows = p.rows, a.channels = p.channels, a.rows_per_sample = p.rows_per_sample, a.rms = p.rms, a.eps = p.eps;
+    a.weight = p.weight, a.bias = p.bias, a.mean = p.mean, a.rstd = p.rstd, a.scale = p.scale;
+    const int bsz = tln_isize(p.btype), rsz = tln_isize(p.rtype);
+    bool vec = p.channels % (16 / std::min(bsz, rsz)) == 0 && tln_s16(p.weight, 0, 4);
+    if (!bwd) {
+        a.branch = p.branch, a.branch_row_stride = p.branch_row_stride;
+        a.res = p.res, a.res_row_stride = p.res_row_stride;
+        a.res_out = p.res_out, a.res_out_row_stride = p.res_out_row_stride;
+        if (p.weight != nullptr) a.y = p.y, a.y_row_stride = p.y_row_stride;
+        vec = vec && tln_s16(a.branch, a.branch_row_stride, bsz) && tln_s16(a.res, a.res_row_stride, rsz) &&
+              tln_s16(a.res_out, a.res_out_row_stride, rsz) && tln_s16(a.y, a.y_row_stride, bsz) && tln_s16(p.bias, 0, 4);
+    } else {
+        if (p.weight != nullptr) {
+            a.x = p.res_out, a.x_row_stride = p.res_out_row_stride;
+            a.dy = p.dy, a.dy_row_stride = p.dy_row_stride;
+            a.dweight = p.dweight, a.dbias = p.dbias, a.workspace = p.workspace;
+        }
+        a.dres = p.dres, a.dres_row_stride = p.dres_row_stride;
+        a.dx = p.dres_in, a.dx_row_stride = p.dres_in_row_stride;
+        a.dbranch = p.dbranch, a.dbranch_row_stride = p.dbranch_row_stride;
+        if (a.dy == nullptr) a.x = nullptr;              // dh is dres: the saved row is not read
+        vec = vec && tln_s16(a.x, a.x_row_stride, rsz) && tln_s16(a.dy, a.dy_row_stride, bsz) && tln_s16(a.dres, a.dres_row_stride, rsz) &&
+              tln_s16(a.dx, a.dx_row_stride, rsz) && tln_s16(a.dbranch, a.dbranch_row_stride, bsz);
+    }
+    switch (p.btype * 3 + p.rtype) {
+        case VIVIM_F32 * 3 + VIVIM_F32: tln_launch<true, float, float>(a, bwd, vec, stream); return true;
+        case VIVIM_F16 * 3 + VIVIM_F16: tln_launch<true, f16_t, f16_t>(a, bwd, vec, stream); return true;
+        case VIVIM_BF16 * 3 + VIVIM_BF16: tln_launch<true, bf16_t, bf16_t>(a, bwd, vec, stream); return true;
+        case VIVIM_F16 * 3 + VIVIM_F32: tln_launch<true, float, f16_t>(a, bwd, vec, stream); return true;
+        case VIVIM_BF16 * 3 + VIVIM_F32: tln_launch<true, float, bf16_t>(a, bwd, vec, stream); return true;
     }
     return false;
 }

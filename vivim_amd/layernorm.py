@@ -21,7 +21,19 @@ LayerNorm of TOKEN-major rows (csrc/token_layernorm.hip; vivim_token_layernorm_p
 
     layer_norm_tm(x, weight, bias, eps, out_dtype=None)   x: (..., C) with unit channel stride whose leading dimensions collapse to
                                             one row stride -> x's shape, contiguous, in out_dtype (None: what F.layer_norm returns)
-`tm_supported(x, weight, bias)` says whether it applies.  No atomics: it also runs under torch.use_deterministic_algorithms."""
+`tm_supported(x, weight, bias)` says whether it applies.  No atomics: it also runs under torch.use_deterministic_algorithms.
+
+The residual add in front of a token-major norm, fused with it (the same kernels; vivim_token_add_norm_params) -- the SegFormer
+blocks' `hidden = drop_path(branch) + residual` followed by a LayerNorm (Vivim(fused_backbone_add_norm=True)):
+
+    add_layer_norm_tm(res, branch, weight, bias, eps, scale=None, out_dtype=None, rms=False) -> (res_new, y)
+                                            res, branch: (..., C) rows as above, branch in res's dtype or f16 / bf16 on an f32 res;
+                                            scale: (res.shape[0],) f32 per-sample DropPath factor or None
+                                            res_new = res + scale * branch, contiguous, in res's dtype; y = the norm of res_new AS
+                                            STORED, in branch's dtype (out_dtype, when given, must say the same); rms: RMSNorm
+    add_tm(res, branch, scale=None) -> res_new                          the add alone
+    rms_norm_tm(x, weight, bias=None, eps, out_dtype=None) -> y         RMSNorm of rows, in x's dtype
+`tm_add_supported(res, branch, weight, bias)` says whether they apply, `tm_add_worthwhile(res)` whether they pay."""
 import ctypes
 
 import torch
@@ -386,3 +398,228 @@ def layer_norm_tm(x, weight, bias, eps=1e-5, out_dtype=None, rows=None):
         raise ValueError(f"layer_norm_tm: {x.dtype} rows with a {out_dtype} output are not built")
     need_stats = torch.is_grad_enabled() and (x.requires_grad or weight.requires_grad or (bias is not None and bias.requires_grad))
     return _LayerNormTM.apply(x, weight, bias, eps, out_dtype, need_stats, rows)
+
+
+# ---- residual add + norm over token-major rows (the ADD instantiation of csrc/token_layernorm.hip)
+def tm_add_pair_ok(branch_dtype, res_dtype):
+    """The (branch = y, residual) dtype pairs the kernels are built for: the same, or f16 / bf16 on an f32 residual stream."""
+    return branch_dtype in ITYPE and (res_dtype == branch_dtype or res_dtype == torch.float32)
+
+
+def tm_add_rows(res, branch, weight=None, bias=None):
+    """(rows, res's row stride, branch's row stride) when add_layer_norm_tm (weight given) / add_tm (weight None) take these
+    tensors, else None."""
+    if not (res.is_cuda and branch.is_cuda and res.device == branch.device and tuple(res.shape) == tuple(branch.shape)):
+        return None
+    if not (res.dim() >= 1 and tm_add_pair_ok(branch.dtype, res.dtype) and 1 <= res.shape[-1] <= TM_MAX_C):
+        return None
+    if res.stride(-1) != 1 or branch.stride(-1) != 1:
+        return None
+    for t in (weight, bias):
+        if t is not None and not (t.dtype == torch.float32 and t.device == res.device and tuple(t.shape) == (res.shape[-1],)
+                                  and t.is_contiguous()):
+            return None
+    a, b = _rows(res), _rows(branch)
+    if a is None or b is None or min(a[1], b[1]) < res.shape[-1] or a[0] >= 2 ** 31:
+        return None
+    return a[0], a[1], b[1]
+
+
+def tm_add_supported(res, branch, weight=None, bias=None):
+    """Whether add_layer_norm_tm / add_tm take these tensors.  True under torch.use_deterministic_algorithms as well: the kernels
+    have no atomics."""
+    return tm_add_rows(res, branch, weight, bias) is not None
+
+
+def tm_add_worthwhile(res):
+    """Where the fused add + norm repays the host time of its Python autograd node: at no shape of the bench yet
+    (profiles/r10_add_norm_tm.txt, five runs).  The kernels of one forward + backward take 14-32 us of GPU time against 34-203 for
+    the ATen composition (mul, add, layer_norm, the consumer's cast and their backward: 8-11 launches) at the four stage shapes, but
+    back to back the call is host time, 92-98 us on a quiet host and up to 237 on a busy one, whatever the shape.  With an fp32
+    branch it wins at (61440, 64) in every run (0.52-0.54x) and loses below (1.12-1.24x); with the bf16 branch of the autocast step
+    it is level with the composition at the three smaller shapes (0.89-0.99x; three disturbed rows at 1.04, 1.23, 1.33) and at
+    (61440, 64), where the composition's own kernels take 190 us, it was 0.49x, 0.49x and 0.91x in three runs and 1.04x and 1.23x
+    in the other two.  The rule is "at or below the composition in every run", and `res` is fp32 in either case: no element
+    count qualifies."""
+    return False
+
+
+def _grad_rows(g, dtype, rows, C):
+    """A gradient in the kernel's dtype, as rows of C channels with one row stride -> (g, row stride)."""
+    if g.dtype != dtype:
+        g = g.to(dtype)
+    rs = _rows(g) if g.stride(-1) == 1 else None
+    if rs is None or rs[1] < C:
+        return g.contiguous(), C
+    return g, rs[1]
+
+
+def _add_norm_params(rows, C, branch_dtype, res_dtype, scale, eps=0.0, rms=False):
+    P = _lib.TokenAddNormParams()
+    P.struct_bytes = ctypes.sizeof(_lib.TokenAddNormParams)
+    P.rows, P.channels, P.eps, P.rms = rows, C, eps, int(rms)
+    P.btype = P.otype = ITYPE[branch_dtype]
+    P.rtype = ITYPE[res_dtype]
+    if scale is not None:
+        P.scale, P.rows_per_sample = scale.data_ptr(), rows // scale.shape[0]
+    return P
+
+
+class _AddNormTM(torch.autograd.Function):
+    """res may be None (h = scale * branch); `res_dtype` None then stores no sum: the norm reads the branch itself."""
+
+    @staticmethod
+    def forward(ctx, res, branch, weight, bias, scale, eps, rms, need_stats, rows, res_dtype):
+        n, res_stride, branch_stride = rows
+        C = branch.shape[-1]
+        P = _add_norm_params(n, C, branch.dtype, res_dtype or branch.dtype, scale, eps, rms)
+        P.branch, P.branch_row_stride = branch.data_ptr(), branch_stride
+        if res is not None:
+            P.res, P.res_row_stride = res.data_ptr(), res_stride
+        res_new = None
+        if res_dtype is not None:
+            res_new = _lib.empty(tuple(branch.shape), res_dtype, branch.device)
+            P.res_out, P.res_out_row_stride = res_new.data_ptr(), C
+        y = _lib.empty(tuple(branch.shape), branch.dtype, branch.device)
+        P.y, P.y_row_stride = y.data_ptr(), C
+        P.weight, P.bias = weight.data_ptr(), ptr(bias)
+        stats = None
+        if need_stats:                                                      # mean, rstd: only for a call a backward may follow
+            stats = _lib.empty((2, n), torch.float32, branch.device)
+            P.mean = stats.data_ptr()
+            P.rstd = P.mean + 4 * n
+        _lib.launch("vivim_token_add_norm_fwd", P, branch.device)
+        # the row the norm read: the stored sum, or the branch itself (its row stride then)
+        ctx.save_for_backward(res_new if res_new is not None else branch, weight, stats, scale)
+        ctx.h_stride = C if res_new is not None else branch_stride
+        ctx.eps, ctx.rms, ctx.has_bias, ctx.branch_dtype, ctx.has_res = eps, rms, bias is not None, branch.dtype, res is not None
+        ctx.set_materialize_grads(False)                                    # an unused output's gradient stays None: NULL in the struct
+        return res_new, y
+
+    @staticmethod
+    def backward(ctx, dres, dy):
+        if dres is None and dy is None:
+            return (None,) * 10
+        h, weight, stats, scale = ctx.saved_tensors
+        C, n = h.shape[-1], stats.shape[1]
+        P = _add_norm_params(n, C, ctx.branch_dtype, h.dtype, scale, ctx.eps, ctx.rms)
+        P.res_out, P.res_out_row_stride = h.data_ptr(), ctx.h_stride
+        P.weight, P.mean = weight.data_ptr(), stats.data_ptr()
+        P.rstd = P.mean + 4 * n
+        if dy is not None:
+            dy, P.dy_row_stride = _grad_rows(dy, ctx.branch_dtype, n, C)
+            P.dy = dy.data_ptr()
+        if dres is not None:
+            dres, P.dres_row_stride = _grad_rows(dres, h.dtype, n, C)
+            P.dres = dres.data_ptr()
+        need_res, need_branch = ctx.has_res and ctx.needs_input_grad[0], ctx.needs_input_grad[1]
+        # without a scale and in one dtype the two gradients are the same bits: written once
+        shared = scale is None and ctx.branch_dtype == h.dtype and (need_res or need_branch)
+        dres_in = dbranch = None
+        if need_res or shared:
+            dres_in = _lib.empty(tuple(h.shape), h.dtype, h.device)
+            P.dres_in, P.dres_in_row_stride = dres_in.data_ptr(), C
+        if need_branch and not shared:
+            dbranch = _lib.empty(tuple(h.shape), ctx.branch_dtype, h.device)
+            P.dbranch, P.dbranch_row_stride = dbranch.data_ptr(), C
+        need_w = dy is not None and ctx.needs_input_grad[2]
+        need_b = dy is not None and ctx.has_bias and ctx.needs_input_grad[3]
+        dwb = ws = None
+        if need_w or need_b:
+            dwb = _lib.empty((2, C), torch.float32, h.device)               # written by the slot sum: no zero fill
+            P.dweight = dwb.data_ptr() if need_w else None
+            P.dbias = dwb.data_ptr() + 4 * C if need_b else None
+            ws = _lib.empty((tm_workspace_slots(n) * 2 * C,), torch.float32, h.device)
+            P.workspace = ws.data_ptr()
+        _lib.launch("vivim_token_add_norm_bwd", P, h.device)
+        if shared:
+            dbranch = dres_in if need_branch else None
+            dres_in = dres_in if need_res else None
+        return (dres_in, dbranch, (dwb[0] if need_w else None), (dwb[1] if need_b else None)) + (None,) * 6
+
+
+class _AddTM(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, res, branch, scale, rows):
+        n, res_stride, branch_stride = rows
+        C = res.shape[-1]
+        P = _add_norm_params(n, C, branch.dtype, res.dtype, scale)
+        P.branch, P.branch_row_stride, P.res, P.res_row_stride = branch.data_ptr(), branch_stride, res.data_ptr(), res_stride
+        res_new = _lib.empty(tuple(res.shape), res.dtype, res.device)
+        P.res_out, P.res_out_row_stride = res_new.data_ptr(), C
+        _lib.launch("vivim_token_add_norm_fwd", P, res.device)
+        ctx.save_for_backward(scale)
+        ctx.branch_dtype, ctx.n = branch.dtype, n
+        return res_new
+
+    @staticmethod
+    def backward(ctx, dres):
+        scale, = ctx.saved_tensors
+        if not ctx.needs_input_grad[1]:
+            return dres, None, None, None
+        if scale is None and ctx.branch_dtype == dres.dtype:
+            return dres, dres, None, None                                   # both gradients are dres itself: no kernel
+        C = dres.shape[-1]
+        g, stride = _grad_rows(dres, dres.dtype, ctx.n, C)
+        P = _add_norm_params(ctx.n, C, ctx.branch_dtype, g.dtype, scale)
+        P.dres, P.dres_row_stride = g.data_ptr(), stride
+        dbranch = _lib.empty(tuple(g.shape), ctx.branch_dtype, g.device)
+        P.dbranch, P.dbranch_row_stride = dbranch.data_ptr(), C
+        _lib.launch("vivim_token_add_norm_bwd", P, g.device)
+        return dres, dbranch, None, None
+
+
+def _check_scale_tm(scale, res, rows):
+    if scale is None:
+        return
+    if not (scale.dtype == torch.float32 and scale.dim() == 1 and scale.shape[0] == res.shape[0] and scale.is_contiguous()
+            and scale.device == res.device and rows % scale.shape[0] == 0):
+        raise ValueError("scale must be a contiguous (res.shape[0],) float32 tensor on res's device")
+
+
+def _requires_grad(*ts):
+    return torch.is_grad_enabled() and any(t is not None and t.requires_grad for t in ts)
+
+
+def add_layer_norm_tm(res, branch, weight, bias, eps=1e-5, scale=None, out_dtype=None, rms=False, rows=None):
+    """(res + scale * branch in res's dtype, the LayerNorm -- rms: RMSNorm -- of that sum as stored, in branch's dtype) for
+    token-major rows.  `rows`: what tm_add_rows(res, branch, weight, bias) returned, from a caller that has just asked."""
+    if out_dtype is not None and out_dtype != branch.dtype:
+        raise ValueError(f"add_layer_norm_tm: a {branch.dtype} branch with a {out_dtype} output is not built")
+    if not tm_add_pair_ok(branch.dtype, res.dtype):
+        raise ValueError(f"add_layer_norm_tm: a {branch.dtype} branch on a {res.dtype} residual is not built")
+    if rows is None:
+        rows = tm_add_rows(res, branch, weight, bias)
+        if rows is None or weight is None:
+            raise ValueError("add_layer_norm_tm: unsupported tensors (tm_add_supported)")
+    _check_scale_tm(scale, res, rows[0])
+    return _AddNormTM.apply(res, branch, weight, bias, scale, eps, rms, _requires_grad(res, branch, weight, bias), rows, res.dtype)
+
+
+def add_tm(res, branch, scale=None, rows=None):
+    """res + scale * branch in res's dtype, contiguous, for token-major rows."""
+    if not tm_add_pair_ok(branch.dtype, res.dtype):
+        raise ValueError(f"add_tm: a {branch.dtype} branch on a {res.dtype} residual is not built")
+    if rows is None:
+        rows = tm_add_rows(res, branch)
+        if rows is None:
+            raise ValueError("add_tm: unsupported tensors (tm_add_supported)")
+    _check_scale_tm(scale, res, rows[0])
+    return _AddTM.apply(res, branch, scale, rows)
+
+
+def norm_tm_no_residual(x, weight, bias, eps, rms, res_dtype=None):
+    """(x in res_dtype or None, the norm of x in x's dtype): the first layer of a residual stream, which has nothing to add."""
+    rows = tm_add_rows(x, x, weight, bias)
+    if rows is None or weight is None:
+        raise ValueError("norm_tm_no_residual: unsupported tensors (tm_add_supported)")
+    if res_dtype is not None and not tm_add_pair_ok(x.dtype, res_dtype):
+        raise ValueError(f"norm_tm_no_residual: {x.dtype} rows with a {res_dtype} residual are not built")
+    return _AddNormTM.apply(None, x, weight, bias, None, eps, rms, _requires_grad(x, weight, bias), rows, res_dtype)
+
+
+def rms_norm_tm(x, weight, bias=None, eps=1e-5, out_dtype=None):
+    """RMSNorm of token-major rows: x * rsqrt(mean(x^2) + eps) * weight (+ bias), in x's dtype."""
+    if out_dtype is not None and out_dtype != x.dtype:
+        raise ValueError(f"rms_norm_tm: {x.dtype} rows with a {out_dtype} output are not built")
+    return norm_tm_no_residual(x, weight, bias, eps, True)[1]

@@ -49,19 +49,21 @@ def recall_focused_loss(logits, targets, num_classes, gamma=2.0, onehot=None, al
 
 
 def build_model(num_classes=3, device="cuda", mamba_kwargs=None, drop_path_rate=0.2, fast_backbone_dwconv=True,
-                fused_upsample=False, fused_decode_head=False, fast_backbone_layernorm=False):
+                fused_upsample=False, fused_decode_head=False, fast_backbone_layernorm=False, fused_backbone_add_norm=False):
     """Vivim with a randomly initialised SegFormer-b3 backbone (no hub access on the GPU box).  The two
     parameter groups that never receive a gradient in Vivim's forward -- the SegFormer 150-class classifier
     and the per-stage encoder layer norms (vivim.py:211-212, 325) -- are frozen so DDP needs no
     unused-parameter search.  `fused_upsample` is Vivim's: the decode head's upsampling through csrc/upsample.hip; so is
     `fused_decode_head`: the eval-mode, no-grad decode head through csrc/decode_head.hip (decode_head.py), and
     `fast_backbone_layernorm`: the SegFormer patch embeddings' and blocks' LayerNorms through csrc/layernorm.hip and
-    csrc/token_layernorm.hip."""
+    csrc/token_layernorm.hip, and `fused_backbone_add_norm`: the SegFormer blocks' residual adds fused with the LayerNorm that
+    reads the sum (vivim._run_stage)."""
     from .vivim import Vivim, segformer_b3_random
     model = Vivim(in_chans=3, out_chans=num_classes, backbone=segformer_b3_random(),
                   drop_path_rate=drop_path_rate, mamba_kwargs=mamba_kwargs,
                   fast_backbone_dwconv=fast_backbone_dwconv, fused_upsample=fused_upsample,
-                  fused_decode_head=fused_decode_head, fast_backbone_layernorm=fast_backbone_layernorm)
+                  fused_decode_head=fused_decode_head, fast_backbone_layernorm=fast_backbone_layernorm,
+                  fused_backbone_add_norm=fused_backbone_add_norm)
     from .dp import freeze_unused
     freeze_unused(model)
     return model.to(device)

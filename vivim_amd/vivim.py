@@ -28,6 +28,10 @@ Differences from the reference, all additive:
     patch-embedding norms read `conv_out.flatten(2).transpose(1, 2)`) through csrc/layernorm.hip, token-major rows (the blocks'
     layernorm_before / layernorm_after, and the sequence-reduction norms when their conv returns channels-last memory) through
     csrc/token_layernorm.hip; under autocast the norms inside the blocks write the autocast dtype their consumers would cast to.  Same Parameters, state-dict keys unchanged; off by default, `VIVIM_NO_FUSED_LAYERNORM=1` opts out again.
+  * `mamba_block(..., fused_backbone_add_norm=True)` (also on Vivim and train_step.build_model) runs the SegFormer blocks of a
+    stage with every residual add fused with the LayerNorm that reads the sum (`_run_stage`; layernorm.add_layer_norm_tm /
+    add_tm, csrc/token_layernorm.hip): DropPath is a per-sample factor inside the kernel, the stream is read and written once
+    per site.  Same Parameters and keys; off by default, `VIVIM_NO_FUSED_LAYERNORM=1` opts out again.
   * timm is not required: DropPath / trunc_normal_ are the torch equivalents.
 """
 import math
@@ -323,16 +327,94 @@ def _run_block(blk, hs, height, width):
     return out[0] if isinstance(out, (tuple, list)) else out
 
 
+def _block_norms(blk):
+    """(the norm in front of the attention, the norm in front of the Mix-FFN) of a SegFormer block in either transformers
+    layout, or None for a block of another form."""
+    for first, second in (("layernorm_before", "layernorm_after"), ("layer_norm_1", "layer_norm_2")):
+        n1, n2 = getattr(blk, first, None), getattr(blk, second, None)
+        if isinstance(n1, nn.LayerNorm) and isinstance(n2, nn.LayerNorm):
+            ok = all(isinstance(getattr(blk, name, None), nn.Module) for name in ("attention", "mlp", "drop_path"))
+            return (n1, n2) if ok else None
+    return None
+
+
+def _add_rows(res, branch, drop_path, norm=None):
+    """What layernorm.tm_add_rows says when the site `drop_path(branch) + res` (followed by `norm`) can take the fused kernels and
+    they pay, else None: the caller then runs the stock composition."""
+    if not isinstance(drop_path, (DropPath, nn.Identity)):
+        return None
+    w = b = None
+    if norm is not None:
+        w, b = norm.weight, norm.bias
+        if w is None or len(norm.normalized_shape) != 1:
+            return None
+        # the norm writes what its consumers (Linears, Convs) read: the autocast dtype under CUDA autocast, else the stream's own
+        want = torch.get_autocast_dtype("cuda") if res.is_cuda and torch.is_autocast_enabled("cuda") else res.dtype
+        if branch.dtype != want:
+            return None
+    rows = _ln.tm_add_rows(res, branch, w, b)
+    return rows if rows is not None and _ln.tm_add_worthwhile(res) else None
+
+
+def _add_norm_site(res, branch, drop_path, norm):
+    """(h, norm(h)) for h = drop_path(branch) + res: one kernel where layernorm.add_layer_norm_tm applies."""
+    rows = _add_rows(res, branch, drop_path, norm)
+    if rows is None:
+        h = drop_path(branch) + res
+        return h, norm(h)
+    scale = drop_path.sample_scale(branch) if isinstance(drop_path, DropPath) else None
+    return _ln.add_layer_norm_tm(res, branch, norm.weight, norm.bias, norm.eps, scale=scale, rows=rows)
+
+
+def _add_site(res, branch, drop_path):
+    """drop_path(branch) + res, the last add of a stage."""
+    rows = _add_rows(res, branch, drop_path)
+    if rows is None:
+        return drop_path(branch) + res
+    scale = drop_path.sample_scale(branch) if isinstance(drop_path, DropPath) else None
+    return _ln.add_tm(res, branch, scale=scale, rows=rows)
+
+
+def _run_stage(blocks, hs, height, width):
+    """The SegFormer blocks of one stage with every residual add fused with the LayerNorm that reads the sum
+    (mamba_block(fused_backbone_add_norm=True)): SegformerLayer.forward restated on the block's own submodules.  A block's
+    second add waits for the next block's first norm; the stage's last add runs alone; the stage's first norm is a module call.
+    A block of another form runs as _run_block."""
+    pending = None                                       # (residual, branch, drop_path): an add that has not run yet
+    for blk in blocks:
+        norms = _block_norms(blk)
+        if norms is None:
+            if pending is not None:
+                hs, pending = _add_site(*pending), None
+            hs = _run_block(blk, hs, height, width)
+            continue
+        if pending is None:
+            y = norms[0](hs)
+        else:
+            hs, y = _add_norm_site(*pending, norms[0])
+        branch = blk.attention(y, height, width)
+        if isinstance(branch, (tuple, list)):
+            branch = branch[0]
+        dropout = getattr(blk, "hidden_dropout", None)
+        if dropout is not None:
+            branch = dropout(branch)
+        hs, y = _add_norm_site(hs, branch, blk.drop_path, norms[1])
+        pending = (hs, blk.mlp(y, height, width), blk.drop_path)
+    return hs if pending is None else _add_site(*pending)
+
+
 class mamba_block(nn.Module):
     """SegFormer encoder stages interleaved with MambaLayer stages (modeling/vivim.py:163-231)."""
 
     def __init__(self, backbone, in_chans=1, depths=[2, 2, 2, 2], dims=[64, 128, 320, 512],
                  drop_path_rate=0.0, layer_scale_init_value=1e-6, out_indices=[0, 1, 2, 3], mamba_kwargs=None,
-                 fast_backbone_dwconv=False, fast_backbone_layernorm=False):
+                 fast_backbone_dwconv=False, fast_backbone_layernorm=False, fused_backbone_add_norm=False):
         super().__init__()
         self.downsample_layers = _Encoder(backbone)
+        self.fused_backbone_add_norm = fused_backbone_add_norm
         if fast_backbone_dwconv:
             _swap_backbone_dwconv(self.downsample_layers)
+        if fast_backbone_dwconv or fused_backbone_add_norm:
             _swap_backbone_droppath(self.downsample_layers)
         if fast_backbone_layernorm:
             _swap_backbone_layernorm(self.downsample_layers)
@@ -352,8 +434,11 @@ class mamba_block(nn.Module):
         enc = self.downsample_layers
         for embed, blocks, _norm, mam_stage in zip(enc.patch_embeddings, enc.block, enc.layer_norm, self.stages):
             hs, height, width = embed(hs)
-            for blk in blocks:
-                hs = _run_block(blk, hs, height, width)
+            if self.fused_backbone_add_norm and not os.environ.get("VIVIM_NO_FUSED_LAYERNORM"):
+                hs = _run_stage(blocks, hs, height, width)
+            else:
+                for blk in blocks:
+                    hs = _run_block(blk, hs, height, width)
             # (the stage layer norm is skipped on purpose, vivim.py:211-212)
             hs = hs.reshape(bz * nf, height, width, -1).permute(0, 3, 1, 2).contiguous()
             hs = hs.reshape(bz, nf, *hs.shape[-3:]).transpose(1, 2)             # (B, C, nf, H, W)
@@ -389,7 +474,8 @@ class Vivim(nn.Module):
                  drop_path_rate=0.2, layer_scale_init_value=1e-6, hidden_size: int = 768, norm_name="instance",
                  conv_block: bool = True, res_block: bool = True, spatial_dims=2, with_edge=False,
                  dropout_rate=0.3, backbone=None, mamba_kwargs=None, fast_backbone_dwconv=False,
-                 fused_upsample=False, fused_decode_head=False, fast_backbone_layernorm=False) -> None:
+                 fused_upsample=False, fused_decode_head=False, fast_backbone_layernorm=False,
+                 fused_backbone_add_norm=False) -> None:
         super().__init__()
         self.fused_upsample = fused_upsample
         self.fused_decode_head = fused_decode_head
@@ -406,7 +492,8 @@ class Vivim(nn.Module):
         self.encoder = mamba_block(backbone, in_chans, depths=depths, dims=feat_size,
                                    drop_path_rate=drop_path_rate, mamba_kwargs=mamba_kwargs,
                                    fast_backbone_dwconv=fast_backbone_dwconv,
-                                   fast_backbone_layernorm=fast_backbone_layernorm)
+                                   fast_backbone_layernorm=fast_backbone_layernorm,
+                                   fused_backbone_add_norm=fused_backbone_add_norm)
         self.decoder = backbone.decode_head
         self.feature_dropout = nn.Dropout2d(dropout_rate)
         self.out = nn.Conv2d(768, out_chans, kernel_size=1)
