@@ -528,6 +528,62 @@ typedef struct {
     void *workspace;                                 /* backward scratch (see above) */
 } vivim_token_add_norm_params;
 
+/* ---- Fused clip + AdamW step (csrc/optimizer.hip; vivim_amd/optimizer.py: FusedStepAdamW, opt-in) ----------------------------
+ * The optimizer end of a train step without a host synchronisation: unscale, non-finite detection, global L2 norm, clipping,
+ * AdamW with decoupled weight decay, the step counter and GradScaler's dynamic loss scale.  All tensors are dense fp32.
+ *
+ * The record (`state`): VIVIM_OPT_STATE_WORDS 4-byte words on the device, owned by the caller, zero except word 0 at the start:
+ *   0 f32 loss scale (65536 for fp16 training, 1 otherwise)   1 i32 growth counter (good scaled steps since the last change)
+ *   2 i32 step count t (steps applied, shared by all tensors) 3 f32 total norm of the unscaled gradients, last statistics pass
+ *   4 i32 found_inf of the last step                          5 f32 factor every gradient of the last step was multiplied with
+ *   6 f32 bc1 = 1 - beta1^t                                   7 f32 bc2s = sqrt(1 - beta2^t)
+ *   8 i32 skipped steps                                       9 f32 clip coefficient of the last step     10 .. 15 reserved (0)
+ *
+ * The tables.  `params`, `exp_avg`, `exp_avg_sq` are DEVICE arrays of device pointers, one entry per tensor of the whole list;
+ * `block_map` is a DEVICE array of total_blocks (tensor, chunk) int32 pairs, tensors ascending: workgroup b works on elements
+ * chunk * VIVIM_OPT_CHUNK .. of its tensor.  They change only when a tensor moves and are built once.  The gradients' addresses
+ * change every step: `grads` and `numel` are HOST arrays of `count` entries for tensors first_tensor .. first_tensor + count - 1,
+ * copied into the kernel arguments of the launch (at most VIVIM_OPT_MAX_TENSORS per call, under 4 KB; nothing is staged, the
+ * arrays may be reused as soon as the call returns).  A longer list is cut into several calls, each with the map rows
+ * first_block .. first_block + n_blocks - 1 of its own tensors.  A NULL gradient leaves its tensor out of the step.
+ *
+ *   vivim_opt_grad_stats: per map row, sum (g * inv_scale)^2 in fp32 (inv_scale = 1 / record[0] when `scaled`, else 1; a
+ *     thread's chain is 16 additions, then a wave and a workgroup sum) and whether any g is inf / nan, STORED into slot
+ *     `row` of the workspace (2 words per row; vivim_opt_step_workspace_bytes = 8 * total_blocks).  No atomics.
+ *   vivim_opt_finalise (one workgroup): adds slots 0 .. total_blocks - 1 in a fixed order in fp64; norm = sqrt(sum);
+ *     found_inf = any flag or a non-finite sum; clip = has_max_norm ? min(1, max_norm / (norm + 1e-6)) : 1;
+ *     factor = found_inf ? 0 : inv_scale * clip; unless found_inf: t += 1, bc1 and bc2s recomputed in fp64; else skipped += 1.
+ *     When `scaled`: found_inf halves the scale and zeroes the growth counter, otherwise the counter is incremented and at
+ *     2000 the scale is doubled and the counter zeroed.  total_blocks = 0: no statistics pass was made -- found_inf = 0,
+ *     clip = 1, factor = inv_scale, the norm is left as it was; t, bc1, bc2s advance.
+ *   vivim_opt_adamw: nothing is written when record[4] is set; otherwise per element, fp32, one rounding per stored value:
+ *     g' = g * factor;  m' = m + (1 - beta1)(g' - m);  v' = beta2 v + (1 - beta2) g'^2;
+ *     p' = p (1 - lr * weight_decay) - (lr / bc1) * m' / (sqrt(v') / bc2s + eps).
+ *     The constants (1 - beta1), (1 - beta2), (1 - lr * weight_decay) are formed in double and rounded once.
+ * 16-byte accesses where the addresses of a chunk are 16-byte aligned, element accesses otherwise and for a chunk's tail.
+ * Everything is bit-repeatable.  No vivim_sizeof row: the caller sets struct_bytes = sizeof(vivim_opt_step_params). */
+#define VIVIM_OPT_CHUNK 4096           /* elements per workgroup and map row */
+#define VIVIM_OPT_MAX_TENSORS 248      /* tensors per call */
+#define VIVIM_OPT_STATE_WORDS 16
+typedef struct {
+    int32_t struct_bytes;                            /* sizeof(vivim_opt_step_params) as the caller compiled it */
+    int32_t count;                                   /* tensors of this call: 1 .. VIVIM_OPT_MAX_TENSORS */
+    int32_t first_tensor;                            /* their position in the device tables */
+    int32_t first_block, n_blocks;                   /* this call's rows of block_map */
+    int32_t total_blocks;                            /* rows of block_map = slots of the workspace, all calls of a step together */
+    int32_t scaled;                                  /* gradients carry the loss scale: unscale, run the scale policy */
+    int32_t has_max_norm;
+    double max_norm;
+    double lr, beta1, beta2, eps, weight_decay;
+    const void *const *grads;                        /* HOST array [count] of device pointers; NULL = no gradient this step */
+    const int64_t *numel;                            /* HOST array [count], each > 0 */
+    const void *params, *exp_avg, *exp_avg_sq;       /* DEVICE arrays of device pointers */
+    const void *block_map;                           /* DEVICE int32 [total_blocks][2] */
+    void *state;                                     /* DEVICE record */
+    void *workspace;                                 /* DEVICE, 8 * total_blocks bytes, 8-byte aligned */
+    int64_t workspace_bytes;
+} vivim_opt_step_params;
+
 int vivim_abi_version(void);
 const char *vivim_last_error(void);
 
@@ -597,6 +653,10 @@ size_t vivim_token_layernorm_bwd_workspace_bytes(const vivim_token_layernorm_par
 int vivim_token_add_norm_fwd(const vivim_token_add_norm_params *p, void *stream);   /* writes res_out (+ y, mean, rstd) */
 int vivim_token_add_norm_bwd(const vivim_token_add_norm_params *p, void *stream);   /* writes dres_in, dbranch (+ dweight, dbias) */
 size_t vivim_token_add_norm_bwd_workspace_bytes(const vivim_token_add_norm_params *p);   /* from rows, channels; 0 on bad sizes */
+int vivim_opt_grad_stats(const vivim_opt_step_params *p, void *stream);   /* reads the gradients, writes this call's slots */
+int vivim_opt_finalise(const vivim_opt_step_params *p, void *stream);     /* reads the slots, updates the record */
+int vivim_opt_adamw(const vivim_opt_step_params *p, void *stream);        /* reads the record and g, updates p, m, v */
+size_t vivim_opt_step_workspace_bytes(const vivim_opt_step_params *p);    /* from total_blocks; 0 on bad sizes */
 
 /* Deterministic backward (for torch.use_deterministic_algorithms).  Same parameters, checks and results as
  * vivim_selective_scan_bwd, and the same kernel family, but every gradient that the default call adds up across

@@ -1,10 +1,12 @@
 """Kernel launches of one tri-directional Mamba block (forward + backward, bf16 autocast, stage-0 shape of the bench) and of
 one whole train step, by kernel name -- the step is host-bound, so launches are what it pays for.
     python tools/launch_count.py [--dim 64] [--batch 3] [--frames 5] [--hw 4096] [--step] [--fused-loss] [--backbone-layernorm]
-                                  [--backbone-add-norm]
+                                  [--backbone-add-norm] [--fp16] [--clip-grad-norm X] [--fused-optimizer]
 --fused-loss (with --step) counts the step with train_step(fused_loss=True) as well, and the loss alone (forward + backward on
 the step's logits shape) both ways.  --backbone-layernorm (with --step) builds the model with fast_backbone_layernorm=True,
---backbone-add-norm with fused_backbone_add_norm=True."""
+--backbone-add-norm with fused_backbone_add_norm=True.  --fp16 and --clip-grad-norm X (with --step) count the step under fp16
+autocast with the dynamic loss scale and with gradient clipping; --fused-optimizer counts that step with
+make_optimizer(fused_step=True) as well (the optimizer phase on the device: csrc/optimizer.hip)."""
 import argparse
 import collections
 import os
@@ -48,6 +50,9 @@ def main():
     ap.add_argument("--fused-loss", action="store_true")
     ap.add_argument("--backbone-layernorm", action="store_true")
     ap.add_argument("--backbone-add-norm", action="store_true")
+    ap.add_argument("--fp16", action="store_true")
+    ap.add_argument("--clip-grad-norm", type=float, default=None)
+    ap.add_argument("--fused-optimizer", action="store_true")
     a = ap.parse_args()
     dev = torch.device("cuda:0")
     from vivim_amd.mamba_simple import Mamba
@@ -66,10 +71,20 @@ def main():
         opt = ts.make_optimizer(model)
         clip, onehot = ts.synthetic_batch(a.batch, a.frames, 256, 3, dev, 0)
 
+        amp = torch.float16 if a.fp16 else torch.bfloat16
+        how = ("fp16" if a.fp16 else "bf16") + ("" if a.clip_grad_norm is None else f", clip_grad_norm={a.clip_grad_norm:g}")
+
         def step():
-            ts.train_step(model, opt, clip, onehot, 3, torch.bfloat16)
-        show("train step" + (", fast_backbone_layernorm=True" if a.backbone_layernorm else "")
+            ts.train_step(model, opt, clip, onehot, 3, amp, clip_grad_norm=a.clip_grad_norm)
+        show(f"train step, {how}" + (", fast_backbone_layernorm=True" if a.backbone_layernorm else "")
              + (", fused_backbone_add_norm=True" if a.backbone_add_norm else ""), *launches(step), top=60)
+        if a.fused_optimizer:
+            fused_opt = ts.make_optimizer(model, fused_step=True)
+
+            def step_fused_opt():
+                ts.train_step(model, fused_opt, clip, onehot, 3, amp, clip_grad_norm=a.clip_grad_norm)
+            show(f"train step, {how}, make_optimizer(fused_step=True): {fused_opt.launches_per_step} optimizer launches",
+                 *launches(step_fused_opt), top=60)
         if a.fused_loss:
             from vivim_amd.seg_loss import recall_focused_loss_fused
 

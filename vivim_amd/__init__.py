@@ -20,4 +20,7 @@ def __getattr__(name):
     if name in ("fused_decode_head", "fold_decode_head"):     # the eval-mode decode head (decode_head.py), likewise
         from . import decode_head
         return getattr(decode_head, name)
+    if name == "FusedStepAdamW":                       # the device-side clip + AdamW step (optimizer.py), likewise
+        from . import optimizer
+        return optimizer.FusedStepAdamW
     raise AttributeError(f"module {__name__!r} has no attribute {name!r}")

@@ -182,6 +182,20 @@ class TokenAddNormParams(ctypes.Structure):
                                      "dres_in", "dbranch", "dweight", "dbias", "workspace")])
 
 
+OPT_CHUNK, OPT_MAX_TENSORS, OPT_STATE_WORDS = 4096, 248, 16          # VIVIM_OPT_* of the header
+
+
+class OptStepParams(ctypes.Structure):
+    """As TokenLayerNormParams: no vivim_sizeof row, not in STRUCTS, its sizeof stated in struct_bytes.  `grads` and `numel` are
+    host arrays of `count` entries; the tables, the record and the workspace are device memory."""
+    _fields_ = ([(n, i32) for n in ("struct_bytes", "count", "first_tensor", "first_block", "n_blocks", "total_blocks", "scaled",
+                                    "has_max_norm")]
+                + [(n, ctypes.c_double) for n in ("max_norm", "lr", "beta1", "beta2", "eps", "weight_decay")]
+                + [("grads", ctypes.POINTER(vp)), ("numel", ctypes.POINTER(i64))]
+                + [(n, vp) for n in ("params", "exp_avg", "exp_avg_sq", "block_map", "state", "workspace")]
+                + [("workspace_bytes", i64)])
+
+
 # The structs in vivim_sizeof order.
 STRUCTS = (SsmFwdParams, SsmBwdParams, ConvFwdParams, ConvBwdParams, DwConvParams, DwConvWgradParams, DirParams,
            ConvUpdateParams, StateUpdateParams, LayerNormParams, WgradNtParams, AddLayerNormParams, SegLossParams,
@@ -249,6 +263,10 @@ ENTRY_POINTS = {
     "vivim_token_add_norm_fwd": Entry(None, (ctypes.POINTER(TokenAddNormParams),), True, _int),
     "vivim_token_add_norm_bwd": Entry(None, (ctypes.POINTER(TokenAddNormParams),), True, _int),
     "vivim_token_add_norm_bwd_workspace_bytes": Entry(None, (ctypes.POINTER(TokenAddNormParams),), False, _size),
+    "vivim_opt_grad_stats": Entry(None, (ctypes.POINTER(OptStepParams),), True, _int),
+    "vivim_opt_finalise": Entry(None, (ctypes.POINTER(OptStepParams),), True, _int),
+    "vivim_opt_adamw": Entry(None, (ctypes.POINTER(OptStepParams),), True, _int),
+    "vivim_opt_step_workspace_bytes": Entry(None, (ctypes.POINTER(OptStepParams),), False, _size),
 }
 EXPORTS = tuple(ENTRY_POINTS)
 
@@ -299,6 +317,11 @@ def algorithmic_bytes(name, P):
     moves the bytes of its default twin."""
     name = name.removesuffix("_det")
     f = P.f if isinstance(P, (SsmBwdParams, ConvBwdParams)) else P       # the forward half of a backward struct
+    if name.startswith("vivim_opt"):                                    # g once | the slots | p, m, v read and written, g read
+        if name.endswith("finalise"):
+            return 8 * P.total_blocks + 4 * OPT_STATE_WORDS
+        n = sum(P.numel[i] for i in range(P.count) if P.grads[i])
+        return 4 * n + 8 * P.n_blocks if name.endswith("stats") else 28 * n
     if name.startswith("vivim_add_layernorm"):
         n = P.batch * P.seqlen * P.channels
         if not P.weight:                                               # add-only: x, branch, x_new / dres, dbranch

@@ -54,6 +54,9 @@ size_t token_layernorm_bwd_workspace_bytes(const vivim_token_layernorm_params&);
 bool token_add_norm_dispatch(const vivim_token_add_norm_params&, bool bwd, hipStream_t);       // the same file, with the residual add
 bool token_add_norm_pair_ok(int btype, int rtype);
 size_t token_add_norm_bwd_workspace_bytes(const vivim_token_add_norm_params&);
+void opt_grad_stats_launch(const vivim_opt_step_params&, hipStream_t);                        // optimizer.hip
+void opt_finalise_launch(const vivim_opt_step_params&, hipStream_t);
+void opt_adamw_launch(const vivim_opt_step_params&, hipStream_t);
 }  // namespace vivim
 
 static thread_local char g_err[512] = "";
@@ -802,6 +805,77 @@ int vivim_token_add_norm_bwd(const vivim_token_add_norm_params* p, void* stream)
     if (!q.dweight && !q.dbias) q.workspace = nullptr;               // nothing to sum: the kernel stores no slot
     if (!vivim::token_add_norm_dispatch(q, true, as_stream(stream)))
         return fail(VIVIM_ERR_UNSUPPORTED, "%s not implemented for branch type %d / residual type %d", fn, p->btype, p->rtype);
+    return after_launch(fn);
+}
+
+// ---- fused clip + AdamW step (optimizer.hip)
+static int check_opt_common(const vivim_opt_step_params* p, const char* fn) {
+    VCHECK(p != nullptr);
+    if (p->struct_bytes != (int32_t)sizeof(vivim_opt_step_params))
+        return fail(VIVIM_ERR_INVALID, "%s: struct_bytes = %d, this library's vivim_opt_step_params has %zu", fn, p->struct_bytes,
+                    sizeof(vivim_opt_step_params));
+    VCHECK(p->state != nullptr && aligned(p->state, 4));
+    if (p->total_blocks < 0) return fail(VIVIM_ERR_INVALID, "%s: total_blocks = %d", fn, p->total_blocks);
+    return VIVIM_OK;
+}
+
+// the tensors and map rows of one multi-tensor call
+static int check_opt_tensors(const vivim_opt_step_params* p, const char* fn) {
+    if (p->count <= 0 || p->count > VIVIM_OPT_MAX_TENSORS)
+        return fail(VIVIM_ERR_INVALID, "%s: count = %d, a call takes 1 to %d tensors", fn, p->count, VIVIM_OPT_MAX_TENSORS);
+    VCHECK(p->grads != nullptr && p->numel != nullptr && p->block_map != nullptr);
+    VCHECK(aligned(p->block_map, 4) && p->first_tensor >= 0);
+    for (int i = 0; i < p->count; ++i) {
+        if (p->numel[i] <= 0) return fail(VIVIM_ERR_INVALID, "%s: numel[%d] = %lld", fn, i, (long long)p->numel[i]);
+        VCHECK(aligned(p->grads[i], 4));
+    }
+    if (p->first_block < 0 || p->n_blocks <= 0 || (int64_t)p->first_block + p->n_blocks > p->total_blocks)
+        return fail(VIVIM_ERR_INVALID, "%s: map rows %d .. %d + %d of %d", fn, p->first_block, p->first_block, p->n_blocks, p->total_blocks);
+    return VIVIM_OK;
+}
+
+static int check_opt_workspace(const vivim_opt_step_params* p, const char* fn) {
+    const size_t need = 8 * (size_t)p->total_blocks;
+    if (need && (p->workspace == nullptr || !aligned(p->workspace, 8) || p->workspace_bytes < (int64_t)need))
+        return bad_workspace(fn, "vivim_opt_step_workspace_bytes", (long long)p->workspace_bytes, p->workspace, 8, need);
+    return VIVIM_OK;
+}
+
+size_t vivim_opt_step_workspace_bytes(const vivim_opt_step_params* p) {
+    return p && p->struct_bytes == (int32_t)sizeof(vivim_opt_step_params) && p->total_blocks > 0 ? 8 * (size_t)p->total_blocks : 0;
+}
+
+int vivim_opt_grad_stats(const vivim_opt_step_params* p, void* stream) {
+    const char* fn = "opt_grad_stats";
+    if (int rc = check_opt_common(p, fn)) return rc;
+    if (int rc = check_opt_tensors(p, fn)) return rc;
+    if (int rc = check_opt_workspace(p, fn)) return rc;
+    vivim::opt_grad_stats_launch(*p, as_stream(stream));
+    return after_launch(fn);
+}
+
+int vivim_opt_finalise(const vivim_opt_step_params* p, void* stream) {
+    const char* fn = "opt_finalise";
+    if (int rc = check_opt_common(p, fn)) return rc;
+    if (!(p->beta1 >= 0.0 && p->beta1 < 1.0 && p->beta2 >= 0.0 && p->beta2 < 1.0))
+        return fail(VIVIM_ERR_INVALID, "%s: betas = (%g, %g), each must be in [0, 1)", fn, p->beta1, p->beta2);
+    if (p->has_max_norm && !(p->max_norm >= 0.0)) return fail(VIVIM_ERR_INVALID, "%s: max_norm = %g", fn, p->max_norm);
+    if (int rc = check_opt_workspace(p, fn)) return rc;
+    vivim::opt_finalise_launch(*p, as_stream(stream));
+    return after_launch(fn);
+}
+
+int vivim_opt_adamw(const vivim_opt_step_params* p, void* stream) {
+    const char* fn = "opt_adamw";
+    if (int rc = check_opt_common(p, fn)) return rc;
+    VCHECK(p->params != nullptr && p->exp_avg != nullptr && p->exp_avg_sq != nullptr);
+    VCHECK(aligned(p->params, 8) && aligned(p->exp_avg, 8) && aligned(p->exp_avg_sq, 8));
+    if (int rc = check_opt_tensors(p, fn)) return rc;
+    if (!(p->beta1 >= 0.0 && p->beta1 < 1.0 && p->beta2 >= 0.0 && p->beta2 < 1.0))
+        return fail(VIVIM_ERR_INVALID, "%s: betas = (%g, %g), each must be in [0, 1)", fn, p->beta1, p->beta2);
+    if (!(p->lr >= 0.0 && p->eps >= 0.0 && p->weight_decay >= 0.0))
+        return fail(VIVIM_ERR_INVALID, "%s: lr = %g, eps = %g, weight_decay = %g: none may be negative", fn, p->lr, p->eps, p->weight_decay);
+    vivim::opt_adamw_launch(*p, as_stream(stream));
     return after_launch(fn);
 }
 

@@ -1,0 +1,296 @@
+// optimizer.hip -- the optimizer end of the train step on the device: unscale, non-finite detection, global L2 norm, clipping,
+// AdamW, the step counter and GradScaler's loss-scale policy, in a handful of launches and without a host synchronisation
+// (include/vivim_hip.h: vivim_opt_step_params; the Python side is vivim_amd/optimizer.py: FusedStepAdamW).
+//
+// Three kernels.  opt_grad_stats_kernel and opt_adamw_kernel are multi-tensor: workgroup b of a launch looks up row
+// first_block + b of the block map (tensor, chunk) -- a device table built once -- and works on VIVIM_OPT_CHUNK consecutive
+// elements of that tensor.  What changes every step, the gradients' addresses, travels in the kernel arguments: a by-value
+// table of at most VIVIM_OPT_MAX_TENSORS (pointer, element count) pairs, copied by the launch itself, so there is no staging
+// buffer whose lifetime anyone has to manage; a longer parameter list is cut into several launches by the caller.
+//   opt_grad_stats_kernel: x = g * inv_scale (inv_scale = 1 / loss scale from the record, a power of two: exact), a thread adds
+//     its 16 squares in one fp32 chain, wave sum, one LDS step, and the workgroup STORES (sum, any non-finite g) into its own
+//     slot of the workspace.  No atomics; every slot is written by exactly one workgroup of the step.
+//   opt_finalise_kernel (one workgroup): adds the slots in fixed order in fp64, writes the norm, found_inf, the clip
+//     coefficient and the factor every gradient is multiplied with, advances t and the two bias corrections unless the step
+//     is skipped, and runs the loss-scale policy (halve on overflow; double after 2000 good steps).
+//   opt_adamw_kernel: returns at once when found_inf is set; otherwise the decoupled-weight-decay update in fp32 with one
+//     rounding per stored value.  16-byte accesses where the four addresses of a chunk allow, element accesses otherwise
+//     (Mamba's per-direction Parameters are rows of a stacked buffer and need not be 16-byte aligned), and for a chunk's tail.
+// A tensor whose gradient pointer is NULL is left out of the step: its slots are written as (0, 0), its state is not touched.
+#include <math.h>
+#include "common.cuh"
+
+namespace vivim {
+
+constexpr int kOptThreads = 256;                                       // 4 waves per workgroup
+constexpr int kOptVec = 4;                                             // floats per 16-byte access
+constexpr int kOptIters = VIVIM_OPT_CHUNK / (kOptThreads * kOptVec);   // accesses per thread and tensor
+static_assert(kOptIters * kOptThreads * kOptVec == VIVIM_OPT_CHUNK, "a chunk is a whole number of 16-byte accesses per thread");
+static_assert(kOptIters * kOptVec <= 256, "a thread's chain of additions is at most 256 long");
+constexpr int kOptGrowthInterval = 2000;                               // GradScaler's growth_interval
+
+// the record's words (include/vivim_hip.h)
+enum { kOsScale = 0, kOsGrowth, kOsStep, kOsNorm, kOsFoundInf, kOsFactor, kOsBc1, kOsBc2s, kOsSkipped, kOsClip };
+
+struct OptArgs {                       // the kernel arguments of the two multi-tensor kernels
+    int32_t first_tensor, count, first_block, scaled;
+    float* const* p;                   // device tables, one entry per tensor of the whole list
+    float* const* m;
+    float* const* v;
+    const int32_t* block_map;          // device: (tensor, chunk) per workgroup of the whole list
+    uint32_t* state;
+    float* workspace;
+    float lr, omb1, b2, omb2, eps, decay;
+    const float* g[VIVIM_OPT_MAX_TENSORS];      // this launch's tensors: first_tensor .. first_tensor + count - 1
+    int64_t n[VIVIM_OPT_MAX_TENSORS];
+};
+static_assert(sizeof(OptArgs) <= 4096, "the by-value table must fit 4 KB of kernel arguments");
+
+struct OptFinArgs {
+    uint32_t* state;
+    const float* workspace;
+    int32_t total_blocks, scaled, has_max_norm, _pad;
+    double max_norm, beta1, beta2;
+};
+
+// -> this workgroup's tensor of the launch (or -1), its first element and how many of the chunk exist
+__device__ __forceinline__ int opt_locate(const OptArgs& a, int blk, int64_t& off, int& nb) {
+    const int ti = __builtin_amdgcn_readfirstlane(a.block_map[2 * (int64_t)blk]);
+    const int chunk = __builtin_amdgcn_readfirstlane(a.block_map[2 * (int64_t)blk + 1]);
+    const int li = ti - a.first_tensor;
+    if (li < 0 || li >= a.count || chunk < 0) return -1;             // a map row of another launch: nothing to do
+    off = (int64_t)chunk * VIVIM_OPT_CHUNK;
+    const int64_t rem = a.n[li] - off;
+    if (rem <= 0 || a.g[li] == nullptr) return -1;
+    nb = (int)(rem < VIVIM_OPT_CHUNK ? rem : VIVIM_OPT_CHUNK);
+    return li;
+}
+
+__device__ __forceinline__ bool opt_aligned16(const void* q) { return (reinterpret_cast<uintptr_t>(q) & 15) == 0; }
+
+// 4 consecutive floats from q[i..]: one 16-byte load when `vec` and all four exist, else the existing ones; the rest read as 0
+__device__ __forceinline__ void opt_load4(const float* __restrict__ q, int i, int nb, bool vec, float (&x)[kOptVec]) {
+    if (vec && i + kOptVec <= nb) {
+        const float4 t = *reinterpret_cast<const float4*>(q + i);
+        x[0] = t.x; x[1] = t.y; x[2] = t.z; x[3] = t.w;
+    } else {
+#pragma unroll
+        for (int k = 0; k < kOptVec; ++k) x[k] = i + k < nb ? q[i + k] : 0.0f;
+    }
+}
+
+__device__ __forceinline__ void opt_store4(float* __restrict__ q, int i, int nb, bool vec, const float (&x)[kOptVec]) {
+    if (vec && i + kOptVec <= nb) {
+        *reinterpret_cast<float4*>(q + i) = make_float4(x[0], x[1], x[2], x[3]);
+    } else {
+#pragma unroll
+        for (int k = 0; k < kOptVec; ++k)
+            if (i + k < nb) q[i + k] = x[k];
+    }
+}
+
+__global__ void __launch_bounds__(kOptThreads) opt_grad_stats_kernel(const OptArgs a) {
+    constexpr int NW = kOptThreads / kWave;
+    __shared__ float red[NW];
+    __shared__ int bad[NW];
+    const int blk = a.first_block + (int)blockIdx.x, tid = threadIdx.x;
+    int64_t off = 0;
+    int nb = 0;
+    const int li = opt_locate(a, blk, off, nb);
+    float acc = 0.0f;
+    int nonfinite = 0;
+    if (li >= 0) {
+        const float inv_scale = a.scaled ? 1.0f / reinterpret_cast<const float*>(a.state)[kOsScale] : 1.0f;
+        const float* __restrict__ g = a.g[li] + off;
+        const bool vec = opt_aligned16(g);
+        float x[kOptIters][kOptVec];
+#pragma unroll
+        for (int it = 0; it < kOptIters; ++it) opt_load4(g, (it * kOptThreads + tid) * kOptVec, nb, vec, x[it]);
+#pragma unroll
+        for (int it = 0; it < kOptIters; ++it)
+#pragma unroll
+            for (int k = 0; k < kOptVec; ++k) {
+                nonfinite |= (__float_as_uint(x[it][k]) & 0x7f800000u) == 0x7f800000u ? 1 : 0;     // inf or nan
+                const float y = x[it][k] * inv_scale;
+                acc = fmaf(y, y, acc);
+            }
+    }
+    acc = wave_sum(acc);
+    nonfinite = __any(nonfinite) ? 1 : 0;
+    const int lane = tid & (kWave - 1), wave = tid / kWave;
+    if (lane == 0) {
+        red[wave] = acc;
+        bad[wave] = nonfinite;
+    }
+    __syncthreads();
+    if (tid == 0) {
+        float s = red[0];
+        int b = bad[0];
+#pragma unroll
+        for (int w = 1; w < NW; ++w) {
+            s += red[w];
+            b |= bad[w];
+        }
+        a.workspace[2 * (int64_t)blk] = s;                                   // slot blk: written, never added to
+        reinterpret_cast<int32_t*>(a.workspace)[2 * (int64_t)blk + 1] = b;
+    }
+}
+
+__device__ __forceinline__ double opt_ipow(double b, int t) {              // b^t by squaring: no libm, the same bits everywhere
+    double r = 1.0;
+    while (t > 0) {
+        if (t & 1) r *= b;
+        b *= b;
+        t >>= 1;
+    }
+    return r;
+}
+
+__global__ void __launch_bounds__(kOptThreads) opt_finalise_kernel(const OptFinArgs a) {
+    __shared__ double sred[kOptThreads];
+    __shared__ int bred[kOptThreads];
+    const int tid = threadIdx.x;
+    double s = 0.0;
+    int b = 0;
+#pragma unroll 8
+    for (int i = tid; i < a.total_blocks; i += kOptThreads) {                // thread t: slots t, t + 256, ... in that order
+        const float2 slot = reinterpret_cast<const float2*>(a.workspace)[i];  // (sum, flag): the workspace is 8-byte aligned
+        s += (double)slot.x;
+        b |= __float_as_int(slot.y);
+    }
+    sred[tid] = s;
+    bred[tid] = b;
+    __syncthreads();
+    for (int w = kOptThreads / 2; w > 0; w >>= 1) {                          // a fixed tree
+        if (tid < w) {
+            sred[tid] += sred[tid + w];
+            bred[tid] |= bred[tid + w];
+        }
+        __syncthreads();
+    }
+    if (tid != 0) return;
+    float* sf = reinterpret_cast<float*>(a.state);
+    int32_t* si = reinterpret_cast<int32_t*>(a.state);
+    const float scale = sf[kOsScale];
+    const double inv_scale = a.scaled ? 1.0 / (double)scale : 1.0;
+    bool found = false;
+    double clip = 1.0;
+    if (a.total_blocks > 0) {                                                // else: no pass over the gradients was made
+        const double sum = sred[0], norm = sqrt(sum);
+        found = bred[0] != 0 || !isfinite(sum);
+        if (a.has_max_norm && !found) clip = fmin(1.0, a.max_norm / (norm + 1e-6));
+        sf[kOsNorm] = (float)norm;
+    }
+    si[kOsFoundInf] = found ? 1 : 0;
+    sf[kOsClip] = (float)clip;
+    sf[kOsFactor] = found ? 0.0f : (float)(inv_scale * clip);
+    if (!found) {
+        const int t = si[kOsStep] + 1;
+        si[kOsStep] = t;
+        sf[kOsBc1] = (float)(1.0 - opt_ipow(a.beta1, t));
+        sf[kOsBc2s] = (float)sqrt(1.0 - opt_ipow(a.beta2, t));
+    } else {
+        si[kOsSkipped] += 1;
+    }
+    if (a.scaled) {                                                          // GradScaler's policy
+        if (found) {
+            sf[kOsScale] = scale * 0.5f;
+            si[kOsGrowth] = 0;
+        } else {
+            const int good = si[kOsGrowth] + 1;
+            const bool grow = good >= kOptGrowthInterval;
+            if (grow) sf[kOsScale] = scale * 2.0f;
+            si[kOsGrowth] = grow ? 0 : good;
+        }
+    }
+}
+
+__global__ void __launch_bounds__(kOptThreads) opt_adamw_kernel(const OptArgs a) {
+    if (reinterpret_cast<const int32_t*>(a.state)[kOsFoundInf] != 0) return;      // a skipped step writes nothing
+    const int blk = a.first_block + (int)blockIdx.x, tid = threadIdx.x;
+    int64_t off = 0;
+    int nb = 0;
+    const int li = opt_locate(a, blk, off, nb);
+    if (li < 0) return;
+    const float* sf = reinterpret_cast<const float*>(a.state);
+    const float factor = sf[kOsFactor], bc2s = sf[kOsBc2s];
+    const float step_size = a.lr / sf[kOsBc1];
+    const int ti = a.first_tensor + li;
+    const float* __restrict__ g = a.g[li] + off;
+    float* __restrict__ p = a.p[ti] + off;
+    float* __restrict__ m = a.m[ti] + off;
+    float* __restrict__ v = a.v[ti] + off;
+    const bool vec = opt_aligned16(g) && opt_aligned16(p) && opt_aligned16(m) && opt_aligned16(v);
+#pragma unroll
+    for (int it = 0; it < kOptIters; ++it) {
+        const int i = (it * kOptThreads + tid) * kOptVec;
+        if (i >= nb) break;
+        float gx[kOptVec], px[kOptVec], mx[kOptVec], vx[kOptVec];
+        opt_load4(g, i, nb, vec, gx);
+        opt_load4(p, i, nb, vec, px);
+        opt_load4(m, i, nb, vec, mx);
+        opt_load4(v, i, nb, vec, vx);
+#pragma unroll
+        for (int k = 0; k < kOptVec; ++k) {
+            const float gs = gx[k] * factor;
+            const float mn = fmaf(a.omb1, gs - mx[k], mx[k]);                     // m + (1 - b1) (g' - m)
+            const float vn = fmaf(a.b2, vx[k], (a.omb2 * gs) * gs);               // b2 v + (1 - b2) g'^2
+            const float denom = sqrtf(vn) / bc2s + a.eps;
+            px[k] = fmaf(-step_size, mn / denom, px[k] * a.decay);               // p (1 - lr wd) - (lr / bc1) m' / denom
+            mx[k] = mn;
+            vx[k] = vn;
+        }
+        opt_store4(p, i, nb, vec, px);
+        opt_store4(m, i, nb, vec, mx);
+        opt_store4(v, i, nb, vec, vx);
+    }
+}
+
+static OptArgs opt_args(const vivim_opt_step_params& q) {
+    OptArgs a;
+    a.first_tensor = q.first_tensor;
+    a.count = q.count;
+    a.first_block = q.first_block;
+    a.scaled = q.scaled;
+    a.p = static_cast<float* const*>(q.params);
+    a.m = static_cast<float* const*>(q.exp_avg);
+    a.v = static_cast<float* const*>(q.exp_avg_sq);
+    a.block_map = static_cast<const int32_t*>(q.block_map);
+    a.state = static_cast<uint32_t*>(q.state);
+    a.workspace = static_cast<float*>(q.workspace);
+    a.lr = (float)q.lr;                                     // each constant is formed in double and rounded once
+    a.omb1 = (float)(1.0 - q.beta1);
+    a.b2 = (float)q.beta2;
+    a.omb2 = (float)(1.0 - q.beta2);
+    a.eps = (float)q.eps;
+    a.decay = (float)(1.0 - q.lr * q.weight_decay);
+    for (int i = 0; i < VIVIM_OPT_MAX_TENSORS; ++i) {
+        a.g[i] = i < q.count ? static_cast<const float*>(q.grads[i]) : nullptr;
+        a.n[i] = i < q.count ? q.numel[i] : 0;
+    }
+    return a;
+}
+
+void opt_grad_stats_launch(const vivim_opt_step_params& q, hipStream_t stream) {
+    hipLaunchKernelGGL(opt_grad_stats_kernel, dim3((unsigned)q.n_blocks), dim3(kOptThreads), 0, stream, opt_args(q));
+}
+
+void opt_adamw_launch(const vivim_opt_step_params& q, hipStream_t stream) {
+    hipLaunchKernelGGL(opt_adamw_kernel, dim3((unsigned)q.n_blocks), dim3(kOptThreads), 0, stream, opt_args(q));
+}
+
+void opt_finalise_launch(const vivim_opt_step_params& q, hipStream_t stream) {
+    OptFinArgs a;
+    a.state = static_cast<uint32_t*>(q.state);
+    a.workspace = static_cast<const float*>(q.workspace);
+    a.total_blocks = q.total_blocks;
+    a.scaled = q.scaled;
+    a.has_max_norm = q.has_max_norm;
+    a._pad = 0;
+    a.max_norm = q.max_norm;
+    a.beta1 = q.beta1;
+    a.beta2 = q.beta2;
+    hipLaunchKernelGGL(opt_finalise_kernel, dim3(1), dim3(kOptThreads), 0, stream, a);
+}
+
+}  // namespace vivim

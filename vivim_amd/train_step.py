@@ -3,8 +3,12 @@ configure_optimizers :503-517, Trainer(precision=16, devices=1) :800-811): Vivim
 recall_focused_loss, backward, AdamW.  Used by bench.py and the tests; the losses are restated from the
 reference source text (it cannot be imported: it needs pytorch_lightning / wandb / medpy and parses argv at
 import time)."""
+import os
+
 import torch
 import torch.nn.functional as F
+
+from .optimizer import FusedStepAdamW
 
 
 def tversky_loss(probs, onehot, alpha=0.3, beta=0.7, smooth=1e-6):
@@ -127,12 +131,17 @@ class LeanFusedAdamW:
                                 maximize=False)
 
 
-def make_optimizer(model, lr=1e-4, weight_decay=1e-2, capturable=False, fused=None, lean=None):
+def make_optimizer(model, lr=1e-4, weight_decay=1e-2, capturable=False, fused=None, lean=None, fused_step=False):
     """AdamW(lr 1e-4, betas (.9, .999), wd 1e-2) as the reference's configure_optimizers (train.py:503-517).  On a GPU
     the update runs as PyTorch's fused multi-tensor kernel (same arithmetic, one launch per dtype/device group
     instead of a Python-side foreach chain: the optimizer was ~10 ms of the host-bound 80 ms step), by default through
-    `LeanFusedAdamW`; `lean=False` gives `torch.optim.AdamW(fused=True)`."""
+    `LeanFusedAdamW`; `lean=False` gives `torch.optim.AdamW(fused=True)`.  `fused_step=True` (opt-in) gives
+    `optimizer.FusedStepAdamW`, with which `train_step` runs unscaling, the overflow check, clipping, the update and the
+    loss-scale policy on the device (csrc/optimizer.hip) without a host synchronisation; `VIVIM_NO_FUSED_OPTIMIZER=1` turns
+    the switch off again."""
     params = [p for p in model.parameters() if p.requires_grad]
+    if fused_step and not os.environ.get("VIVIM_NO_FUSED_OPTIMIZER"):
+        return FusedStepAdamW(params, lr=lr, betas=(0.9, 0.999), weight_decay=weight_decay)
     on_gpu = bool(params) and all(p.is_cuda and p.dtype == torch.float32 for p in params)
     if fused is None:
         fused = on_gpu and not capturable
@@ -162,7 +171,9 @@ def train_step(model, optimizer, clip, onehot, num_classes, amp_dtype=torch.bflo
     reference trains with Trainer(precision=16), multiclass_training_folds.py:800-811; bf16 / fp32 need none);
     `clip_grad_norm` (the reference's gradient_clip_val) clips the global gradient norm before the update.
     `fused_loss=True` takes the loss and its gradient from the fused kernels (seg_loss.recall_focused_loss_fused: three
-    launches, cancellation-free) instead of the eager chain of recall_focused_loss; opt-in, the default step is unchanged."""
+    launches, cancellation-free) instead of the eager chain of recall_focused_loss; opt-in, the default step is unchanged.
+    With a `FusedStepAdamW` the loss is multiplied by the optimizer's loss scale ON THE DEVICE (fp16) and everything after the
+    backward is `optimizer.step(max_norm=clip_grad_norm, scaled=...)`: no `_SCALERS` entry, no host synchronisation."""
     if not model.training:                 # Module.train() walks all ~4000 submodules: 3 ms of host time when repeated per step
         model.train()
     with torch.autocast("cuda", dtype=amp_dtype, enabled=amp_dtype != torch.float32):
@@ -175,6 +186,11 @@ def train_step(model, optimizer, clip, onehot, num_classes, amp_dtype=torch.bflo
     else:
         loss = recall_focused_loss(logits, target, num_classes)
     optimizer.zero_grad(set_to_none=True)
+    if isinstance(optimizer, FusedStepAdamW):
+        scaled = amp_dtype == torch.float16
+        (loss * optimizer.loss_scale if scaled else loss).backward()
+        optimizer.step(max_norm=clip_grad_norm, scaled=scaled)
+        return loss.detach()
     if amp_dtype == torch.float16:
         sc = _SCALERS.setdefault(id(optimizer), {"scale": 65536.0, "good": 0})      # dynamic loss scale, GradScaler's policy
         (loss * sc["scale"]).backward()
