@@ -584,6 +584,45 @@ typedef struct {
     int64_t workspace_bytes;
 } vivim_opt_step_params;
 
+/* ---- Master weights: the fused step for fp16 / bf16 parameters (vivim_amd/optimizer.py: FusedStepAdamW(master_weights=True)) ---
+ * The model's parameter and its gradient are 16-bit tensors of type `dtype` (1 = VIVIM_F16, 2 = VIVIM_BF16); the value the
+ * optimizer owns is an fp32 master.  vivim_opt_mw_params is vivim_opt_step_params field for field, then `masters` -- a DEVICE
+ * array of device pointers like `params`, one entry per tensor of the whole list (entries of fp32 tensors are not read) -- and
+ * `dtype`.  A call is homogeneous: every tensor first_tensor .. first_tensor + count - 1 has that type; the caller orders its
+ * tables by type (fp32, fp16, bf16), cuts them so that no call straddles two, and sends the fp32 cuts to the entry points above.
+ * The record, the block map, the workspace (and its query) and vivim_opt_finalise are shared by all cuts of a step.
+ *
+ *   vivim_opt_grad_stats_mw: as vivim_opt_grad_stats on g widened to fp32 (exact); the non-finite test reads the widened value.
+ *   vivim_opt_adamw_mw: nothing is written when record[4] is set; otherwise g' = float(g) * factor, and m', v' and
+ *     master' = master (1 - lr * weight_decay) - (lr / bc1) * m' / (sqrt(v') / bc2s + eps) by the arithmetic above, unchanged;
+ *     master', m', v' are stored and params[i] receives p16 = master' rounded to nearest even (fp16: overflow gives +-inf,
+ *     subnormals are rounded, not flushed) -- the 16-bit value autocast's cast of an fp32 parameter would have produced.
+ * A thread works on the same four consecutive elements as in the fp32 kernels (8-byte accesses of the 16-bit tensors where
+ * g and p16 are 8-byte and master, m, v 16-byte aligned; element accesses otherwise), and the sums run in the same order: the
+ * results equal those of the fp32 entry points given the widened gradients, bit for bit.  Per element 2 + 12 bytes are read and
+ * 12 + 2 written: the 28 bytes of the fp32 step.  The caller sets struct_bytes = sizeof(vivim_opt_mw_params). */
+typedef struct {
+    int32_t struct_bytes;                            /* sizeof(vivim_opt_mw_params) as the caller compiled it */
+    int32_t count;
+    int32_t first_tensor;
+    int32_t first_block, n_blocks;
+    int32_t total_blocks;
+    int32_t scaled;
+    int32_t has_max_norm;
+    double max_norm;
+    double lr, beta1, beta2, eps, weight_decay;
+    const void *const *grads;                        /* HOST array [count] of device pointers to `dtype` gradients; NULL = none */
+    const int64_t *numel;                            /* HOST array [count], each > 0 */
+    const void *params, *exp_avg, *exp_avg_sq;       /* DEVICE arrays of device pointers: `dtype` parameters, fp32 moments */
+    const void *block_map;
+    void *state;
+    void *workspace;
+    int64_t workspace_bytes;
+    const void *masters;                             /* DEVICE array of device pointers: the fp32 masters */
+    int32_t dtype;                                   /* 1 = VIVIM_F16, 2 = VIVIM_BF16 */
+    int32_t _pad0;
+} vivim_opt_mw_params;
+
 int vivim_abi_version(void);
 const char *vivim_last_error(void);
 
@@ -657,6 +696,8 @@ int vivim_opt_grad_stats(const vivim_opt_step_params *p, void *stream);   /* rea
 int vivim_opt_finalise(const vivim_opt_step_params *p, void *stream);     /* reads the slots, updates the record */
 int vivim_opt_adamw(const vivim_opt_step_params *p, void *stream);        /* reads the record and g, updates p, m, v */
 size_t vivim_opt_step_workspace_bytes(const vivim_opt_step_params *p);    /* from total_blocks; 0 on bad sizes */
+int vivim_opt_grad_stats_mw(const vivim_opt_mw_params *p, void *stream);  /* 16-bit gradients; writes this call's slots */
+int vivim_opt_adamw_mw(const vivim_opt_mw_params *p, void *stream);       /* updates master, m, v; writes the 16-bit p */
 
 /* Deterministic backward (for torch.use_deterministic_algorithms).  Same parameters, checks and results as
  * vivim_selective_scan_bwd, and the same kernel family, but every gradient that the default call adds up across

@@ -1,12 +1,14 @@
 """Kernel launches of one tri-directional Mamba block (forward + backward, bf16 autocast, stage-0 shape of the bench) and of
 one whole train step, by kernel name -- the step is host-bound, so launches are what it pays for.
     python tools/launch_count.py [--dim 64] [--batch 3] [--frames 5] [--hw 4096] [--step] [--fused-loss] [--backbone-layernorm]
-                                  [--backbone-add-norm] [--fp16] [--clip-grad-norm X] [--fused-optimizer]
+                                  [--backbone-add-norm] [--fp16] [--clip-grad-norm X] [--fused-optimizer] [--master-weights]
 --fused-loss (with --step) counts the step with train_step(fused_loss=True) as well, and the loss alone (forward + backward on
 the step's logits shape) both ways.  --backbone-layernorm (with --step) builds the model with fast_backbone_layernorm=True,
 --backbone-add-norm with fused_backbone_add_norm=True.  --fp16 and --clip-grad-norm X (with --step) count the step under fp16
 autocast with the dynamic loss scale and with gradient clipping; --fused-optimizer counts that step with
-make_optimizer(fused_step=True) as well (the optimizer phase on the device: csrc/optimizer.hip)."""
+make_optimizer(fused_step=True) as well (the optimizer phase on the device: csrc/optimizer.hip), and --master-weights (with both)
+counts it once more, last, with the model's Linear / Conv2d parameters lowered to the autocast dtype and
+make_optimizer(fused_step=True, master_weights=True): autocast's per-parameter casts are gone."""
 import argparse
 import collections
 import os
@@ -53,6 +55,7 @@ def main():
     ap.add_argument("--fp16", action="store_true")
     ap.add_argument("--clip-grad-norm", type=float, default=None)
     ap.add_argument("--fused-optimizer", action="store_true")
+    ap.add_argument("--master-weights", action="store_true")
     a = ap.parse_args()
     dev = torch.device("cuda:0")
     from vivim_amd.mamba_simple import Mamba
@@ -98,6 +101,15 @@ def main():
                     logits.grad = None
                     fn(logits, target, 3).backward()
                 show(f"loss alone ({title}), forward + backward, {tuple(logits.shape)} bf16", *launches(loss_only), top=12)
+        if a.master_weights and a.fused_optimizer:                    # last: it changes the model
+            from vivim_amd.optimizer import lower_params
+            lowered = lower_params(model, amp)
+            mw_opt = ts.make_optimizer(model, fused_step=True, master_weights=True)
+
+            def step_mw():
+                ts.train_step(model, mw_opt, clip, onehot, 3, amp, clip_grad_norm=a.clip_grad_norm)
+            show(f"train step, {how}, {len(lowered)} parameters lowered, make_optimizer(fused_step=True, master_weights=True): "
+                 f"{mw_opt.launches_per_step} optimizer launches", *launches(step_mw), top=60)
 
 
 if __name__ == "__main__":

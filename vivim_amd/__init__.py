@@ -20,7 +20,7 @@ def __getattr__(name):
     if name in ("fused_decode_head", "fold_decode_head"):     # the eval-mode decode head (decode_head.py), likewise
         from . import decode_head
         return getattr(decode_head, name)
-    if name == "FusedStepAdamW":                       # the device-side clip + AdamW step (optimizer.py), likewise
+    if name in ("FusedStepAdamW", "lower_params", "raise_params"):   # the device-side clip + AdamW step (optimizer.py), likewise
         from . import optimizer
-        return optimizer.FusedStepAdamW
+        return getattr(optimizer, name)
     raise AttributeError(f"module {__name__!r} has no attribute {name!r}")

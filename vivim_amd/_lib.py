@@ -196,6 +196,12 @@ class OptStepParams(ctypes.Structure):
                 + [("workspace_bytes", i64)])
 
 
+class OptMwParams(ctypes.Structure):
+    """vivim_opt_mw_params: OptStepParams field for field, then the masters' table and the 16-bit type (F16 / BF16) of the call's
+    parameters and gradients.  Its sizeof is stated in struct_bytes."""
+    _fields_ = OptStepParams._fields_ + [("masters", vp), ("dtype", i32), ("_pad0", i32)]
+
+
 # The structs in vivim_sizeof order.
 STRUCTS = (SsmFwdParams, SsmBwdParams, ConvFwdParams, ConvBwdParams, DwConvParams, DwConvWgradParams, DirParams,
            ConvUpdateParams, StateUpdateParams, LayerNormParams, WgradNtParams, AddLayerNormParams, SegLossParams,
@@ -267,6 +273,8 @@ ENTRY_POINTS = {
     "vivim_opt_finalise": Entry(None, (ctypes.POINTER(OptStepParams),), True, _int),
     "vivim_opt_adamw": Entry(None, (ctypes.POINTER(OptStepParams),), True, _int),
     "vivim_opt_step_workspace_bytes": Entry(None, (ctypes.POINTER(OptStepParams),), False, _size),
+    "vivim_opt_grad_stats_mw": Entry(None, (ctypes.POINTER(OptMwParams),), True, _int),
+    "vivim_opt_adamw_mw": Entry(None, (ctypes.POINTER(OptMwParams),), True, _int),
 }
 EXPORTS = tuple(ENTRY_POINTS)
 
@@ -321,6 +329,8 @@ def algorithmic_bytes(name, P):
         if name.endswith("finalise"):
             return 8 * P.total_blocks + 4 * OPT_STATE_WORDS
         n = sum(P.numel[i] for i in range(P.count) if P.grads[i])
+        if name.endswith("_mw"):                                        # a 2-byte g | master, m, v read and written, g read, p16 written
+            return 2 * n + 8 * P.n_blocks if name.endswith("stats_mw") else 28 * n
         return 4 * n + 8 * P.n_blocks if name.endswith("stats") else 28 * n
     if name.startswith("vivim_add_layernorm"):
         n = P.batch * P.seqlen * P.channels

@@ -3,7 +3,9 @@
 // tensor layer (selective_scan.cpp:233-304, 352-438; causal_conv1d.cpp:135-163, 198-238).
 #include <hip/hip_runtime.h>
 #include <stdarg.h>
+#include <stddef.h>
 #include <stdio.h>
+#include <string.h>
 #include <type_traits>
 #include "../../include/vivim_hip.h"
 #include "det.cuh"
@@ -57,6 +59,8 @@ size_t token_add_norm_bwd_workspace_bytes(const vivim_token_add_norm_params&);
 void opt_grad_stats_launch(const vivim_opt_step_params&, hipStream_t);                        // optimizer.hip
 void opt_finalise_launch(const vivim_opt_step_params&, hipStream_t);
 void opt_adamw_launch(const vivim_opt_step_params&, hipStream_t);
+void opt_grad_stats_mw_launch(const vivim_opt_step_params&, int dtype, hipStream_t);
+void opt_adamw_mw_launch(const vivim_opt_step_params&, const void* masters, int dtype, hipStream_t);
 }  // namespace vivim
 
 static thread_local char g_err[512] = "";
@@ -820,14 +824,14 @@ static int check_opt_common(const vivim_opt_step_params* p, const char* fn) {
 }
 
 // the tensors and map rows of one multi-tensor call
-static int check_opt_tensors(const vivim_opt_step_params* p, const char* fn) {
+static int check_opt_tensors(const vivim_opt_step_params* p, const char* fn, size_t grad_align = 4) {
     if (p->count <= 0 || p->count > VIVIM_OPT_MAX_TENSORS)
         return fail(VIVIM_ERR_INVALID, "%s: count = %d, a call takes 1 to %d tensors", fn, p->count, VIVIM_OPT_MAX_TENSORS);
     VCHECK(p->grads != nullptr && p->numel != nullptr && p->block_map != nullptr);
     VCHECK(aligned(p->block_map, 4) && p->first_tensor >= 0);
     for (int i = 0; i < p->count; ++i) {
         if (p->numel[i] <= 0) return fail(VIVIM_ERR_INVALID, "%s: numel[%d] = %lld", fn, i, (long long)p->numel[i]);
-        VCHECK(aligned(p->grads[i], 4));
+        VCHECK(aligned(p->grads[i], grad_align));
     }
     if (p->first_block < 0 || p->n_blocks <= 0 || (int64_t)p->first_block + p->n_blocks > p->total_blocks)
         return fail(VIVIM_ERR_INVALID, "%s: map rows %d .. %d + %d of %d", fn, p->first_block, p->first_block, p->n_blocks, p->total_blocks);
@@ -876,6 +880,46 @@ int vivim_opt_adamw(const vivim_opt_step_params* p, void* stream) {
     if (!(p->lr >= 0.0 && p->eps >= 0.0 && p->weight_decay >= 0.0))
         return fail(VIVIM_ERR_INVALID, "%s: lr = %g, eps = %g, weight_decay = %g: none may be negative", fn, p->lr, p->eps, p->weight_decay);
     vivim::opt_adamw_launch(*p, as_stream(stream));
+    return after_launch(fn);
+}
+
+// ---- the same step for 16-bit parameters with fp32 masters: vivim_opt_mw_params is vivim_opt_step_params + masters + dtype
+static int check_opt_mw(const vivim_opt_mw_params* p, const char* fn, vivim_opt_step_params& q) {
+    VCHECK(p != nullptr);
+    if (p->struct_bytes != (int32_t)sizeof(vivim_opt_mw_params))
+        return fail(VIVIM_ERR_INVALID, "%s: struct_bytes = %d, this library's vivim_opt_mw_params has %zu", fn, p->struct_bytes,
+                    sizeof(vivim_opt_mw_params));
+    static_assert(offsetof(vivim_opt_mw_params, masters) == sizeof(vivim_opt_step_params), "the common fields come first");
+    memcpy(&q, p, sizeof(q));
+    q.struct_bytes = (int32_t)sizeof(q);
+    if (int rc = check_opt_common(&q, fn)) return rc;
+    if (p->dtype != VIVIM_F16 && p->dtype != VIVIM_BF16)
+        return fail(VIVIM_ERR_INVALID, "%s: dtype = %d, master weights are for 1 (fp16) and 2 (bf16)", fn, p->dtype);
+    return VIVIM_OK;
+}
+
+int vivim_opt_grad_stats_mw(const vivim_opt_mw_params* p, void* stream) {
+    const char* fn = "opt_grad_stats_mw";
+    vivim_opt_step_params q;
+    if (int rc = check_opt_mw(p, fn, q)) return rc;
+    if (int rc = check_opt_tensors(&q, fn, 2)) return rc;
+    if (int rc = check_opt_workspace(&q, fn)) return rc;
+    vivim::opt_grad_stats_mw_launch(q, p->dtype, as_stream(stream));
+    return after_launch(fn);
+}
+
+int vivim_opt_adamw_mw(const vivim_opt_mw_params* p, void* stream) {
+    const char* fn = "opt_adamw_mw";
+    vivim_opt_step_params q;
+    if (int rc = check_opt_mw(p, fn, q)) return rc;
+    VCHECK(q.params != nullptr && q.exp_avg != nullptr && q.exp_avg_sq != nullptr && p->masters != nullptr);
+    VCHECK(aligned(q.params, 8) && aligned(q.exp_avg, 8) && aligned(q.exp_avg_sq, 8) && aligned(p->masters, 8));
+    if (int rc = check_opt_tensors(&q, fn, 2)) return rc;
+    if (!(q.beta1 >= 0.0 && q.beta1 < 1.0 && q.beta2 >= 0.0 && q.beta2 < 1.0))
+        return fail(VIVIM_ERR_INVALID, "%s: betas = (%g, %g), each must be in [0, 1)", fn, q.beta1, q.beta2);
+    if (!(q.lr >= 0.0 && q.eps >= 0.0 && q.weight_decay >= 0.0))
+        return fail(VIVIM_ERR_INVALID, "%s: lr = %g, eps = %g, weight_decay = %g: none may be negative", fn, q.lr, q.eps, q.weight_decay);
+    vivim::opt_adamw_mw_launch(q, p->masters, p->dtype, as_stream(stream));
     return after_launch(fn);
 }
 

@@ -17,6 +17,13 @@
 //     rounding per stored value.  16-byte accesses where the four addresses of a chunk allow, element accesses otherwise
 //     (Mamba's per-direction Parameters are rows of a stacked buffer and need not be 16-byte aligned), and for a chunk's tail.
 // A tensor whose gradient pointer is NULL is left out of the step: its slots are written as (0, 0), its state is not touched.
+//
+// Master weights (vivim_opt_mw_params): the two multi-tensor kernels are templates over the gradient's element type.  With a
+// 16-bit type (fp16, bf16) the gradient is widened to fp32 exactly and opt_adamw_kernel updates an fp32 master with the fp32
+// arithmetic unchanged, then stores p16 = RNE(master') into the model's parameter.  A thread still owns four consecutive
+// elements per iteration (8-byte accesses of the 16-bit tensors), so the chain, wave and slot sums run in the fp32 kernels'
+// order and the results are those of the fp32 route fed the widened gradients, bit for bit.  A launch is homogeneous: the
+// caller orders its tables by type and no call straddles two.
 #include <math.h>
 #include "common.cuh"
 
@@ -34,14 +41,15 @@ enum { kOsScale = 0, kOsGrowth, kOsStep, kOsNorm, kOsFoundInf, kOsFactor, kOsBc1
 
 struct OptArgs {                       // the kernel arguments of the two multi-tensor kernels
     int32_t first_tensor, count, first_block, scaled;
-    float* const* p;                   // device tables, one entry per tensor of the whole list
+    void* const* p;                    // device tables, one entry per tensor of the whole list; p has the gradient's type
     float* const* m;
     float* const* v;
+    float* const* w;                   // the fp32 masters of 16-bit parameters (unused by the fp32 kernels)
     const int32_t* block_map;          // device: (tensor, chunk) per workgroup of the whole list
     uint32_t* state;
     float* workspace;
     float lr, omb1, b2, omb2, eps, decay;
-    const float* g[VIVIM_OPT_MAX_TENSORS];      // this launch's tensors: first_tensor .. first_tensor + count - 1
+    const void* g[VIVIM_OPT_MAX_TENSORS];       // this launch's tensors: first_tensor .. first_tensor + count - 1
     int64_t n[VIVIM_OPT_MAX_TENSORS];
 };
 static_assert(sizeof(OptArgs) <= 4096, "the by-value table must fit 4 KB of kernel arguments");
@@ -66,29 +74,68 @@ __device__ __forceinline__ int opt_locate(const OptArgs& a, int blk, int64_t& of
     return li;
 }
 
-__device__ __forceinline__ bool opt_aligned16(const void* q) { return (reinterpret_cast<uintptr_t>(q) & 15) == 0; }
+// whether q takes one access of four elements: 16 bytes of fp32, 8 bytes of a 16-bit type
+template <typename T> __device__ __forceinline__ bool opt_aligned(const T* q) {
+    return (reinterpret_cast<uintptr_t>(q) & (kOptVec * sizeof(T) - 1)) == 0;
+}
 
-// 4 consecutive floats from q[i..]: one 16-byte load when `vec` and all four exist, else the existing ones; the rest read as 0
-__device__ __forceinline__ void opt_load4(const float* __restrict__ q, int i, int nb, bool vec, float (&x)[kOptVec]) {
+// fp32 <-> the 16-bit types.  Widening is exact.  Narrowing is round-to-nearest-even with torch's results in every bit: fp16
+// through the hardware conversion (overflow gives inf, subnormals are rounded), bf16 in integer arithmetic (a NaN becomes 0x7fc0).
+__device__ __forceinline__ float opt_widen(float x) { return x; }
+__device__ __forceinline__ float opt_widen(f16_t x) { return static_cast<float>(x); }
+__device__ __forceinline__ float opt_widen(bf16_t x) { return __uint_as_float((uint32_t)__builtin_bit_cast(uint16_t, x) << 16); }
+template <typename T> __device__ __forceinline__ T opt_narrow(float x);
+template <> __device__ __forceinline__ f16_t opt_narrow<f16_t>(float x) { return static_cast<f16_t>(x); }
+template <> __device__ __forceinline__ bf16_t opt_narrow<bf16_t>(float x) {
+    const uint32_t u = __float_as_uint(x);
+    const uint16_t r = x != x ? (uint16_t)0x7fc0 : (uint16_t)((u + 0x7fffu + ((u >> 16) & 1u)) >> 16);
+    return __builtin_bit_cast(bf16_t, r);
+}
+
+// 4 consecutive elements from q[i..] as fp32: one access when `vec` and all four exist, else the existing ones; the rest read as 0
+template <typename T>
+__device__ __forceinline__ void opt_load4(const T* __restrict__ q, int i, int nb, bool vec, float (&x)[kOptVec]) {
     if (vec && i + kOptVec <= nb) {
-        const float4 t = *reinterpret_cast<const float4*>(q + i);
-        x[0] = t.x; x[1] = t.y; x[2] = t.z; x[3] = t.w;
+        if constexpr (sizeof(T) == 4) {
+            const float4 t = *reinterpret_cast<const float4*>(q + i);
+            x[0] = t.x; x[1] = t.y; x[2] = t.z; x[3] = t.w;
+        } else {
+            union { u32x2 raw; T e[kOptVec]; } u;
+            u.raw = *reinterpret_cast<const u32x2*>(q + i);
+#pragma unroll
+            for (int k = 0; k < kOptVec; ++k) x[k] = opt_widen(u.e[k]);
+        }
     } else {
 #pragma unroll
-        for (int k = 0; k < kOptVec; ++k) x[k] = i + k < nb ? q[i + k] : 0.0f;
+        for (int k = 0; k < kOptVec; ++k) x[k] = i + k < nb ? opt_widen(q[i + k]) : 0.0f;
     }
 }
 
-__device__ __forceinline__ void opt_store4(float* __restrict__ q, int i, int nb, bool vec, const float (&x)[kOptVec]) {
-    if (vec && i + kOptVec <= nb) {
-        *reinterpret_cast<float4*>(q + i) = make_float4(x[0], x[1], x[2], x[3]);
-    } else {
+template <typename T>
+__device__ __forceinline__ void opt_store4(T* __restrict__ q, int i, int nb, bool vec, const float (&x)[kOptVec]) {
+    if constexpr (sizeof(T) == 4) {
+        if (vec && i + kOptVec <= nb) {
+            *reinterpret_cast<float4*>(q + i) = make_float4(x[0], x[1], x[2], x[3]);
+        } else {
 #pragma unroll
-        for (int k = 0; k < kOptVec; ++k)
-            if (i + k < nb) q[i + k] = x[k];
+            for (int k = 0; k < kOptVec; ++k)
+                if (i + k < nb) q[i + k] = x[k];
+        }
+    } else {
+        union { u32x2 raw; T e[kOptVec]; } u;
+#pragma unroll
+        for (int k = 0; k < kOptVec; ++k) u.e[k] = opt_narrow<T>(x[k]);
+        if (vec && i + kOptVec <= nb) {
+            *reinterpret_cast<u32x2*>(q + i) = u.raw;
+        } else {
+#pragma unroll
+            for (int k = 0; k < kOptVec; ++k)
+                if (i + k < nb) q[i + k] = u.e[k];
+        }
     }
 }
 
+template <typename G>   // the gradient's element type: float, f16_t or bf16_t
 __global__ void __launch_bounds__(kOptThreads) opt_grad_stats_kernel(const OptArgs a) {
     constexpr int NW = kOptThreads / kWave;
     __shared__ float red[NW];
@@ -101,8 +148,8 @@ __global__ void __launch_bounds__(kOptThreads) opt_grad_stats_kernel(const OptAr
     int nonfinite = 0;
     if (li >= 0) {
         const float inv_scale = a.scaled ? 1.0f / reinterpret_cast<const float*>(a.state)[kOsScale] : 1.0f;
-        const float* __restrict__ g = a.g[li] + off;
-        const bool vec = opt_aligned16(g);
+        const G* __restrict__ g = static_cast<const G*>(a.g[li]) + off;
+        const bool vec = opt_aligned(g);
         float x[kOptIters][kOptVec];
 #pragma unroll
         for (int it = 0; it < kOptIters; ++it) opt_load4(g, (it * kOptThreads + tid) * kOptVec, nb, vec, x[it]);
@@ -205,7 +252,10 @@ __global__ void __launch_bounds__(kOptThreads) opt_finalise_kernel(const OptFinA
     }
 }
 
+// G = float: p is the fp32 parameter.  G = f16_t / bf16_t: the fp32 value lives in the master w, p receives its rounded copy.
+template <typename G>
 __global__ void __launch_bounds__(kOptThreads) opt_adamw_kernel(const OptArgs a) {
+    constexpr bool kMaster = sizeof(G) == 2;
     if (reinterpret_cast<const int32_t*>(a.state)[kOsFoundInf] != 0) return;      // a skipped step writes nothing
     const int blk = a.first_block + (int)blockIdx.x, tid = threadIdx.x;
     int64_t off = 0;
@@ -216,11 +266,12 @@ __global__ void __launch_bounds__(kOptThreads) opt_adamw_kernel(const OptArgs a)
     const float factor = sf[kOsFactor], bc2s = sf[kOsBc2s];
     const float step_size = a.lr / sf[kOsBc1];
     const int ti = a.first_tensor + li;
-    const float* __restrict__ g = a.g[li] + off;
-    float* __restrict__ p = a.p[ti] + off;
+    const G* __restrict__ g = static_cast<const G*>(a.g[li]) + off;
+    G* __restrict__ p16 = static_cast<G*>(a.p[ti]) + off;                         // only stored to, and only with a master
+    float* __restrict__ p = kMaster ? a.w[ti] + off : reinterpret_cast<float*>(p16);
     float* __restrict__ m = a.m[ti] + off;
     float* __restrict__ v = a.v[ti] + off;
-    const bool vec = opt_aligned16(g) && opt_aligned16(p) && opt_aligned16(m) && opt_aligned16(v);
+    const bool vec = opt_aligned(g) && opt_aligned(p16) && opt_aligned(p) && opt_aligned(m) && opt_aligned(v);
 #pragma unroll
     for (int it = 0; it < kOptIters; ++it) {
         const int i = (it * kOptThreads + tid) * kOptVec;
@@ -241,20 +292,22 @@ __global__ void __launch_bounds__(kOptThreads) opt_adamw_kernel(const OptArgs a)
             vx[k] = vn;
         }
         opt_store4(p, i, nb, vec, px);
+        if constexpr (kMaster) opt_store4(p16, i, nb, vec, px);
         opt_store4(m, i, nb, vec, mx);
         opt_store4(v, i, nb, vec, vx);
     }
 }
 
-static OptArgs opt_args(const vivim_opt_step_params& q) {
+static OptArgs opt_args(const vivim_opt_step_params& q, const void* masters = nullptr) {
     OptArgs a;
     a.first_tensor = q.first_tensor;
     a.count = q.count;
     a.first_block = q.first_block;
     a.scaled = q.scaled;
-    a.p = static_cast<float* const*>(q.params);
+    a.p = static_cast<void* const*>(q.params);
     a.m = static_cast<float* const*>(q.exp_avg);
     a.v = static_cast<float* const*>(q.exp_avg_sq);
+    a.w = static_cast<float* const*>(masters);
     a.block_map = static_cast<const int32_t*>(q.block_map);
     a.state = static_cast<uint32_t*>(q.state);
     a.workspace = static_cast<float*>(q.workspace);
@@ -265,18 +318,31 @@ static OptArgs opt_args(const vivim_opt_step_params& q) {
     a.eps = (float)q.eps;
     a.decay = (float)(1.0 - q.lr * q.weight_decay);
     for (int i = 0; i < VIVIM_OPT_MAX_TENSORS; ++i) {
-        a.g[i] = i < q.count ? static_cast<const float*>(q.grads[i]) : nullptr;
+        a.g[i] = i < q.count ? q.grads[i] : nullptr;
         a.n[i] = i < q.count ? q.numel[i] : 0;
     }
     return a;
 }
 
 void opt_grad_stats_launch(const vivim_opt_step_params& q, hipStream_t stream) {
-    hipLaunchKernelGGL(opt_grad_stats_kernel, dim3((unsigned)q.n_blocks), dim3(kOptThreads), 0, stream, opt_args(q));
+    hipLaunchKernelGGL(opt_grad_stats_kernel<float>, dim3((unsigned)q.n_blocks), dim3(kOptThreads), 0, stream, opt_args(q));
 }
 
 void opt_adamw_launch(const vivim_opt_step_params& q, hipStream_t stream) {
-    hipLaunchKernelGGL(opt_adamw_kernel, dim3((unsigned)q.n_blocks), dim3(kOptThreads), 0, stream, opt_args(q));
+    hipLaunchKernelGGL(opt_adamw_kernel<float>, dim3((unsigned)q.n_blocks), dim3(kOptThreads), 0, stream, opt_args(q));
+}
+
+// dtype: VIVIM_F16 or VIVIM_BF16 (checked by the caller)
+void opt_grad_stats_mw_launch(const vivim_opt_step_params& q, int dtype, hipStream_t stream) {
+    const dim3 grid((unsigned)q.n_blocks), block(kOptThreads);
+    if (dtype == VIVIM_F16) hipLaunchKernelGGL(opt_grad_stats_kernel<f16_t>, grid, block, 0, stream, opt_args(q));
+    else hipLaunchKernelGGL(opt_grad_stats_kernel<bf16_t>, grid, block, 0, stream, opt_args(q));
+}
+
+void opt_adamw_mw_launch(const vivim_opt_step_params& q, const void* masters, int dtype, hipStream_t stream) {
+    const dim3 grid((unsigned)q.n_blocks), block(kOptThreads);
+    if (dtype == VIVIM_F16) hipLaunchKernelGGL(opt_adamw_kernel<f16_t>, grid, block, 0, stream, opt_args(q, masters));
+    else hipLaunchKernelGGL(opt_adamw_kernel<bf16_t>, grid, block, 0, stream, opt_args(q, masters));
 }
 
 void opt_finalise_launch(const vivim_opt_step_params& q, hipStream_t stream) {

@@ -57,6 +57,9 @@ def wrap(model, device=None, bucket_cap_mb=25):
     backward scans still run); identity when the world is 1."""
     if not (dist.is_available() and dist.is_initialized()) or (dist.get_world_size() == 1 and not _REHEARSE):
         return model
+    if getattr(model, "_vivim_param_dtype", None) is not None:
+        raise ValueError("dp.wrap: this model's parameters are stored in %s (lower_params); summing 16-bit gradients across ranks "
+                         "is not supported -- raise_params(model) first" % model._vivim_param_dtype)
     ids = [device.index] if device is not None and device.type == "cuda" else None
     # a channels-last parameter (the decode head's 1x1 `out` conv) gets a channels-last gradient, which cannot be a view of
     # its contiguous bucket ("Grad strides do not match bucket view strides": an extra copy per step): store it densely

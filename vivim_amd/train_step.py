@@ -8,7 +8,7 @@ import os
 import torch
 import torch.nn.functional as F
 
-from .optimizer import FusedStepAdamW
+from .optimizer import FusedStepAdamW, check_autocast_dtype, lower_params
 
 
 def tversky_loss(probs, onehot, alpha=0.3, beta=0.7, smooth=1e-6):
@@ -53,7 +53,8 @@ def recall_focused_loss(logits, targets, num_classes, gamma=2.0, onehot=None, al
 
 
 def build_model(num_classes=3, device="cuda", mamba_kwargs=None, drop_path_rate=0.2, fast_backbone_dwconv=True,
-                fused_upsample=False, fused_decode_head=False, fast_backbone_layernorm=False, fused_backbone_add_norm=False):
+                fused_upsample=False, fused_decode_head=False, fast_backbone_layernorm=False, fused_backbone_add_norm=False,
+                low_precision_params=None):
     """Vivim with a randomly initialised SegFormer-b3 backbone (no hub access on the GPU box).  The two
     parameter groups that never receive a gradient in Vivim's forward -- the SegFormer 150-class classifier
     and the per-stage encoder layer norms (vivim.py:211-212, 325) -- are frozen so DDP needs no
@@ -61,7 +62,9 @@ def build_model(num_classes=3, device="cuda", mamba_kwargs=None, drop_path_rate=
     `fused_decode_head`: the eval-mode, no-grad decode head through csrc/decode_head.hip (decode_head.py), and
     `fast_backbone_layernorm`: the SegFormer patch embeddings' and blocks' LayerNorms through csrc/layernorm.hip and
     csrc/token_layernorm.hip, and `fused_backbone_add_norm`: the SegFormer blocks' residual adds fused with the LayerNorm that
-    reads the sum (vivim._run_stage)."""
+    reads the sum (vivim._run_stage).  `low_precision_params` (torch.float16 / torch.bfloat16, opt-in): the nn.Linear / nn.Conv2d
+    parameters outside the Mamba layers are stored in that dtype once the model is on the device (optimizer.lower_params);
+    such a model trains under autocast to that dtype with `make_optimizer(model, fused_step=True, master_weights=True)`."""
     from .vivim import Vivim, segformer_b3_random
     model = Vivim(in_chans=3, out_chans=num_classes, backbone=segformer_b3_random(),
                   drop_path_rate=drop_path_rate, mamba_kwargs=mamba_kwargs,
@@ -70,7 +73,10 @@ def build_model(num_classes=3, device="cuda", mamba_kwargs=None, drop_path_rate=
                   fused_backbone_add_norm=fused_backbone_add_norm)
     from .dp import freeze_unused
     freeze_unused(model)
-    return model.to(device)
+    model = model.to(device)
+    if low_precision_params is not None:
+        lower_params(model, low_precision_params)
+    return model
 
 
 class LeanFusedAdamW:
@@ -131,17 +137,24 @@ class LeanFusedAdamW:
                                 maximize=False)
 
 
-def make_optimizer(model, lr=1e-4, weight_decay=1e-2, capturable=False, fused=None, lean=None, fused_step=False):
+def make_optimizer(model, lr=1e-4, weight_decay=1e-2, capturable=False, fused=None, lean=None, fused_step=False,
+                   master_weights=False):
     """AdamW(lr 1e-4, betas (.9, .999), wd 1e-2) as the reference's configure_optimizers (train.py:503-517).  On a GPU
     the update runs as PyTorch's fused multi-tensor kernel (same arithmetic, one launch per dtype/device group
     instead of a Python-side foreach chain: the optimizer was ~10 ms of the host-bound 80 ms step), by default through
     `LeanFusedAdamW`; `lean=False` gives `torch.optim.AdamW(fused=True)`.  `fused_step=True` (opt-in) gives
     `optimizer.FusedStepAdamW`, with which `train_step` runs unscaling, the overflow check, clipping, the update and the
     loss-scale policy on the device (csrc/optimizer.hip) without a host synchronisation; `VIVIM_NO_FUSED_OPTIMIZER=1` turns
-    the switch off again."""
+    the switch off again.  `master_weights=True` on top of it is the mode for a model whose parameters `lower_params` stored
+    in 16 bits (fp32 masters in the optimizer); no other optimizer takes such a model, and there is no quiet fall-back."""
     params = [p for p in model.parameters() if p.requires_grad]
-    if fused_step and not os.environ.get("VIVIM_NO_FUSED_OPTIMIZER"):
-        return FusedStepAdamW(params, lr=lr, betas=(0.9, 0.999), weight_decay=weight_decay)
+    fused_step = fused_step and not os.environ.get("VIVIM_NO_FUSED_OPTIMIZER")
+    if getattr(model, "_vivim_param_dtype", None) is not None and not (fused_step and master_weights):
+        raise ValueError("make_optimizer: this model's parameters are stored in %s (lower_params); it needs fused_step=True and "
+                         "master_weights=True (and VIVIM_NO_FUSED_OPTIMIZER unset) -- or raise_params(model) to train it in fp32"
+                         % model._vivim_param_dtype)
+    if fused_step:
+        return FusedStepAdamW(params, lr=lr, betas=(0.9, 0.999), weight_decay=weight_decay, master_weights=master_weights)
     on_gpu = bool(params) and all(p.is_cuda and p.dtype == torch.float32 for p in params)
     if fused is None:
         fused = on_gpu and not capturable
@@ -174,6 +187,7 @@ def train_step(model, optimizer, clip, onehot, num_classes, amp_dtype=torch.bflo
     launches, cancellation-free) instead of the eager chain of recall_focused_loss; opt-in, the default step is unchanged.
     With a `FusedStepAdamW` the loss is multiplied by the optimizer's loss scale ON THE DEVICE (fp16) and everything after the
     backward is `optimizer.step(max_norm=clip_grad_norm, scaled=...)`: no `_SCALERS` entry, no host synchronisation."""
+    check_autocast_dtype(model, amp_dtype)
     if not model.training:                 # Module.train() walks all ~4000 submodules: 3 ms of host time when repeated per step
         model.train()
     with torch.autocast("cuda", dtype=amp_dtype, enabled=amp_dtype != torch.float32):
@@ -218,6 +232,7 @@ def eval_step(model, clip, onehot, num_classes, tracker=None, amp_dtype=torch.bf
     """The validation counterpart of train_step: forward under no_grad + autocast, the loss (eager, or the fused kernels with
     `fused_loss=True`), and, when a `tracker` (seg_metrics.SegMetricsTracker) is given, its update with the logits and the label
     map -- two launches on the device, no host synchronisation.  Returns the detached loss."""
+    check_autocast_dtype(model, amp_dtype)
     if model.training:                     # Module.eval() walks all ~4000 submodules, like train() in train_step
         model.eval()
     with torch.no_grad():
