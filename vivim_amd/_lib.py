@@ -1,11 +1,15 @@
 """ctypes binding of libvivim_hip.so (C ABI: include/vivim_hip.h).
 
+The header is the one description of the ABI: it is parsed once, at import, into the params structs, the entry-point table
+and the constants below.  The parser refuses whatever it does not understand instead of guessing.
+
 The library is the product: if it is missing or fails to load this module raises -- there is no
 PyTorch/CPU fallback anywhere in vivim_amd.
 """
 import collections
 import ctypes
 import os
+import re
 import subprocess
 
 import torch
@@ -13,270 +17,142 @@ import torch
 _HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(_HERE, "csrc")
 SO_PATH = os.environ.get("VIVIM_LIB") or os.path.join(CSRC, "libvivim_hip.so")   # VIVIM_LIB: A/B builds
+HEADER = os.path.join(os.path.dirname(_HERE), "include", "vivim_hip.h")
 
 i32, i64, vp = ctypes.c_int32, ctypes.c_int64, ctypes.c_void_p
 
-F32, F16, BF16 = 0, 1, 2
-
-
-class SsmFwdParams(ctypes.Structure):
-    _fields_ = (
-        [(n, i32) for n in ("batch", "dim", "seqlen", "dstate", "n_groups", "itype", "is_variable_B",
-                            "is_variable_C", "delta_softplus", "_pad0")]
-        + [(n, i64) for n in ("u_batch_stride", "u_d_stride", "delta_batch_stride", "delta_d_stride",
-                              "z_batch_stride", "z_d_stride", "out_batch_stride", "out_d_stride",
-                              "out_z_batch_stride", "out_z_d_stride", "A_d_stride", "A_dstate_stride",
-                              "B_batch_stride", "B_group_stride", "B_dstate_stride",
-                              "C_batch_stride", "C_group_stride", "C_dstate_stride")]
-        + [(n, vp) for n in ("u", "delta", "A", "B", "C", "D", "delta_bias", "z", "out", "out_z", "x", "workspace")]
-        + [("workspace_bytes", i64)]
-    )
-
-
-class SsmBwdParams(ctypes.Structure):
-    _fields_ = (
-        [("f", SsmFwdParams)]
-        + [(n, i64) for n in ("dout_batch_stride", "dout_d_stride", "du_batch_stride", "du_d_stride",
-                              "ddelta_batch_stride", "ddelta_d_stride", "dz_batch_stride", "dz_d_stride",
-                              "dA_d_stride", "dA_dstate_stride",
-                              "dB_batch_stride", "dB_group_stride", "dB_dstate_stride",
-                              "dC_batch_stride", "dC_group_stride", "dC_dstate_stride")]
-        + [(n, vp) for n in ("dout", "du", "ddelta", "dz", "dA", "dB", "dC", "dD", "ddelta_bias", "workspace")]
-        + [("workspace_bytes", i64)]
-    )
-
-
-class ConvFwdParams(ctypes.Structure):
-    _fields_ = (
-        [(n, i32) for n in ("batch", "dim", "seqlen", "width", "itype", "wtype", "silu_activation", "_pad0")]
-        + [(n, i64) for n in ("x_batch_stride", "x_c_stride", "x_l_stride",
-                              "out_batch_stride", "out_c_stride", "out_l_stride",
-                              "weight_c_stride", "weight_width_stride")]
-        + [(n, vp) for n in ("x", "weight", "bias", "out")]
-    )
-
-
-class ConvBwdParams(ctypes.Structure):
-    _fields_ = (
-        [("f", ConvFwdParams)]
-        + [(n, i64) for n in ("dout_batch_stride", "dout_c_stride", "dout_l_stride",
-                              "dx_batch_stride", "dx_c_stride", "dx_l_stride",
-                              "dweight_c_stride", "dweight_width_stride")]
-        + [(n, vp) for n in ("dout", "dx", "dweight", "dbias")]
-    )
-
-
-class DwConvParams(ctypes.Structure):
-    _fields_ = (
-        [(n, i32) for n in ("batch", "depth", "height", "width", "channels", "kd", "itype", "flip")]
-        + [(n, i64) for n in ("x_batch_stride", "x_token_stride", "y_batch_stride", "y_token_stride")]
-        + [(n, vp) for n in ("x", "wt", "bias", "y")]
-        + [("act", i32), ("_pad1", i32), ("aux", vp), ("aux_batch_stride", i64), ("aux_token_stride", i64)]
-    )
-
-
-class DwConvWgradParams(ctypes.Structure):
-    _fields_ = (
-        [(n, i32) for n in ("batch", "depth", "height", "width", "channels", "kd", "itype", "_pad0")]
-        + [(n, i64) for n in ("x_batch_stride", "x_token_stride", "dy_batch_stride", "dy_token_stride")]
-        + [(n, vp) for n in ("x", "dy", "dwt", "dbias")]
-    )
-
-
-class DirParams(ctypes.Structure):
-    _fields_ = ([(n, i32) for n in ("batch", "channels", "seqlen", "nframes", "csplit", "itype")]
-                + [("scale", ctypes.c_float), ("_pad0", i32)]
-                + [(n, i64) for n in ("flat_batch_stride", "flat_c_stride", "stk_batch_stride", "stk_half_stride",
-                                      "stk_dir_stride", "stk_c_stride")]
-                + [("src", vp), ("dst", vp)])
-
-
-class ConvUpdateParams(ctypes.Structure):
-    _fields_ = ([(n, i32) for n in ("batch", "dim", "width", "itype", "wtype", "silu_activation")]
-                + [(n, i64) for n in ("x_batch_stride", "x_c_stride", "state_batch_stride", "state_c_stride",
-                                      "state_w_stride", "weight_c_stride", "weight_width_stride",
-                                      "out_batch_stride", "out_c_stride")]
-                + [(n, vp) for n in ("x", "conv_state", "weight", "bias", "out")])
-
-
-class StateUpdateParams(ctypes.Structure):
-    _fields_ = ([(n, i32) for n in ("batch", "dim", "dstate", "itype", "stype", "dt_softplus")]
-                + [(n, i64) for n in ("state_batch_stride", "state_d_stride", "state_n_stride", "x_batch_stride",
-                                      "x_d_stride", "dt_batch_stride", "dt_d_stride", "A_d_stride", "A_n_stride",
-                                      "B_batch_stride", "B_n_stride", "C_batch_stride", "C_n_stride",
-                                      "z_batch_stride", "z_d_stride", "out_batch_stride", "out_d_stride")]
-                + [(n, vp) for n in ("state", "x", "dt", "A", "B", "C", "D", "z", "dt_bias", "out")])
-
-
-class LayerNormParams(ctypes.Structure):
-    _fields_ = ([(n, i32) for n in ("batch", "seqlen", "channels", "itype", "otype")] + [("eps", ctypes.c_float)]
-                + [(n, i64) for n in ("x_batch_stride", "x_c_stride", "y_batch_stride", "y_token_stride",
-                                      "dx_batch_stride", "dx_c_stride")]
-                + [(n, vp) for n in ("x", "weight", "bias", "y", "mean", "rstd", "dy", "dx", "dweight", "dbias", "workspace")])
-
-
-class WgradNtParams(ctypes.Structure):
-    _fields_ = ([(n, i32) for n in ("groups", "m", "n", "k", "itype", "_pad0")]
-                + [(n, i64) for n in ("a_group_stride", "a_row_stride", "b_group_stride", "b_row_stride",
-                                      "out_group_stride", "out_row_stride")]
-                + [(n, vp) for n in ("a", "b", "out")])
-
-
-class AddLayerNormParams(ctypes.Structure):
-    _fields_ = ([(n, i32) for n in ("batch", "seqlen", "channels", "itype", "btype", "otype")]
-                + [("eps", ctypes.c_float), ("_pad0", i32)]
-                + [(n, i64) for n in ("x_batch_stride", "x_c_stride", "x_new_batch_stride", "x_new_c_stride",
-                                      "branch_batch_stride", "branch_token_stride", "y_batch_stride", "y_token_stride",
-                                      "dres_batch_stride", "dres_c_stride", "dx_batch_stride", "dx_c_stride",
-                                      "dbranch_batch_stride", "dbranch_token_stride")]
-                + [(n, vp) for n in ("x", "branch", "scale", "weight", "bias", "x_new", "y", "mean", "rstd", "dy", "dres",
-                                     "dx", "dbranch", "dweight", "dbias", "workspace")])
-
-
-class SegLossParams(ctypes.Structure):
-    _fields_ = ([(n, i32) for n in ("batch", "classes", "pixels", "itype", "ttype")]
-                + [(n, ctypes.c_float) for n in ("gamma", "focal_weight", "tversky_weight", "tversky_alpha", "tversky_beta",
-                                                 "smooth", "eps")]
-                + [(n, i64) for n in ("logits_batch_stride", "logits_c_stride", "dlogits_batch_stride", "dlogits_c_stride",
-                                      "target_batch_stride")]
-                + [(n, vp) for n in ("logits", "target", "alpha", "loss", "coef", "workspace")]
-                + [("workspace_bytes", i64), ("grad_out", vp), ("dlogits", vp)])
-
-
-class SegMetricsParams(ctypes.Structure):
-    _fields_ = ([(n, i32) for n in ("batch", "classes", "pixels", "itype", "ttype", "_pad0")]
-                + [(n, i64) for n in ("logits_batch_stride", "logits_c_stride", "target_batch_stride", "pred_batch_stride")]
-                + [(n, vp) for n in ("logits", "target", "counts", "pred", "state", "workspace")]
-                + [("workspace_bytes", i64)])
-
-
-class UpsampleParams(ctypes.Structure):
-    _fields_ = ([(n, i32) for n in ("batch", "channels", "in_h", "in_w", "out_h", "out_w", "itype", "layout")]
-                + [("x_batch_stride", i64), ("y_batch_stride", i64)]
-                + [(n, vp) for n in ("x", "y", "dy", "dx")])
-
-
-class DecodeHeadParams(ctypes.Structure):
-    """No vivim_sizeof row (and not in STRUCTS): the caller states its sizeof in struct_bytes and the entry point refuses
-    any other value."""
-    _fields_ = ([(n, i32) for n in ("struct_bytes", "batch", "hidden", "classes", "n_maps", "out_h", "out_w", "itype")]
-                + [("map_h", i32 * 4), ("map_w", i32 * 4), ("map_batch_stride", i64 * 4), ("logits_batch_stride", i64),
-                   ("maps", vp * 4)]
-                + [(n, vp) for n in ("bias", "w_out", "b_out", "logits")])
-
-
-class TokenLayerNormParams(ctypes.Structure):
-    """As DecodeHeadParams: no vivim_sizeof row, not in STRUCTS, its sizeof stated in struct_bytes."""
-    _fields_ = ([(n, i32) for n in ("struct_bytes", "rows", "channels", "itype", "otype")] + [("eps", ctypes.c_float)]
-                + [(n, i64) for n in ("x_row_stride", "y_row_stride", "dy_row_stride", "dx_row_stride")]
-                + [(n, vp) for n in ("x", "weight", "bias", "y", "mean", "rstd", "dy", "dx", "dweight", "dbias", "workspace")])
-
-
-class TokenAddNormParams(ctypes.Structure):
-    """As TokenLayerNormParams: no vivim_sizeof row, not in STRUCTS, its sizeof stated in struct_bytes."""
-    _fields_ = ([(n, i32) for n in ("struct_bytes", "rows", "channels", "rows_per_sample", "btype", "rtype", "otype", "rms")]
-                + [("eps", ctypes.c_float), ("_pad0", i32)]
-                + [(n, i64) for n in ("branch_row_stride", "res_row_stride", "res_out_row_stride", "y_row_stride", "dy_row_stride",
-                                      "dres_row_stride", "dres_in_row_stride", "dbranch_row_stride")]
-                + [(n, vp) for n in ("branch", "res", "scale", "weight", "bias", "res_out", "y", "mean", "rstd", "dy", "dres",
-                                     "dres_in", "dbranch", "dweight", "dbias", "workspace")])
-
-
-OPT_CHUNK, OPT_MAX_TENSORS, OPT_STATE_WORDS = 4096, 248, 16          # VIVIM_OPT_* of the header
-
-
-class OptStepParams(ctypes.Structure):
-    """As TokenLayerNormParams: no vivim_sizeof row, not in STRUCTS, its sizeof stated in struct_bytes.  `grads` and `numel` are
-    host arrays of `count` entries; the tables, the record and the workspace are device memory."""
-    _fields_ = ([(n, i32) for n in ("struct_bytes", "count", "first_tensor", "first_block", "n_blocks", "total_blocks", "scaled",
-                                    "has_max_norm")]
-                + [(n, ctypes.c_double) for n in ("max_norm", "lr", "beta1", "beta2", "eps", "weight_decay")]
-                + [("grads", ctypes.POINTER(vp)), ("numel", ctypes.POINTER(i64))]
-                + [(n, vp) for n in ("params", "exp_avg", "exp_avg_sq", "block_map", "state", "workspace")]
-                + [("workspace_bytes", i64)])
-
-
-class OptMwParams(ctypes.Structure):
-    """vivim_opt_mw_params: OptStepParams field for field, then the masters' table and the 16-bit type (F16 / BF16) of the call's
-    parameters and gradients.  Its sizeof is stated in struct_bytes."""
-    _fields_ = OptStepParams._fields_ + [("masters", vp), ("dtype", i32), ("_pad0", i32)]
-
-
-# The structs in vivim_sizeof order.
-STRUCTS = (SsmFwdParams, SsmBwdParams, ConvFwdParams, ConvBwdParams, DwConvParams, DwConvWgradParams, DirParams,
-           ConvUpdateParams, StateUpdateParams, LayerNormParams, WgradNtParams, AddLayerNormParams, SegLossParams,
-           SegMetricsParams, UpsampleParams)
+# The one table kept by hand: C struct -> Python class.  Everything else about the ABI -- fields, entry points, constants --
+# is read from the header.  The order is vivim_sizeof's (not the header's: wgrad_nt comes before add_layernorm); the structs
+# that open with `struct_bytes` have no vivim_sizeof row and come last.
+STRUCT_NAMES = {
+    "vivim_ssm_fwd_params": "SsmFwdParams", "vivim_ssm_bwd_params": "SsmBwdParams",
+    "vivim_conv_fwd_params": "ConvFwdParams", "vivim_conv_bwd_params": "ConvBwdParams",
+    "vivim_dwconv_params": "DwConvParams", "vivim_dwconv_wgrad_params": "DwConvWgradParams",
+    "vivim_dir_params": "DirParams", "vivim_conv_update_params": "ConvUpdateParams",
+    "vivim_state_update_params": "StateUpdateParams", "vivim_layernorm_params": "LayerNormParams",
+    "vivim_wgrad_nt_params": "WgradNtParams", "vivim_add_layernorm_params": "AddLayerNormParams",
+    "vivim_seg_loss_params": "SegLossParams", "vivim_seg_metrics_params": "SegMetricsParams",
+    "vivim_upsample_params": "UpsampleParams",
+    "vivim_decode_head_params": "DecodeHeadParams", "vivim_token_layernorm_params": "TokenLayerNormParams",
+    "vivim_token_add_norm_params": "TokenAddNormParams", "vivim_opt_step_params": "OptStepParams",
+    "vivim_opt_mw_params": "OptMwParams",
+}
 
 # One entry per exported function: its params struct (or None), the ctypes types of the arguments between `params` and
 # `stream` in the C signature, whether a stream comes last, and the restype.
 Entry = collections.namedtuple("Entry", "struct extra stream restype")
-_int, _size = ctypes.c_int, ctypes.c_size_t
+
+_FIELD_TYPES = {"int32_t": i32, "int64_t": i64, "float": ctypes.c_float, "double": ctypes.c_double,
+                "void *": vp, "const void *": vp, "const void *const *": ctypes.POINTER(vp),
+                "const int64_t *": ctypes.POINTER(i64)}
+_ARG_TYPES = {"void *": vp, "size_t": ctypes.c_size_t, "int": ctypes.c_int}
+_RESTYPES = {"int": ctypes.c_int, "size_t": ctypes.c_size_t, "const char *": ctypes.c_char_p}
+_DIRECTIVES = r"\s*#\s*(include|define|ifndef\s+VIVIM_HIP_H|endif)\b"         # what may stand outside a struct
 
 
-def _kernel(struct, *extra):
-    return Entry(struct, extra, True, _int)
+def _refuse(what, text):
+    raise ValueError(f"vivim_hip.h: {what}: {' '.join(text.split())!r}")
 
 
-def _query(struct, restype=_size):
-    return Entry(struct, (), False, restype)
+def _ctype(text):
+    """Canonical spelling of a C type: 'const  void * const*' -> 'const void *const *'."""
+    return re.sub(r"\s*\*\s*", " *", " ".join(text.split()))
 
 
-ENTRY_POINTS = {
-    "vivim_abi_version": Entry(None, (), False, _int),
-    "vivim_last_error": Entry(None, (), False, ctypes.c_char_p),
-    "vivim_scan_chunk_len": Entry(None, (_int,), False, _int),
-    "vivim_sizeof": Entry(None, (_int,), False, _size),
-    "vivim_set_tuning": Entry(None, (_int, _int), False, _int),
-    "vivim_scan_ckpt_len": _query(SsmFwdParams, _int),
-    "vivim_scan_fwd_workspace_bytes": _query(SsmFwdParams),
-    "vivim_scan_bwd_workspace_bytes": _query(SsmFwdParams),
-    "vivim_selective_scan_fwd": _kernel(SsmFwdParams),
-    "vivim_selective_scan_fwd_lean": _kernel(SsmFwdParams, vp),
-    "vivim_selective_scan_bwd": _kernel(SsmBwdParams),
-    "vivim_scan_bwd_det_workspace_bytes": _query(SsmFwdParams),
-    "vivim_scan_bwd_det_call_workspace_bytes": _query(SsmBwdParams),
-    "vivim_selective_scan_bwd_det": _kernel(SsmBwdParams, vp, _size),
-    "vivim_causal_conv1d_fwd": _kernel(ConvFwdParams),
-    "vivim_causal_conv1d_bwd": _kernel(ConvBwdParams),
-    "vivim_causal_conv1d_bwd_det_workspace_bytes": _query(ConvFwdParams),
-    "vivim_causal_conv1d_bwd_det": _kernel(ConvBwdParams, vp, _size),
-    "vivim_dwconv_fwd": _kernel(DwConvParams),
-    "vivim_dwconv_wgrad": _kernel(DwConvWgradParams),
-    "vivim_dwconv_wgrad_det_workspace_bytes": _query(DwConvWgradParams),
-    "vivim_dwconv_wgrad_det": _kernel(DwConvWgradParams, vp, _size),
-    "vivim_dir_scatter": _kernel(DirParams),
-    "vivim_dir_gather": _kernel(DirParams),
-    "vivim_causal_conv1d_update": _kernel(ConvUpdateParams),
-    "vivim_selective_state_update": _kernel(StateUpdateParams),
-    "vivim_layernorm_cm_fwd": _kernel(LayerNormParams),
-    "vivim_layernorm_cm_bwd": _kernel(LayerNormParams),
-    "vivim_layernorm_bwd_workspace_bytes": _query(LayerNormParams),
-    "vivim_wgrad_nt": _kernel(WgradNtParams),
-    "vivim_add_layernorm_cm_fwd": _kernel(AddLayerNormParams),
-    "vivim_add_layernorm_cm_bwd": _kernel(AddLayerNormParams),
-    "vivim_add_layernorm_bwd_workspace_bytes": _query(AddLayerNormParams),
-    "vivim_seg_loss_fwd": _kernel(SegLossParams),
-    "vivim_seg_loss_bwd": _kernel(SegLossParams),
-    "vivim_seg_loss_workspace_bytes": _query(SegLossParams),
-    "vivim_seg_metrics": _kernel(SegMetricsParams),
-    "vivim_seg_metrics_workspace_bytes": _query(SegMetricsParams),
-    "vivim_upsample_bilinear2d_fwd": _kernel(UpsampleParams),
-    "vivim_upsample_bilinear2d_bwd": _kernel(UpsampleParams),
-    "vivim_decode_head_fwd": Entry(None, (ctypes.POINTER(DecodeHeadParams),), True, _int),
-    "vivim_token_layernorm_fwd": Entry(None, (ctypes.POINTER(TokenLayerNormParams),), True, _int),
-    "vivim_token_layernorm_bwd": Entry(None, (ctypes.POINTER(TokenLayerNormParams),), True, _int),
-    "vivim_token_layernorm_bwd_workspace_bytes": Entry(None, (ctypes.POINTER(TokenLayerNormParams),), False, _size),
-    "vivim_token_add_norm_fwd": Entry(None, (ctypes.POINTER(TokenAddNormParams),), True, _int),
-    "vivim_token_add_norm_bwd": Entry(None, (ctypes.POINTER(TokenAddNormParams),), True, _int),
-    "vivim_token_add_norm_bwd_workspace_bytes": Entry(None, (ctypes.POINTER(TokenAddNormParams),), False, _size),
-    "vivim_opt_grad_stats": Entry(None, (ctypes.POINTER(OptStepParams),), True, _int),
-    "vivim_opt_finalise": Entry(None, (ctypes.POINTER(OptStepParams),), True, _int),
-    "vivim_opt_adamw": Entry(None, (ctypes.POINTER(OptStepParams),), True, _int),
-    "vivim_opt_step_workspace_bytes": Entry(None, (ctypes.POINTER(OptStepParams),), False, _size),
-    "vivim_opt_grad_stats_mw": Entry(None, (ctypes.POINTER(OptMwParams),), True, _int),
-    "vivim_opt_adamw_mw": Entry(None, (ctypes.POINTER(OptMwParams),), True, _int),
-}
+def _declarator(text, table, context):
+    """'const void *u' -> ('u', c_void_p), 'int32_t map_h[4]' -> ('map_h', c_int32 * 4), the type looked up in `table`."""
+    m = re.fullmatch(r"([\w\s*]*?)(\w+)\s*(?:\[\s*(\d+)\s*\])?", text.strip())
+    if not m:                                                           # a bit-field, a function pointer, ...
+        _refuse("cannot parse the declarator", context)
+    if _ctype(m[1]) not in table:
+        _refuse(f"unknown type {_ctype(m[1])!r}", context)
+    ctype = table[_ctype(m[1])]
+    return m[2], (ctype * int(m[3]) if m[3] else ctype)
+
+
+def _has_sizeof_row(cls):
+    return cls._fields_[0][0] != "struct_bytes"       # such a struct states its own sizeof and the entry point checks it
+
+
+def parse_header(text, names=STRUCT_NAMES):
+    """-> (constants, classes, entry points) of a header written like include/vivim_hip.h: the `#define VIVIM_* <int>` and
+    enumerator values by name; one ctypes.Structure per `typedef struct { ... } vivim_*;`, by Python name in the order of
+    `names`; one Entry per function declaration, in header order.  ValueError on anything else: it never guesses."""
+    text = re.sub(r"/\*.*?\*/", " ", text, flags=re.S)
+    consts = {k: int(v) for k, v in re.findall(r"^[ \t]*#[ \t]*define[ \t]+(VIVIM_\w+)[ \t]+(-?\d+)[ \t]*$", text, flags=re.M)}
+    by_c_name = {}
+
+    def struct(m):
+        body, c_name = m[1], m[2]
+        if "{" in body or "#" in body:
+            _refuse("nested braces or a preprocessor line in a struct", m[0])
+        if c_name not in names:
+            _refuse("a struct without a Python name in STRUCT_NAMES", c_name)
+        types = {**_FIELD_TYPES, **by_c_name}                           # an earlier struct may be a field, by value
+        fields = []
+        for stmt in filter(None, (s.strip() for s in body.split(";"))):
+            base = re.match(r"(?:const\s+)?\w+", stmt) or _refuse("cannot parse the field", stmt)
+            first, *more = stmt.split(",")                              # `const void *u, *delta`: the stars belong to the names
+            for decl in [first] + [f"{base[0]} {d}" for d in more]:
+                fields.append(_declarator(decl, types, stmt))
+        by_c_name[c_name] = type(names[c_name], (ctypes.Structure,), {"_fields_": fields, "__module__": __name__})
+        return " "
+
+    def enum(m):
+        for item in filter(None, (s.strip() for s in m[1].split(","))):
+            kv = re.fullmatch(r"(\w+)\s*=\s*(-?\d+)", item) or _refuse("cannot parse the enumerator", item)
+            consts[kv[1]] = int(kv[2])
+        return " "
+
+    text = re.sub(r"typedef\s+struct\s*\{(.*?)\}\s*(\w+)\s*;", struct, text, flags=re.S)
+    text = re.sub(r"(?:typedef\s+)?enum\s*\{([^{}]*)\}\s*\w*\s*;", enum, text)
+    missing = [c for c in names if c not in by_c_name]
+    if missing:
+        _refuse("STRUCT_NAMES names structs the header does not have", ", ".join(missing))
+    text = re.sub(r"^[ \t]*#[ \t]*ifdef[ \t]+__cplusplus\b.*?^[ \t]*#[ \t]*endif\b", " ", text, flags=re.S | re.M)   # extern "C"
+    for line in re.findall(r"^[ \t]*#.*$", text, flags=re.M):
+        if not re.match(_DIRECTIVES, line):
+            _refuse("a preprocessor line it does not know", line)
+    text = re.sub(r"^[ \t]*#.*$", " ", text, flags=re.M)
+
+    entries = {}
+    for decl in filter(None, (s.strip() for s in text.split(";"))):     # what is left: function declarations
+        m = re.fullmatch(r"([\w\s*]+?)(\w+)\s*\(([\w\s*,]*)\)", decl) or _refuse("cannot parse the declaration", decl)
+        if _ctype(m[1]) not in _RESTYPES:
+            _refuse(f"unknown return type {_ctype(m[1])!r}", decl)
+        args = [] if m[3].strip() == "void" else [a.strip() for a in m[3].split(",")]
+        stream = bool(args) and re.fullmatch(r"void\s*\*\s*stream", args[-1]) is not None
+        args = args[:-1] if stream else args
+        params, extra = None, []
+        for k, arg in enumerate(args):
+            p = re.fullmatch(r"const\s+(vivim_\w+)\s*\*\s*\w+", arg) if k == 0 else None
+            if not p:
+                extra.append(_declarator(arg, _ARG_TYPES, decl)[1])
+            elif p[1] not in by_c_name:
+                _refuse(f"unknown struct {p[1]}", decl)
+            elif _has_sizeof_row(by_c_name[p[1]]):
+                params = by_c_name[p[1]]
+            else:
+                extra.append(ctypes.POINTER(by_c_name[p[1]]))
+        entries[m[2]] = Entry(params, tuple(extra), stream, _RESTYPES[_ctype(m[1])])
+    return consts, {names[c]: by_c_name[c] for c in names}, entries
+
+
+def _read_header():
+    try:
+        with open(HEADER) as f:
+            return f.read()
+    except OSError as e:
+        raise ImportError(f"{HEADER} cannot be read ({e}): the binding is derived from it") from e
+
+
+_consts, _classes, ENTRY_POINTS = parse_header(_read_header())
+globals().update(_classes)                              # SsmFwdParams ... OptMwParams, the classes STRUCT_NAMES names
+STRUCTS = tuple(c for c in _classes.values() if _has_sizeof_row(c))    # in vivim_sizeof order
 EXPORTS = tuple(ENTRY_POINTS)
+ABI_VERSION = _consts["VIVIM_ABI_VERSION"]
+F32, F16, BF16 = _consts["VIVIM_F32"], _consts["VIVIM_F16"], _consts["VIVIM_BF16"]
+OPT_CHUNK, OPT_MAX_TENSORS, OPT_STATE_WORDS = (_consts["VIVIM_OPT_" + n] for n in ("CHUNK", "MAX_TENSORS", "STATE_WORDS"))
 
 _lib = None
 
@@ -306,7 +182,7 @@ def lib():
             fn = getattr(L, name)
             fn.argtypes = ([ctypes.POINTER(e.struct)] if e.struct else []) + list(e.extra) + ([vp] if e.stream else [])
             fn.restype = e.restype
-        if L.vivim_abi_version() != 8:
+        if L.vivim_abi_version() != ABI_VERSION:
             raise ImportError("libvivim_hip.so ABI version mismatch")
         for which, st in enumerate(STRUCTS):
             if L.vivim_sizeof(which) != ctypes.sizeof(st):
