@@ -23,4 +23,9 @@ def __getattr__(name):
     if name in ("FusedStepAdamW", "lower_params", "raise_params"):   # the device-side clip + AdamW step (optimizer.py), likewise
         from . import optimizer
         return getattr(optimizer, name)
+    # the structure loss (structure_loss.py), likewise.  `vivim_amd.structure_loss` itself is that module, so the eager binary
+    # form is reached as vivim_amd.structure_loss.structure_loss
+    if name in ("multiclass_structure_loss", "structure_loss_fused", "multiclass_structure_loss_fused"):
+        from .structure_loss import multiclass_structure_loss, multiclass_structure_loss_fused, structure_loss_fused  # noqa: F401
+        return locals()[name]
     raise AttributeError(f"module {__name__!r} has no attribute {name!r}")

@@ -1,7 +1,9 @@
 """ctypes binding of libvivim_hip.so (C ABI: include/vivim_hip.h).
 
 The header is the one description of the ABI: it is parsed once, at import, into the params structs, the entry-point table
-and the constants below.  The parser refuses whatever it does not understand instead of guessing.
+and the constants below.  The parser refuses whatever it does not understand instead of guessing.  That header is frozen at
+ABI version 8; what was added since is declared in include/vivim_hip_ext.h, parsed the same way into EXT_STRUCT_NAMES and
+EXT_ENTRY_POINTS, and exported from the same library: `call` and `launch` take a name of either table.
 
 The library is the product: if it is missing or fails to load this module raises -- there is no
 PyTorch/CPU fallback anywhere in vivim_amd.
@@ -18,6 +20,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(_HERE, "csrc")
 SO_PATH = os.environ.get("VIVIM_LIB") or os.path.join(CSRC, "libvivim_hip.so")   # VIVIM_LIB: A/B builds
 HEADER = os.path.join(os.path.dirname(_HERE), "include", "vivim_hip.h")
+EXT_HEADER = os.path.join(os.path.dirname(_HERE), "include", "vivim_hip_ext.h")    # what was added after ABI version 8
 
 i32, i64, vp = ctypes.c_int32, ctypes.c_int64, ctypes.c_void_p
 
@@ -37,6 +40,9 @@ STRUCT_NAMES = {
     "vivim_token_add_norm_params": "TokenAddNormParams", "vivim_opt_step_params": "OptStepParams",
     "vivim_opt_mw_params": "OptMwParams",
 }
+# The same table for include/vivim_hip_ext.h.  vivim_hip.h is frozen at version 8 (and with it the tables derived from it below);
+# a struct added since is declared there, opens with `struct_bytes` and has no vivim_sizeof row.
+EXT_STRUCT_NAMES = {"vivim_structure_loss_params": "StructureLossParams"}
 
 # One entry per exported function: its params struct (or None), the ctypes types of the arguments between `params` and
 # `stream` in the C signature, whether a stream comes last, and the restype.
@@ -47,7 +53,7 @@ _FIELD_TYPES = {"int32_t": i32, "int64_t": i64, "float": ctypes.c_float, "double
                 "const int64_t *": ctypes.POINTER(i64)}
 _ARG_TYPES = {"void *": vp, "size_t": ctypes.c_size_t, "int": ctypes.c_int}
 _RESTYPES = {"int": ctypes.c_int, "size_t": ctypes.c_size_t, "const char *": ctypes.c_char_p}
-_DIRECTIVES = r"\s*#\s*(include|define|ifndef\s+VIVIM_HIP_H|endif)\b"         # what may stand outside a struct
+_DIRECTIVES = r"\s*#\s*(include|define|ifndef\s+VIVIM_HIP(_EXT)?_H|endif)\b"        # what may stand outside a struct
 
 
 def _refuse(what, text):
@@ -138,12 +144,13 @@ def parse_header(text, names=STRUCT_NAMES):
     return consts, {names[c]: by_c_name[c] for c in names}, entries
 
 
-def _read_header():
+def _read_header(path=None):
+    path = path or HEADER
     try:
-        with open(HEADER) as f:
+        with open(path) as f:
             return f.read()
     except OSError as e:
-        raise ImportError(f"{HEADER} cannot be read ({e}): the binding is derived from it") from e
+        raise ImportError(f"{path} cannot be read ({e}): the binding is derived from it") from e
 
 
 _consts, _classes, ENTRY_POINTS = parse_header(_read_header())
@@ -153,6 +160,10 @@ EXPORTS = tuple(ENTRY_POINTS)
 ABI_VERSION = _consts["VIVIM_ABI_VERSION"]
 F32, F16, BF16 = _consts["VIVIM_F32"], _consts["VIVIM_F16"], _consts["VIVIM_BF16"]
 OPT_CHUNK, OPT_MAX_TENSORS, OPT_STATE_WORDS = (_consts["VIVIM_OPT_" + n] for n in ("CHUNK", "MAX_TENSORS", "STATE_WORDS"))
+_, _ext_classes, EXT_ENTRY_POINTS = parse_header(_read_header(EXT_HEADER), EXT_STRUCT_NAMES)
+if any(_has_sizeof_row(c) for c in _ext_classes.values()) or set(EXT_ENTRY_POINTS) & set(ENTRY_POINTS):
+    raise ImportError(f"{EXT_HEADER}: a struct that does not open with struct_bytes, or a function vivim_hip.h already declares")
+globals().update(_ext_classes)                          # StructureLossParams
 
 _lib = None
 
@@ -178,7 +189,7 @@ def lib():
         # and every launch of ours then fails with "no ROCm-capable device is detected" (seen with build() followed by
         # smoke() in one process)
         L = ctypes.CDLL(SO_PATH)
-        for name, e in ENTRY_POINTS.items():
+        for name, e in {**ENTRY_POINTS, **EXT_ENTRY_POINTS}.items():
             fn = getattr(L, name)
             fn.argtypes = ([ctypes.POINTER(e.struct)] if e.struct else []) + list(e.extra) + ([vp] if e.stream else [])
             fn.restype = e.restype
@@ -242,6 +253,10 @@ def algorithmic_bytes(name, P):
     if name.startswith("vivim_seg_metrics"):                            # logits, labels, the prediction map if wanted, the counts
         n = P.batch * P.pixels
         return n * (P.classes * _ISIZE[P.itype] + (8 if P.ttype == 0 else 1) + (1 if P.pred else 0)) + 12 * P.batch * P.classes
+    if name.startswith("vivim_structure_loss"):                         # logits (+ dlogits), labels, the per-image factors
+        n = P.batch * P.height * P.width
+        return (n * ((2 if name.endswith("bwd") else 1) * P.classes * _ISIZE[P.itype] + (8 if P.ttype == 0 else 1))
+                + 12 * P.batch * P.classes)
     if name.startswith("vivim_seg_loss"):                               # logits (+ dlogits), labels, the per-image factors
         n = P.batch * P.pixels
         return (n * ((2 if name.endswith("bwd") else 1) * P.classes * _ISIZE[P.itype] + (8 if P.ttype == 0 else 1))

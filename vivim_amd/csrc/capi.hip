@@ -8,6 +8,7 @@
 #include <string.h>
 #include <type_traits>
 #include "../../include/vivim_hip.h"
+#include "../../include/vivim_hip_ext.h"
 #include "det.cuh"
 
 namespace vivim {
@@ -61,6 +62,9 @@ void opt_finalise_launch(const vivim_opt_step_params&, hipStream_t);
 void opt_adamw_launch(const vivim_opt_step_params&, hipStream_t);
 void opt_grad_stats_mw_launch(const vivim_opt_step_params&, int dtype, hipStream_t);
 void opt_adamw_mw_launch(const vivim_opt_step_params&, const void* masters, int dtype, hipStream_t);
+bool structure_loss_dispatch(const vivim_structure_loss_params&, bool bwd, hipStream_t);      // structure_loss.hip
+size_t structure_loss_workspace_bytes(const vivim_structure_loss_params&);
+int64_t structure_loss_tiles(const vivim_structure_loss_params&);
 }  // namespace vivim
 
 static thread_local char g_err[512] = "";
@@ -920,6 +924,75 @@ int vivim_opt_adamw_mw(const vivim_opt_mw_params* p, void* stream) {
     if (!(q.lr >= 0.0 && q.eps >= 0.0 && q.weight_decay >= 0.0))
         return fail(VIVIM_ERR_INVALID, "%s: lr = %g, eps = %g, weight_decay = %g: none may be negative", fn, q.lr, q.eps, q.weight_decay);
     vivim::opt_adamw_mw_launch(q, p->masters, p->dtype, as_stream(stream));
+    return after_launch(fn);
+}
+
+// ---- include/vivim_hip_ext.h: what was added after ABI version 8 ----
+
+static bool structure_loss_sizes_ok(const vivim_structure_loss_params* p) {
+    return p->batch > 0 && p->classes > 0 && p->height > 0 && p->width > 0;
+}
+
+// every refusal the forward and the backward of the structure loss share, before any launch
+static int check_structure_loss(const vivim_structure_loss_params* p, const char* fn) {
+    if (p == nullptr) return fail(VIVIM_ERR_INVALID, "%s: params is NULL", fn);
+    if (p->struct_bytes != (int32_t)sizeof(vivim_structure_loss_params))
+        return fail(VIVIM_ERR_INVALID, "%s: struct_bytes = %d, this library's vivim_structure_loss_params has %zu", fn, p->struct_bytes,
+                    sizeof(vivim_structure_loss_params));
+    if (!dtype_ok(p->itype) || (p->ttype != 0 && p->ttype != 1))
+        return fail(VIVIM_ERR_INVALID, "%s: itype = %d, ttype = %d: logits are fp32 / fp16 / bf16 (0 / 1 / 2), targets int64 / uint8 (0 / 1)",
+                    fn, p->itype, p->ttype);
+    if (!structure_loss_sizes_ok(p))
+        return fail(VIVIM_ERR_INVALID, "%s: batch = %d, classes = %d, height = %d, width = %d: every size must be positive", fn, p->batch,
+                    p->classes, p->height, p->width);
+    if (p->classes > 8)
+        return fail(VIVIM_ERR_UNSUPPORTED, "%s: %d classes: the kernels are built for 1 to 8 classes", fn, p->classes);
+    if (p->first_class < 0 || p->first_class > 255)
+        return fail(VIVIM_ERR_INVALID, "%s: first_class = %d: labels are compared as values in [0, 256)", fn, p->first_class);
+    // pixel offsets inside a plane, tile origins + halo, and the grid are 32-bit integers
+    if ((int64_t)p->height * p->width > INT32_MAX - 4096 || (int64_t)p->batch * vivim::structure_loss_tiles(*p) > INT32_MAX)
+        return fail(VIVIM_ERR_INVALID, "%s: batch = %d, height = %d, width = %d: the index range overflows int32", fn, p->batch, p->height,
+                    p->width);
+    const uintptr_t ib = p->itype == VIVIM_F32 ? 4 : 2;
+    if (p->logits == nullptr || !aligned(p->logits, ib))
+        return fail(VIVIM_ERR_INVALID, "%s: logits at %p: need a %d-byte aligned pointer", fn, p->logits, (int)ib);
+    if (p->target == nullptr || !aligned(p->target, p->ttype == 0 ? 8 : 1))
+        return fail(VIVIM_ERR_INVALID, "%s: target at %p: need a %d-byte aligned pointer", fn, p->target, p->ttype == 0 ? 8 : 1);
+    return VIVIM_OK;
+}
+
+size_t vivim_structure_loss_workspace_bytes(const vivim_structure_loss_params* p) {
+    if (p == nullptr || p->struct_bytes != (int32_t)sizeof(vivim_structure_loss_params) || !structure_loss_sizes_ok(p) || p->classes > 8 ||
+        !dtype_ok(p->itype))
+        return 0;
+    return vivim::structure_loss_workspace_bytes(*p);
+}
+
+int vivim_structure_loss_fwd(const vivim_structure_loss_params* p, void* stream) {
+    const char* fn = "structure_loss_fwd";
+    if (int rc = check_structure_loss(p, fn)) return rc;
+    if (p->loss == nullptr || !aligned(p->loss, 4)) return fail(VIVIM_ERR_INVALID, "%s: loss at %p: need a 4-byte aligned pointer", fn, p->loss);
+    if (!aligned(p->coef, 4))                                          // NULL: not wanted
+        return fail(VIVIM_ERR_INVALID, "%s: coef at %p: need a 4-byte aligned pointer (or NULL)", fn, p->coef);
+    const size_t need = vivim::structure_loss_workspace_bytes(*p);
+    if (p->workspace == nullptr || !aligned(p->workspace, 8) || p->workspace_bytes < 0 || (size_t)p->workspace_bytes < need)
+        return bad_workspace(fn, "vivim_structure_loss_workspace_bytes", p->workspace_bytes, p->workspace, 8, need);
+    if (!vivim::structure_loss_dispatch(*p, false, as_stream(stream)))
+        return fail(VIVIM_ERR_UNSUPPORTED, "%s not implemented for input type %d", fn, p->itype);
+    return after_launch(fn);
+}
+
+int vivim_structure_loss_bwd(const vivim_structure_loss_params* p, void* stream) {
+    const char* fn = "structure_loss_bwd";
+    if (int rc = check_structure_loss(p, fn)) return rc;
+    const uintptr_t ib = p->itype == VIVIM_F32 ? 4 : 2;
+    if (p->coef == nullptr || !aligned(p->coef, 4)) return fail(VIVIM_ERR_INVALID, "%s: coef at %p: need a 4-byte aligned pointer", fn, p->coef);
+    if (p->grad_out == nullptr || !aligned(p->grad_out, 4))
+        return fail(VIVIM_ERR_INVALID, "%s: grad_out at %p: need a 4-byte aligned pointer", fn, p->grad_out);
+    if (p->dlogits == nullptr || !aligned(p->dlogits, ib))
+        return fail(VIVIM_ERR_INVALID, "%s: dlogits at %p: need a %d-byte aligned pointer", fn, p->dlogits, (int)ib);
+    if (!vivim::structure_loss_dispatch(*p, true, as_stream(stream)))
+        return fail(VIVIM_ERR_UNSUPPORTED, "%s not implemented for input type %d", fn, p->itype);
     return after_launch(fn);
 }
 

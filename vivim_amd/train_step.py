@@ -179,14 +179,31 @@ def synthetic_batch(batch, clip_length, image_size, num_classes, device, seed):
 _SCALERS = {}
 
 
-def train_step(model, optimizer, clip, onehot, num_classes, amp_dtype=torch.bfloat16, clip_grad_norm=None, fused_loss=False):
+def _criterion_loss(criterion, logits, target, num_classes, fused_loss):
+    """The loss `criterion` names: "recall_focused" (recall_focused_loss, the default) or "structure"
+    (structure_loss.multiclass_structure_loss); `fused_loss` takes either from its fused kernels."""
+    if criterion == "recall_focused":
+        if fused_loss:
+            from .seg_loss import recall_focused_loss_fused
+            return recall_focused_loss_fused(logits, target, num_classes)
+        return recall_focused_loss(logits, target, num_classes)
+    if criterion == "structure":
+        from . import structure_loss as sl
+        return (sl.multiclass_structure_loss_fused if fused_loss else sl.multiclass_structure_loss)(logits, target, num_classes)
+    raise ValueError(f"criterion {criterion!r}: expected 'recall_focused' or 'structure'")
+
+
+def train_step(model, optimizer, clip, onehot, num_classes, amp_dtype=torch.bfloat16, clip_grad_norm=None, fused_loss=False,
+               criterion="recall_focused"):
     """One fwd + loss + bwd + optimizer step; returns the detached loss.  fp16 autocast runs under a GradScaler (the
     reference trains with Trainer(precision=16), multiclass_training_folds.py:800-811; bf16 / fp32 need none);
     `clip_grad_norm` (the reference's gradient_clip_val) clips the global gradient norm before the update.
     `fused_loss=True` takes the loss and its gradient from the fused kernels (seg_loss.recall_focused_loss_fused: three
     launches, cancellation-free) instead of the eager chain of recall_focused_loss; opt-in, the default step is unchanged.
     With a `FusedStepAdamW` the loss is multiplied by the optimizer's loss scale ON THE DEVICE (fp16) and everything after the
-    backward is `optimizer.step(max_norm=clip_grad_norm, scaled=...)`: no `_SCALERS` entry, no host synchronisation."""
+    backward is `optimizer.step(max_norm=clip_grad_norm, scaled=...)`: no `_SCALERS` entry, no host synchronisation.
+    `criterion="structure"` trains with the structure loss instead (structure_loss.multiclass_structure_loss; with `fused_loss=True`
+    its fused kernels); the default criterion is unchanged."""
     check_autocast_dtype(model, amp_dtype)
     if not model.training:                 # Module.train() walks all ~4000 submodules: 3 ms of host time when repeated per step
         model.train()
@@ -194,11 +211,7 @@ def train_step(model, optimizer, clip, onehot, num_classes, amp_dtype=torch.bflo
         logits = model(clip)                                   # (B*nf, C, H, W)
     B, T = onehot.shape[:2]
     target = onehot.argmax(dim=2).view(B * T, *onehot.shape[-2:])
-    if fused_loss:
-        from .seg_loss import recall_focused_loss_fused
-        loss = recall_focused_loss_fused(logits, target, num_classes)
-    else:
-        loss = recall_focused_loss(logits, target, num_classes)
+    loss = _criterion_loss(criterion, logits, target, num_classes, fused_loss)
     optimizer.zero_grad(set_to_none=True)
     if isinstance(optimizer, FusedStepAdamW):
         scaled = amp_dtype == torch.float16
@@ -228,10 +241,10 @@ def train_step(model, optimizer, clip, onehot, num_classes, amp_dtype=torch.bflo
     return loss.detach()
 
 
-def eval_step(model, clip, onehot, num_classes, tracker=None, amp_dtype=torch.bfloat16, fused_loss=False):
+def eval_step(model, clip, onehot, num_classes, tracker=None, amp_dtype=torch.bfloat16, fused_loss=False, criterion="recall_focused"):
     """The validation counterpart of train_step: forward under no_grad + autocast, the loss (eager, or the fused kernels with
     `fused_loss=True`), and, when a `tracker` (seg_metrics.SegMetricsTracker) is given, its update with the logits and the label
-    map -- two launches on the device, no host synchronisation.  Returns the detached loss."""
+    map -- two launches on the device, no host synchronisation.  `criterion` as in train_step.  Returns the detached loss."""
     check_autocast_dtype(model, amp_dtype)
     if model.training:                     # Module.eval() walks all ~4000 submodules, like train() in train_step
         model.eval()
@@ -240,11 +253,7 @@ def eval_step(model, clip, onehot, num_classes, tracker=None, amp_dtype=torch.bf
             logits = model(clip)                               # (B*nf, C, H, W)
         B, T = onehot.shape[:2]
         target = onehot.argmax(dim=2).view(B * T, *onehot.shape[-2:])
-        if fused_loss:
-            from .seg_loss import recall_focused_loss_fused
-            loss = recall_focused_loss_fused(logits, target, num_classes)
-        else:
-            loss = recall_focused_loss(logits, target, num_classes)
+        loss = _criterion_loss(criterion, logits, target, num_classes, fused_loss)
         if tracker is not None:
             tracker.update(logits, target)
     return loss.detach()
