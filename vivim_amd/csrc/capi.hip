@@ -7,65 +7,12 @@
 #include <stdio.h>
 #include <string.h>
 #include <type_traits>
-#include "../../include/vivim_hip.h"
-#include "../../include/vivim_hip_ext.h"
-#include "det.cuh"
+#include "ops.cuh"
 
-namespace vivim {
-bool conv_fwd_dispatch(const vivim_conv_fwd_params&, hipStream_t);
-bool conv_bwd_dispatch(const vivim_conv_bwd_params&, hipStream_t);
-bool conv_cl_fwd_dispatch(const vivim_conv_fwd_params&, hipStream_t);                // conv1d_cl.hip (channel-last)
-bool conv_cl_bwd_dispatch(const vivim_conv_bwd_params&, hipStream_t);
-bool ssm_fwd_dispatch(const vivim_ssm_fwd_params&, hipStream_t);
-bool ssm_fwd_lean_dispatch(const vivim_ssm_fwd_params&, void* last_state, hipStream_t);   // scan_plan.hip
-bool dwconv_fwd_dispatch(const vivim_dwconv_params&, hipStream_t);
-bool dwconv_wgrad_dispatch(const vivim_dwconv_wgrad_params&, hipStream_t);
-template <bool GATHER> bool dir_dispatch(const vivim_dir_params&, hipStream_t);     // dirmap.hip
-void conv_update_launch(const vivim_conv_update_params&, hipStream_t);               // update.hip
-void state_update_launch(const vivim_state_update_params&, hipStream_t);
-bool ssm_bwd_dispatch(const vivim_ssm_bwd_params&, hipStream_t);
-int scan_chunk_len(int itype);
-int scan_ckpt_len(const vivim_ssm_fwd_params&);
-size_t scan_bwd_workspace_bytes(const vivim_ssm_fwd_params&);
-size_t scan_bwd_det_workspace_bytes(const vivim_ssm_fwd_params&);                   // scan_plan.hip
-size_t scan_bwd_det_call_workspace_bytes(const vivim_ssm_bwd_params&);
-size_t conv_bwd_det_slots(const vivim_conv_fwd_params&);                             // conv1d.hip / conv1d_cl.hip
-bool conv_bwd_det_launch(const vivim_conv_bwd_params&, hipStream_t);
-size_t conv_cl_bwd_det_slots(const vivim_conv_fwd_params&);
-bool conv_cl_bwd_det_launch(const vivim_conv_bwd_params&, hipStream_t);
-size_t dwconv_wgrad_det_workspace_bytes(const vivim_dwconv_wgrad_params&);           // dwconv.hip
-int dwconv_wgrad_det_dispatch(const vivim_dwconv_wgrad_params&, void*, size_t, hipStream_t);
-int ssm_bwd_det_dispatch(const vivim_ssm_bwd_params&, void* det_ws, size_t det_ws_bytes, hipStream_t);
-bool layernorm_dispatch(const vivim_layernorm_params&, bool bwd, hipStream_t);   // layernorm.hip
-size_t layernorm_bwd_workspace_bytes(const vivim_layernorm_params&);
-bool wgrad_nt_dispatch(const vivim_wgrad_nt_params&, hipStream_t);                 // wgrad.hip
-bool add_layernorm_dispatch(const vivim_add_layernorm_params&, bool bwd, hipStream_t);   // layernorm.hip, with the residual add
-size_t add_layernorm_bwd_workspace_bytes(const vivim_add_layernorm_params&);
-size_t scan_fwd_workspace_bytes(const vivim_ssm_fwd_params&);
-bool seg_loss_dispatch(const vivim_seg_loss_params&, bool bwd, hipStream_t);       // seg_loss.hip
-size_t seg_loss_workspace_bytes(const vivim_seg_loss_params&);
-bool seg_metrics_dispatch(const vivim_seg_metrics_params&, hipStream_t);          // seg_metrics.hip
-size_t seg_metrics_workspace_bytes(const vivim_seg_metrics_params&);
-bool upsample_dispatch(const vivim_upsample_params&, bool bwd, hipStream_t);      // upsample.hip
-int64_t upsample_blocks(const vivim_upsample_params&, bool bwd);
-bool decode_head_dispatch(const vivim_decode_head_params&, hipStream_t);          // decode_head.hip
-int64_t decode_head_blocks(const vivim_decode_head_params&);
-int decode_head_max_hidden();
-bool token_layernorm_dispatch(const vivim_token_layernorm_params&, bool bwd, hipStream_t);   // token_layernorm.hip
-bool token_layernorm_pair_ok(int itype, int otype);
-size_t token_layernorm_bwd_workspace_bytes(const vivim_token_layernorm_params&);
-bool token_add_norm_dispatch(const vivim_token_add_norm_params&, bool bwd, hipStream_t);       // the same file, with the residual add
-bool token_add_norm_pair_ok(int btype, int rtype);
-size_t token_add_norm_bwd_workspace_bytes(const vivim_token_add_norm_params&);
-void opt_grad_stats_launch(const vivim_opt_step_params&, hipStream_t);                        // optimizer.hip
-void opt_finalise_launch(const vivim_opt_step_params&, hipStream_t);
-void opt_adamw_launch(const vivim_opt_step_params&, hipStream_t);
-void opt_grad_stats_mw_launch(const vivim_opt_step_params&, int dtype, hipStream_t);
-void opt_adamw_mw_launch(const vivim_opt_step_params&, const void* masters, int dtype, hipStream_t);
-bool structure_loss_dispatch(const vivim_structure_loss_params&, bool bwd, hipStream_t);      // structure_loss.hip
-size_t structure_loss_workspace_bytes(const vivim_structure_loss_params&);
-int64_t structure_loss_tiles(const vivim_structure_loss_params&);
-}  // namespace vivim
+using vivim::Launch;
+using vivim::conv_channel_last;
+using vivim::elem_bytes;
+using vivim::vec_elems;
 
 static thread_local char g_err[512] = "";
 
@@ -97,6 +44,17 @@ static hipStream_t as_stream(void* stream) { return static_cast<hipStream_t>(str
 static int bad_workspace(const char* fn, const char* query, long long bytes, const void* at, int align, size_t need) {
     return fail(VIVIM_ERR_INVALID, "%s: workspace of %lld bytes at %p: need a %d-byte aligned one of %s() = %zu", fn, bytes, at, align,
                 query, need);
+}
+// the same for a workspace that the params struct carries, with its own alignment; VIVIM_OK: it will do
+static int check_workspace(const char* fn, const char* query, const void* ws, int64_t bytes, int align, size_t need) {
+    if (ws == nullptr || !aligned(ws, align) || bytes < 0 || (size_t)bytes < need) return bad_workspace(fn, query, bytes, ws, align, need);
+    return VIVIM_OK;
+}
+// a params struct of another library version; `name` is the struct's
+static int check_struct_bytes(const char* fn, const char* name, int32_t struct_bytes, size_t size) {
+    if (struct_bytes != (int32_t)size)
+        return fail(VIVIM_ERR_INVALID, "%s: struct_bytes = %d, this library's %s has %zu", fn, struct_bytes, name, size);
+    return VIVIM_OK;
 }
 
 // mode: the full forward, the backward (its `f` half), or the lean forward (no checkpoints; out_z alone when z is given)
@@ -239,10 +197,11 @@ size_t vivim_scan_bwd_det_call_workspace_bytes(const vivim_ssm_bwd_params* p) {
 int vivim_selective_scan_bwd_det(const vivim_ssm_bwd_params* p, void* det_ws, size_t det_ws_bytes, void* stream) {
     if (int rc = check_ssm_bwd(p)) return rc;
     switch (vivim::ssm_bwd_det_dispatch(*p, det_ws, det_ws_bytes, as_stream(stream))) {
-        case 0: break;
-        case 2: return bad_workspace("selective_scan_bwd_det", "vivim_scan_bwd_det_call_workspace_bytes", det_ws_bytes, det_ws, 16,
-                                     vivim::scan_bwd_det_call_workspace_bytes(*p));
-        default: return fail(VIVIM_ERR_UNSUPPORTED, "selective_scan_bwd_det not implemented for input type %d", p->f.itype);
+        case Launch::ok: break;
+        case Launch::bad_workspace:
+            return bad_workspace("selective_scan_bwd_det", "vivim_scan_bwd_det_call_workspace_bytes", det_ws_bytes, det_ws, 16,
+                                 vivim::scan_bwd_det_call_workspace_bytes(*p));
+        case Launch::unsupported: return fail(VIVIM_ERR_UNSUPPORTED, "selective_scan_bwd_det not implemented for input type %d", p->f.itype);
     }
     return after_launch("selective_scan_bwd_det");
 }
@@ -260,16 +219,12 @@ static int check_conv(const vivim_conv_fwd_params* p) {
     return VIVIM_OK;
 }
 
-// causal_conv1d.cpp:151: is_channel_last = x.stride(1) == 1 && x.stride(2) > 1
-static bool conv_channel_last(const vivim_conv_fwd_params* p) { return p->x_c_stride == 1 && p->x_l_stride > 1; }
-
 int vivim_causal_conv1d_fwd(const vivim_conv_fwd_params* p, void* stream) {
     if (int rc = check_conv(p)) return rc;
     VCHECK(p->out != nullptr);
-    const bool cl = conv_channel_last(p);
+    const bool cl = conv_channel_last(*p);
     if (cl) { VCHECK(p->out_c_stride == 1); } else { VCHECK(p->out_l_stride == 1); }
-    if (!(cl ? vivim::conv_cl_fwd_dispatch(*p, as_stream(stream))
-             : vivim::conv_fwd_dispatch(*p, as_stream(stream))))
+    if (!vivim::conv_fwd_dispatch(*p, as_stream(stream)))
         return fail(VIVIM_ERR_UNSUPPORTED, "causal_conv1d_fwd not implemented for input type %d / weight type %d",
                     p->itype, p->wtype);
     return after_launch("causal_conv1d_fwd");
@@ -279,7 +234,7 @@ static int check_conv_bwd(const vivim_conv_bwd_params* p) {
     VCHECK(p != nullptr);
     if (int rc = check_conv(&p->f)) return rc;
     VCHECK(p->dout && p->dx && p->dweight);
-    const bool cl = conv_channel_last(&p->f);
+    const bool cl = conv_channel_last(p->f);
     if (cl) { VCHECK(p->dout_c_stride == 1 && p->dx_c_stride == 1); }      // causal_conv1d.cpp:221, 237
     else    { VCHECK(p->dout_l_stride == 1 && p->dx_l_stride == 1); }      // causal_conv1d.cpp:220, 236
     VCHECK((p->f.bias == nullptr) == (p->dbias == nullptr));
@@ -287,36 +242,26 @@ static int check_conv_bwd(const vivim_conv_bwd_params* p) {
 }
 
 size_t vivim_causal_conv1d_bwd_det_workspace_bytes(const vivim_conv_fwd_params* f) {
-    if (check_conv(f) != VIVIM_OK) return 0;
-    const size_t slots = conv_channel_last(f) ? vivim::conv_cl_bwd_det_slots(*f) : vivim::conv_bwd_det_slots(*f);
-    return sizeof(float) * slots * (size_t)f->dim * (f->width + 1);
+    return check_conv(f) == VIVIM_OK ? vivim::conv_bwd_det_workspace_bytes(*f) : 0;
 }
 
 int vivim_causal_conv1d_bwd_det(const vivim_conv_bwd_params* p, void* det_ws, size_t det_ws_bytes, void* stream) {
     if (int rc = check_conv_bwd(p)) return rc;
-    const size_t need = vivim_causal_conv1d_bwd_det_workspace_bytes(&p->f);
-    if (det_ws == nullptr || det_ws_bytes < need || !aligned16(det_ws))
-        return bad_workspace("causal_conv1d_bwd_det", "vivim_causal_conv1d_bwd_det_workspace_bytes", det_ws_bytes, det_ws, 16, need);
-    const bool cl = conv_channel_last(&p->f);
-    const hipStream_t s = as_stream(stream);
-    vivim_conv_bwd_params d = *p;
-    d.dweight = det_ws;
-    d.dbias = nullptr;
-    if (!(cl ? vivim::conv_cl_bwd_det_launch(d, s) : vivim::conv_bwd_det_launch(d, s)))
-        return fail(VIVIM_ERR_UNSUPPORTED, "causal_conv1d_bwd_det not implemented for input type %d / weight type %d",
-                    p->f.itype, p->f.wtype);
-    const int slots = (int)(cl ? vivim::conv_cl_bwd_det_slots(p->f) : vivim::conv_bwd_det_slots(p->f));
-    const int64_t D = p->f.dim, W = p->f.width, sstride = D * (W + 1);
-    const float* ws = static_cast<const float*>(det_ws);
-    vivim::det_reduce(ws, slots, vivim::det_out(static_cast<float*>(p->dweight), {D, W}, {p->dweight_c_stride, p->dweight_width_stride}), s, sstride);
-    if (p->dbias) vivim::det_reduce(ws + D * W, slots, vivim::det_out(static_cast<float*>(p->dbias), {D}, {1}), s, sstride);
+    switch (vivim::conv_bwd_det_dispatch(*p, det_ws, det_ws_bytes, as_stream(stream))) {
+        case Launch::ok: break;
+        case Launch::bad_workspace:
+            return bad_workspace("causal_conv1d_bwd_det", "vivim_causal_conv1d_bwd_det_workspace_bytes", det_ws_bytes, det_ws, 16,
+                                 vivim::conv_bwd_det_workspace_bytes(p->f));
+        case Launch::unsupported:
+            return fail(VIVIM_ERR_UNSUPPORTED, "causal_conv1d_bwd_det not implemented for input type %d / weight type %d",
+                        p->f.itype, p->f.wtype);
+    }
     return after_launch("causal_conv1d_bwd_det");
 }
 
 int vivim_causal_conv1d_bwd(const vivim_conv_bwd_params* p, void* stream) {
     if (int rc = check_conv_bwd(p)) return rc;
-    if (!(conv_channel_last(&p->f) ? vivim::conv_cl_bwd_dispatch(*p, as_stream(stream))
-             : vivim::conv_bwd_dispatch(*p, as_stream(stream))))
+    if (!vivim::conv_bwd_dispatch(*p, as_stream(stream)))
         return fail(VIVIM_ERR_UNSUPPORTED, "causal_conv1d_bwd not implemented for input type %d / weight type %d",
                     p->f.itype, p->f.wtype);
     return after_launch("causal_conv1d_bwd");
@@ -334,7 +279,7 @@ int vivim_dwconv_fwd(const vivim_dwconv_params* p, void* stream) {
     VCHECK(p != nullptr);
     if (int rc = check_dw_dims(p->batch, p->depth, p->height, p->width, p->channels, p->kd, p->itype)) return rc;
     VCHECK(p->x && p->wt && p->y);
-    const int64_t cv = p->itype == VIVIM_F32 ? 4 : 8;
+    const int64_t cv = vec_elems(p->itype);
     VCHECK(p->channels % cv == 0 && p->x_token_stride % cv == 0 && p->x_batch_stride % cv == 0 &&
            p->y_token_stride % cv == 0 && p->y_batch_stride % cv == 0);
     VCHECK(aligned16(p->x) && aligned16(p->y));
@@ -366,10 +311,11 @@ size_t vivim_dwconv_wgrad_det_workspace_bytes(const vivim_dwconv_wgrad_params* p
 int vivim_dwconv_wgrad_det(const vivim_dwconv_wgrad_params* p, void* det_ws, size_t det_ws_bytes, void* stream) {
     if (int rc = check_dw_wgrad(p)) return rc;
     switch (vivim::dwconv_wgrad_det_dispatch(*p, det_ws, det_ws_bytes, as_stream(stream))) {
-        case 0: break;
-        case 2: return bad_workspace("dwconv_wgrad_det", "vivim_dwconv_wgrad_det_workspace_bytes", det_ws_bytes, det_ws, 16,
-                                     vivim::dwconv_wgrad_det_workspace_bytes(*p));
-        default: return fail(VIVIM_ERR_UNSUPPORTED, "dwconv_wgrad_det not implemented for input type %d", p->itype);
+        case Launch::ok: break;
+        case Launch::bad_workspace:
+            return bad_workspace("dwconv_wgrad_det", "vivim_dwconv_wgrad_det_workspace_bytes", det_ws_bytes, det_ws, 16,
+                                 vivim::dwconv_wgrad_det_workspace_bytes(*p));
+        case Launch::unsupported: return fail(VIVIM_ERR_UNSUPPORTED, "dwconv_wgrad_det not implemented for input type %d", p->itype);
     }
     return after_launch("dwconv_wgrad_det");
 }
@@ -388,7 +334,7 @@ static int check_dir(const vivim_dir_params* p) {
     VCHECK(p->batch <= 65535 && p->channels <= 65535);
     VCHECK(p->seqlen % p->nframes == 0 && p->channels % p->csplit == 0);
     VCHECK(p->src && p->dst);
-    const int64_t e = p->itype == VIVIM_F32 ? 4 : 8;            // 16-byte vectors on both sides
+    const int64_t e = vec_elems(p->itype);                      // 16-byte vectors on both sides
     VCHECK(p->seqlen % e == 0);
     VCHECK(aligned16(p->src) && aligned16(p->dst));
     VCHECK(p->flat_batch_stride % e == 0 && p->flat_c_stride % e == 0 && p->stk_batch_stride % e == 0 &&
@@ -434,7 +380,7 @@ static int check_layernorm(const vivim_layernorm_params* p) {
     VCHECK(p->batch > 0 && p->seqlen > 0 && p->channels > 0 && p->batch <= 65535);
     if (p->channels > 512)
         return fail(VIVIM_ERR_UNSUPPORTED, "layernorm_cm: more than 512 channels do not fit the backward's two LDS tiles");
-    const int64_t e = p->itype == VIVIM_F32 ? 4 : 8;             // 16-byte vectors along the tokens of x / dx
+    const int64_t e = vec_elems(p->itype);                       // 16-byte vectors along the tokens of x / dx
     VCHECK(p->seqlen % e == 0 && p->x_batch_stride % e == 0 && p->x_c_stride % e == 0);
     VCHECK(p->x && aligned16(p->x) && p->mean && p->rstd);
     return VIVIM_OK;
@@ -455,7 +401,7 @@ size_t vivim_layernorm_bwd_workspace_bytes(const vivim_layernorm_params* p) {
 int vivim_layernorm_cm_bwd(const vivim_layernorm_params* p, void* stream) {
     if (int rc = check_layernorm(p)) return rc;
     VCHECK(p->dy && p->dx && aligned16(p->dx));
-    const int64_t e = p->itype == VIVIM_F32 ? 4 : 8;
+    const int64_t e = vec_elems(p->itype);
     VCHECK(p->dx_batch_stride % e == 0 && p->dx_c_stride % e == 0);
     if ((p->dweight || p->dbias) && !p->workspace)
         return fail(VIVIM_ERR_INVALID, "layernorm_cm_bwd: dweight / dbias need the workspace (vivim_layernorm_bwd_workspace_bytes)");
@@ -491,7 +437,7 @@ static int check_add_layernorm(const vivim_add_layernorm_params* p, int64_t* e) 
                     p->btype, p->itype);
     if (p->weight && p->otype != VIVIM_F32 && p->otype != p->itype)
         return fail(VIVIM_ERR_UNSUPPORTED, "add_layernorm_cm: output type %d with x type %d is not built (f32 or x's type)", p->otype, p->itype);
-    *e = p->itype == VIVIM_F32 ? 4 : 8;
+    *e = vec_elems(p->itype);
     VCHECK(p->seqlen % *e == 0);
     return VIVIM_OK;
 }
@@ -548,8 +494,7 @@ int vivim_seg_loss_fwd(const vivim_seg_loss_params* p, void* stream) {
     VCHECK(p->loss && aligned(p->loss, 4));
     VCHECK(aligned(p->coef, 4));                                    // NULL: not wanted
     const size_t need = vivim::seg_loss_workspace_bytes(*p);
-    if (p->workspace == nullptr || !aligned(p->workspace, 4) || p->workspace_bytes < 0 || (size_t)p->workspace_bytes < need)
-        return bad_workspace("seg_loss_fwd", "vivim_seg_loss_workspace_bytes", p->workspace_bytes, p->workspace, 4, need);
+    if (int rc = check_workspace("seg_loss_fwd", "vivim_seg_loss_workspace_bytes", p->workspace, p->workspace_bytes, 4, need)) return rc;
     if (!vivim::seg_loss_dispatch(*p, false, as_stream(stream)))
         return fail(VIVIM_ERR_UNSUPPORTED, "seg_loss_fwd not implemented for input type %d / %d classes", p->itype, p->classes);
     return after_launch("seg_loss_fwd");
@@ -557,7 +502,7 @@ int vivim_seg_loss_fwd(const vivim_seg_loss_params* p, void* stream) {
 
 int vivim_seg_loss_bwd(const vivim_seg_loss_params* p, void* stream) {
     if (int rc = check_seg_loss(p)) return rc;
-    const uintptr_t ib = p->itype == VIVIM_F32 ? 4 : 2;
+    const uintptr_t ib = elem_bytes(p->itype);
     VCHECK(p->coef && aligned(p->coef, 4));
     VCHECK(p->grad_out && aligned(p->grad_out, 4));
     VCHECK(p->dlogits && aligned(p->dlogits, ib));
@@ -575,8 +520,7 @@ int vivim_seg_metrics(const vivim_seg_metrics_params* p, void* stream) {
     VCHECK(p->counts && aligned(p->counts, 4));
     VCHECK(aligned(p->state, 8));         // NULL: not wanted (pred: any address)
     const size_t need = vivim::seg_metrics_workspace_bytes(*p);
-    if (p->workspace == nullptr || !aligned(p->workspace, 4) || p->workspace_bytes < 0 || (size_t)p->workspace_bytes < need)
-        return bad_workspace("seg_metrics", "vivim_seg_metrics_workspace_bytes", p->workspace_bytes, p->workspace, 4, need);
+    if (int rc = check_workspace("seg_metrics", "vivim_seg_metrics_workspace_bytes", p->workspace, p->workspace_bytes, 4, need)) return rc;
     if (!vivim::seg_metrics_dispatch(*p, as_stream(stream)))
         return fail(VIVIM_ERR_UNSUPPORTED, "seg_metrics not implemented for input type %d / %d classes", p->itype, p->classes);
     return after_launch("seg_metrics");
@@ -590,7 +534,7 @@ static int check_upsample(const vivim_upsample_params* p, bool bwd) {
     if (p->out_h < p->in_h || p->out_w < p->in_w)
         return fail(VIVIM_ERR_UNSUPPORTED, "upsample_bilinear2d: (%d, %d) -> (%d, %d): upsampling only", p->in_h, p->in_w, p->out_h,
                     p->out_w);
-    const uintptr_t ib = p->itype == VIVIM_F32 ? 4 : 2;
+    const uintptr_t ib = elem_bytes(p->itype);
     const void* src = bwd ? p->dy : p->x;
     const void* dst = bwd ? p->dx : p->y;
     VCHECK(src != nullptr && aligned(src, ib));
@@ -620,9 +564,7 @@ int vivim_upsample_bilinear2d_bwd(const vivim_upsample_params* p, void* stream) 
 // every refusal of the fused decode head, before any launch
 static int check_decode_head(const vivim_decode_head_params* p) {
     VCHECK(p != nullptr);
-    if (p->struct_bytes != (int32_t)sizeof(vivim_decode_head_params))
-        return fail(VIVIM_ERR_INVALID, "decode_head_fwd: struct_bytes = %d, this library's vivim_decode_head_params has %zu", p->struct_bytes,
-                    sizeof(vivim_decode_head_params));
+    if (int rc = check_struct_bytes("decode_head_fwd", "vivim_decode_head_params", p->struct_bytes, sizeof(*p))) return rc;
     VCHECK(dtype_ok(p->itype));
     VCHECK(p->batch > 0 && p->hidden > 0 && p->classes > 0 && p->out_h > 0 && p->out_w > 0);
     VCHECK(p->n_maps >= 1 && p->n_maps <= 4);
@@ -630,7 +572,7 @@ static int check_decode_head(const vivim_decode_head_params* p) {
     if (p->hidden > vivim::decode_head_max_hidden())
         return fail(VIVIM_ERR_INVALID, "decode_head_fwd: hidden = %d: bias and w_out are kept in LDS, which holds up to %d channels",
                     p->hidden, vivim::decode_head_max_hidden());
-    const uintptr_t ib = p->itype == VIVIM_F32 ? 4 : 2;
+    const uintptr_t ib = elem_bytes(p->itype);
     // the kernel indexes inside an image, and builds its grid, with 32-bit integers
     VCHECK((int64_t)p->classes * p->out_h * p->out_w <= INT32_MAX);
     for (int s = 0; s < p->n_maps; ++s) {
@@ -661,9 +603,7 @@ int vivim_decode_head_fwd(const vivim_decode_head_params* p, void* stream) {
 // every refusal the forward and the backward of the token-major LayerNorm share, before any launch
 static int check_token_layernorm(const vivim_token_layernorm_params* p, const char* fn) {
     VCHECK(p != nullptr);
-    if (p->struct_bytes != (int32_t)sizeof(vivim_token_layernorm_params))
-        return fail(VIVIM_ERR_INVALID, "%s: struct_bytes = %d, this library's vivim_token_layernorm_params has %zu", fn, p->struct_bytes,
-                    sizeof(vivim_token_layernorm_params));
+    if (int rc = check_struct_bytes(fn, "vivim_token_layernorm_params", p->struct_bytes, sizeof(*p))) return rc;
     VCHECK(dtype_ok(p->itype) && dtype_ok(p->otype));
     VCHECK(p->rows > 0);
     if (p->channels < 1)
@@ -710,9 +650,7 @@ int vivim_token_layernorm_bwd(const vivim_token_layernorm_params* p, void* strea
                     (long long)p->dy_row_stride, (long long)p->dx_row_stride, p->channels);
     if ((p->dweight || p->dbias) && !p->workspace)
         return fail(VIVIM_ERR_INVALID, "token_layernorm_bwd: dweight / dbias need the workspace (vivim_token_layernorm_bwd_workspace_bytes)");
-    vivim_token_layernorm_params q = *p;
-    if (!q.dweight && !q.dbias) q.workspace = nullptr;               // nothing to sum: the kernel stores no slot
-    if (!vivim::token_layernorm_dispatch(q, true, as_stream(stream)))
+    if (!vivim::token_layernorm_dispatch(*p, true, as_stream(stream)))
         return fail(VIVIM_ERR_UNSUPPORTED, "token_layernorm_bwd not implemented for input type %d / output type %d", p->itype, p->otype);
     return after_launch("token_layernorm_bwd");
 }
@@ -720,9 +658,7 @@ int vivim_token_layernorm_bwd(const vivim_token_layernorm_params* p, void* strea
 // every refusal the forward and the backward of the token-major residual add + norm share, before any launch
 static int check_token_add_norm(const vivim_token_add_norm_params* p, const char* fn) {
     VCHECK(p != nullptr);
-    if (p->struct_bytes != (int32_t)sizeof(vivim_token_add_norm_params))
-        return fail(VIVIM_ERR_INVALID, "%s: struct_bytes = %d, this library's vivim_token_add_norm_params has %zu", fn, p->struct_bytes,
-                    sizeof(vivim_token_add_norm_params));
+    if (int rc = check_struct_bytes(fn, "vivim_token_add_norm_params", p->struct_bytes, sizeof(*p))) return rc;
     if (!dtype_ok(p->btype) || !dtype_ok(p->rtype) || !dtype_ok(p->otype))
         return fail(VIVIM_ERR_INVALID, "%s: btype = %d, rtype = %d, otype = %d: a type tag is 0 (f32), 1 (f16) or 2 (bf16)", fn, p->btype,
                     p->rtype, p->otype);
@@ -746,7 +682,7 @@ static int check_token_add_norm(const vivim_token_add_norm_params* p, const char
 static int check_tan_tensor(const char* fn, const char* name, const void* q, bool required, int type, int64_t stride, int channels) {
     if (q == nullptr)
         return required ? fail(VIVIM_ERR_INVALID, "%s: %s is NULL", fn, name) : VIVIM_OK;
-    if (!aligned(q, type == VIVIM_F32 ? 4 : 2))
+    if (!aligned(q, elem_bytes(type)))
         return fail(VIVIM_ERR_INVALID, "%s: %s = %p is not aligned to its element type", fn, name, q);
     if (stride < channels)
         return fail(VIVIM_ERR_INVALID, "%s: %s_row_stride = %lld is less than the %d channels of a row", fn, name, (long long)stride, channels);
@@ -809,9 +745,7 @@ int vivim_token_add_norm_bwd(const vivim_token_add_norm_params* p, void* stream)
     if (int rc = check_tan_tensor(fn, "dres_in", p->dres_in, false, p->rtype, p->dres_in_row_stride, C)) return rc;
     if (int rc = check_tan_tensor(fn, "dbranch", p->dbranch, false, p->btype, p->dbranch_row_stride, C)) return rc;
     if (int rc = check_tan_f32(fn, "scale", p->scale, false)) return rc;
-    vivim_token_add_norm_params q = *p;
-    if (!q.dweight && !q.dbias) q.workspace = nullptr;               // nothing to sum: the kernel stores no slot
-    if (!vivim::token_add_norm_dispatch(q, true, as_stream(stream)))
+    if (!vivim::token_add_norm_dispatch(*p, true, as_stream(stream)))
         return fail(VIVIM_ERR_UNSUPPORTED, "%s not implemented for branch type %d / residual type %d", fn, p->btype, p->rtype);
     return after_launch(fn);
 }
@@ -819,9 +753,7 @@ int vivim_token_add_norm_bwd(const vivim_token_add_norm_params* p, void* stream)
 // ---- fused clip + AdamW step (optimizer.hip)
 static int check_opt_common(const vivim_opt_step_params* p, const char* fn) {
     VCHECK(p != nullptr);
-    if (p->struct_bytes != (int32_t)sizeof(vivim_opt_step_params))
-        return fail(VIVIM_ERR_INVALID, "%s: struct_bytes = %d, this library's vivim_opt_step_params has %zu", fn, p->struct_bytes,
-                    sizeof(vivim_opt_step_params));
+    if (int rc = check_struct_bytes(fn, "vivim_opt_step_params", p->struct_bytes, sizeof(*p))) return rc;
     VCHECK(p->state != nullptr && aligned(p->state, 4));
     if (p->total_blocks < 0) return fail(VIVIM_ERR_INVALID, "%s: total_blocks = %d", fn, p->total_blocks);
     return VIVIM_OK;
@@ -849,6 +781,15 @@ static int check_opt_workspace(const vivim_opt_step_params* p, const char* fn) {
     return VIVIM_OK;
 }
 
+// the hyper-parameters of a step: the betas, and for the `update` itself lr, eps and weight_decay
+static int check_opt_hyper(const vivim_opt_step_params* p, const char* fn, bool update) {
+    if (!(p->beta1 >= 0.0 && p->beta1 < 1.0 && p->beta2 >= 0.0 && p->beta2 < 1.0))
+        return fail(VIVIM_ERR_INVALID, "%s: betas = (%g, %g), each must be in [0, 1)", fn, p->beta1, p->beta2);
+    if (update && !(p->lr >= 0.0 && p->eps >= 0.0 && p->weight_decay >= 0.0))
+        return fail(VIVIM_ERR_INVALID, "%s: lr = %g, eps = %g, weight_decay = %g: none may be negative", fn, p->lr, p->eps, p->weight_decay);
+    return VIVIM_OK;
+}
+
 size_t vivim_opt_step_workspace_bytes(const vivim_opt_step_params* p) {
     return p && p->struct_bytes == (int32_t)sizeof(vivim_opt_step_params) && p->total_blocks > 0 ? 8 * (size_t)p->total_blocks : 0;
 }
@@ -865,8 +806,7 @@ int vivim_opt_grad_stats(const vivim_opt_step_params* p, void* stream) {
 int vivim_opt_finalise(const vivim_opt_step_params* p, void* stream) {
     const char* fn = "opt_finalise";
     if (int rc = check_opt_common(p, fn)) return rc;
-    if (!(p->beta1 >= 0.0 && p->beta1 < 1.0 && p->beta2 >= 0.0 && p->beta2 < 1.0))
-        return fail(VIVIM_ERR_INVALID, "%s: betas = (%g, %g), each must be in [0, 1)", fn, p->beta1, p->beta2);
+    if (int rc = check_opt_hyper(p, fn, false)) return rc;
     if (p->has_max_norm && !(p->max_norm >= 0.0)) return fail(VIVIM_ERR_INVALID, "%s: max_norm = %g", fn, p->max_norm);
     if (int rc = check_opt_workspace(p, fn)) return rc;
     vivim::opt_finalise_launch(*p, as_stream(stream));
@@ -879,10 +819,7 @@ int vivim_opt_adamw(const vivim_opt_step_params* p, void* stream) {
     VCHECK(p->params != nullptr && p->exp_avg != nullptr && p->exp_avg_sq != nullptr);
     VCHECK(aligned(p->params, 8) && aligned(p->exp_avg, 8) && aligned(p->exp_avg_sq, 8));
     if (int rc = check_opt_tensors(p, fn)) return rc;
-    if (!(p->beta1 >= 0.0 && p->beta1 < 1.0 && p->beta2 >= 0.0 && p->beta2 < 1.0))
-        return fail(VIVIM_ERR_INVALID, "%s: betas = (%g, %g), each must be in [0, 1)", fn, p->beta1, p->beta2);
-    if (!(p->lr >= 0.0 && p->eps >= 0.0 && p->weight_decay >= 0.0))
-        return fail(VIVIM_ERR_INVALID, "%s: lr = %g, eps = %g, weight_decay = %g: none may be negative", fn, p->lr, p->eps, p->weight_decay);
+    if (int rc = check_opt_hyper(p, fn, true)) return rc;
     vivim::opt_adamw_launch(*p, as_stream(stream));
     return after_launch(fn);
 }
@@ -890,9 +827,7 @@ int vivim_opt_adamw(const vivim_opt_step_params* p, void* stream) {
 // ---- the same step for 16-bit parameters with fp32 masters: vivim_opt_mw_params is vivim_opt_step_params + masters + dtype
 static int check_opt_mw(const vivim_opt_mw_params* p, const char* fn, vivim_opt_step_params& q) {
     VCHECK(p != nullptr);
-    if (p->struct_bytes != (int32_t)sizeof(vivim_opt_mw_params))
-        return fail(VIVIM_ERR_INVALID, "%s: struct_bytes = %d, this library's vivim_opt_mw_params has %zu", fn, p->struct_bytes,
-                    sizeof(vivim_opt_mw_params));
+    if (int rc = check_struct_bytes(fn, "vivim_opt_mw_params", p->struct_bytes, sizeof(*p))) return rc;
     static_assert(offsetof(vivim_opt_mw_params, masters) == sizeof(vivim_opt_step_params), "the common fields come first");
     memcpy(&q, p, sizeof(q));
     q.struct_bytes = (int32_t)sizeof(q);
@@ -919,10 +854,7 @@ int vivim_opt_adamw_mw(const vivim_opt_mw_params* p, void* stream) {
     VCHECK(q.params != nullptr && q.exp_avg != nullptr && q.exp_avg_sq != nullptr && p->masters != nullptr);
     VCHECK(aligned(q.params, 8) && aligned(q.exp_avg, 8) && aligned(q.exp_avg_sq, 8) && aligned(p->masters, 8));
     if (int rc = check_opt_tensors(&q, fn, 2)) return rc;
-    if (!(q.beta1 >= 0.0 && q.beta1 < 1.0 && q.beta2 >= 0.0 && q.beta2 < 1.0))
-        return fail(VIVIM_ERR_INVALID, "%s: betas = (%g, %g), each must be in [0, 1)", fn, q.beta1, q.beta2);
-    if (!(q.lr >= 0.0 && q.eps >= 0.0 && q.weight_decay >= 0.0))
-        return fail(VIVIM_ERR_INVALID, "%s: lr = %g, eps = %g, weight_decay = %g: none may be negative", fn, q.lr, q.eps, q.weight_decay);
+    if (int rc = check_opt_hyper(&q, fn, true)) return rc;
     vivim::opt_adamw_mw_launch(q, p->masters, p->dtype, as_stream(stream));
     return after_launch(fn);
 }
@@ -936,9 +868,7 @@ static bool structure_loss_sizes_ok(const vivim_structure_loss_params* p) {
 // every refusal the forward and the backward of the structure loss share, before any launch
 static int check_structure_loss(const vivim_structure_loss_params* p, const char* fn) {
     if (p == nullptr) return fail(VIVIM_ERR_INVALID, "%s: params is NULL", fn);
-    if (p->struct_bytes != (int32_t)sizeof(vivim_structure_loss_params))
-        return fail(VIVIM_ERR_INVALID, "%s: struct_bytes = %d, this library's vivim_structure_loss_params has %zu", fn, p->struct_bytes,
-                    sizeof(vivim_structure_loss_params));
+    if (int rc = check_struct_bytes(fn, "vivim_structure_loss_params", p->struct_bytes, sizeof(*p))) return rc;
     if (!dtype_ok(p->itype) || (p->ttype != 0 && p->ttype != 1))
         return fail(VIVIM_ERR_INVALID, "%s: itype = %d, ttype = %d: logits are fp32 / fp16 / bf16 (0 / 1 / 2), targets int64 / uint8 (0 / 1)",
                     fn, p->itype, p->ttype);
@@ -953,7 +883,7 @@ static int check_structure_loss(const vivim_structure_loss_params* p, const char
     if ((int64_t)p->height * p->width > INT32_MAX - 4096 || (int64_t)p->batch * vivim::structure_loss_tiles(*p) > INT32_MAX)
         return fail(VIVIM_ERR_INVALID, "%s: batch = %d, height = %d, width = %d: the index range overflows int32", fn, p->batch, p->height,
                     p->width);
-    const uintptr_t ib = p->itype == VIVIM_F32 ? 4 : 2;
+    const uintptr_t ib = elem_bytes(p->itype);
     if (p->logits == nullptr || !aligned(p->logits, ib))
         return fail(VIVIM_ERR_INVALID, "%s: logits at %p: need a %d-byte aligned pointer", fn, p->logits, (int)ib);
     if (p->target == nullptr || !aligned(p->target, p->ttype == 0 ? 8 : 1))
@@ -975,8 +905,7 @@ int vivim_structure_loss_fwd(const vivim_structure_loss_params* p, void* stream)
     if (!aligned(p->coef, 4))                                          // NULL: not wanted
         return fail(VIVIM_ERR_INVALID, "%s: coef at %p: need a 4-byte aligned pointer (or NULL)", fn, p->coef);
     const size_t need = vivim::structure_loss_workspace_bytes(*p);
-    if (p->workspace == nullptr || !aligned(p->workspace, 8) || p->workspace_bytes < 0 || (size_t)p->workspace_bytes < need)
-        return bad_workspace(fn, "vivim_structure_loss_workspace_bytes", p->workspace_bytes, p->workspace, 8, need);
+    if (int rc = check_workspace(fn, "vivim_structure_loss_workspace_bytes", p->workspace, p->workspace_bytes, 8, need)) return rc;
     if (!vivim::structure_loss_dispatch(*p, false, as_stream(stream)))
         return fail(VIVIM_ERR_UNSUPPORTED, "%s not implemented for input type %d", fn, p->itype);
     return after_launch(fn);
@@ -985,7 +914,7 @@ int vivim_structure_loss_fwd(const vivim_structure_loss_params* p, void* stream)
 int vivim_structure_loss_bwd(const vivim_structure_loss_params* p, void* stream) {
     const char* fn = "structure_loss_bwd";
     if (int rc = check_structure_loss(p, fn)) return rc;
-    const uintptr_t ib = p->itype == VIVIM_F32 ? 4 : 2;
+    const uintptr_t ib = elem_bytes(p->itype);
     if (p->coef == nullptr || !aligned(p->coef, 4)) return fail(VIVIM_ERR_INVALID, "%s: coef at %p: need a 4-byte aligned pointer", fn, p->coef);
     if (p->grad_out == nullptr || !aligned(p->grad_out, 4))
         return fail(VIVIM_ERR_INVALID, "%s: grad_out at %p: need a 4-byte aligned pointer", fn, p->grad_out);

@@ -22,6 +22,18 @@ using bf16_t = __bf16;
 typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
 typedef uint32_t u32x2 __attribute__((ext_vector_type(2)));
 
+// Host side: calls fn(T{}) with the element type that the tag `itype` names; false, and no call, for a tag that names none.
+template <typename F> inline bool with_itype(int itype, F&& fn) {
+    switch (itype) {
+        case VIVIM_F32: fn(float{}); return true;
+        case VIVIM_F16: fn(f16_t{}); return true;
+        case VIVIM_BF16: fn(bf16_t{}); return true;
+    }
+    return false;
+}
+inline int elem_bytes(int itype) { return itype == VIVIM_F32 ? 4 : 2; }   // of one element
+inline int vec_elems(int itype) { return itype == VIVIM_F32 ? 4 : 8; }    // elements per 16-byte vector
+
 // ---- fast transcendental forms (one hardware op each, as the reference's --use_fast_math build) ----
 __device__ __forceinline__ float fast_exp2(float x) { return __builtin_amdgcn_exp2f(x); }
 __device__ __forceinline__ float fast_exp(float x) { return __builtin_amdgcn_exp2f(x * kLog2e); }

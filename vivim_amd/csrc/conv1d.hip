@@ -11,7 +11,7 @@
 //   * conv1d_{fwd,bwd}_kernel: everything else (ragged or unaligned rows, rows of one tile: stage 3's 320 tokens).  One
 //     tile per wave; halos move between neighbouring lanes with wave shuffles, the two lanes at the wave edges fetch
 //     theirs with guarded scalar loads.
-#include "det.cuh"
+#include "ops.cuh"
 
 namespace vivim {
 
@@ -458,15 +458,13 @@ static void launch_conv_bwd(const vivim_conv_bwd_params& p, hipStream_t stream) 
     hipLaunchKernelGGL((conv1d_bwd_kernel<T, WT, E, false>), grid, dim3(kConvThreads), 0, stream, p);
 }
 
-template <typename T>
-static bool dispatch_w_fwd(const vivim_conv_fwd_params& p, hipStream_t s) {
-    switch (p.wtype) {
-        case VIVIM_F32: launch_conv_fwd<T, float>(p, s); return true;
-        case VIVIM_F16: launch_conv_fwd<T, f16_t>(p, s); return true;
-        case VIVIM_BF16: launch_conv_fwd<T, bf16_t>(p, s); return true;
-    }
-    return false;
+// Calls fn(T{}, WT{}) with the element types of x and of the weights: all nine pairs are built.
+template <typename F> static bool with_conv_types(const vivim_conv_fwd_params& f, F&& fn) {
+    bool ok = false;
+    with_itype(f.itype, [&](auto t) { ok = with_itype(f.wtype, [&](auto w) { fn(t, w); }); });
+    return ok;
 }
+
 // Deterministic: the one-tile-per-workgroup kernel for every shape, (batch, tile) slots.
 static dim3 conv_det_grid(const vivim_conv_fwd_params& f, int esize) {
     const int E = 16 / esize;
@@ -477,53 +475,40 @@ static void launch_conv_bwd_det(const vivim_conv_bwd_params& p, hipStream_t stre
     constexpr int E = 16 / sizeof(T);
     hipLaunchKernelGGL((conv1d_bwd_kernel<T, WT, E, false, true>), conv_det_grid(p.f, sizeof(T)), dim3(kConvThreads), 0, stream, p);
 }
-size_t conv_bwd_det_slots(const vivim_conv_fwd_params& f) {
-    const dim3 g = conv_det_grid(f, f.itype == VIVIM_F32 ? 4 : 2);
+static size_t conv_bwd_det_slots(const vivim_conv_fwd_params& f) {
+    if (conv_channel_last(f)) return conv_cl_bwd_det_slots(f);
+    const dim3 g = conv_det_grid(f, elem_bytes(f.itype));
     return (size_t)g.x * g.z;
 }
-bool conv_bwd_det_launch(const vivim_conv_bwd_params& p, hipStream_t s) {
-    auto w = [&](auto t) {
-        typedef decltype(t) T;
-        switch (p.f.wtype) {
-            case VIVIM_F32: launch_conv_bwd_det<T, float>(p, s); return true;
-            case VIVIM_F16: launch_conv_bwd_det<T, f16_t>(p, s); return true;
-            case VIVIM_BF16: launch_conv_bwd_det<T, bf16_t>(p, s); return true;
-        }
-        return false;
-    };
-    switch (p.f.itype) {
-        case VIVIM_F32: return w(float{});
-        case VIVIM_F16: return w(f16_t{});
-        case VIVIM_BF16: return w(bf16_t{});
-    }
-    return false;
+// A slot holds dweight (dim, width), then dbias (dim).
+size_t conv_bwd_det_workspace_bytes(const vivim_conv_fwd_params& f) {
+    return sizeof(float) * conv_bwd_det_slots(f) * (size_t)f.dim * (f.width + 1);
 }
-
-template <typename T>
-static bool dispatch_w_bwd(const vivim_conv_bwd_params& p, hipStream_t s) {
-    switch (p.f.wtype) {
-        case VIVIM_F32: launch_conv_bwd<T, float>(p, s); return true;
-        case VIVIM_F16: launch_conv_bwd<T, f16_t>(p, s); return true;
-        case VIVIM_BF16: launch_conv_bwd<T, bf16_t>(p, s); return true;
-    }
-    return false;
+// The deterministic protocol (det.cuh): the slot workspace is refused before anything is launched.
+Launch conv_bwd_det_dispatch(const vivim_conv_bwd_params& p, void* ws, size_t bytes, hipStream_t s) {
+    const vivim_conv_fwd_params& f = p.f;
+    if (!det_ws_ok(ws, bytes, conv_bwd_det_workspace_bytes(f))) return Launch::bad_workspace;
+    vivim_conv_bwd_params d = p;
+    d.dweight = ws;
+    d.dbias = nullptr;
+    if (!(conv_channel_last(f) ? conv_cl_bwd_det_launch(d, s)
+                               : with_conv_types(f, [&](auto t, auto w) { launch_conv_bwd_det<decltype(t), decltype(w)>(d, s); })))
+        return Launch::unsupported;
+    const int slots = (int)conv_bwd_det_slots(f);
+    const int64_t D = f.dim, W = f.width, sstride = D * (W + 1);
+    const float* slot = static_cast<const float*>(ws);
+    det_reduce(slot, slots, det_out(static_cast<float*>(p.dweight), {D, W}, {p.dweight_c_stride, p.dweight_width_stride}), s, sstride);
+    if (p.dbias) det_reduce(slot + D * W, slots, det_out(static_cast<float*>(p.dbias), {D}, {1}), s, sstride);
+    return Launch::ok;
 }
 
 bool conv_fwd_dispatch(const vivim_conv_fwd_params& p, hipStream_t s) {
-    switch (p.itype) {
-        case VIVIM_F32: return dispatch_w_fwd<float>(p, s);
-        case VIVIM_F16: return dispatch_w_fwd<f16_t>(p, s);
-        case VIVIM_BF16: return dispatch_w_fwd<bf16_t>(p, s);
-    }
-    return false;
+    if (conv_channel_last(p)) return conv_cl_fwd_dispatch(p, s);
+    return with_conv_types(p, [&](auto t, auto w) { launch_conv_fwd<decltype(t), decltype(w)>(p, s); });
 }
 bool conv_bwd_dispatch(const vivim_conv_bwd_params& p, hipStream_t s) {
-    switch (p.f.itype) {
-        case VIVIM_F32: return dispatch_w_bwd<float>(p, s);
-        case VIVIM_F16: return dispatch_w_bwd<f16_t>(p, s);
-        case VIVIM_BF16: return dispatch_w_bwd<bf16_t>(p, s);
-    }
-    return false;
+    if (conv_channel_last(p.f)) return conv_cl_bwd_dispatch(p, s);
+    return with_conv_types(p.f, [&](auto t, auto w) { launch_conv_bwd<decltype(t), decltype(w)>(p, s); });
 }
 
 }  // namespace vivim

@@ -7,7 +7,7 @@
 // tokens, keeps the last three rows of its channels in registers as the sliding window and walks its chunk row by row.
 // Every row access of a wave is one contiguous run of 64 * E elements; there is no shared memory and no barrier.  The halo
 // costs three extra rows per chunk (forward) or six (backward).  Not on Vivim's path (its x has unit seqlen stride).
-#include "det.cuh"
+#include "ops.cuh"
 
 namespace vivim {
 
@@ -202,12 +202,7 @@ static unsigned cl_blocks(const vivim_conv_fwd_params& p, const ClGeom& g) {
 bool conv_cl_fwd_dispatch(const vivim_conv_fwd_params& p, hipStream_t s) {
     const ClGeom g = cl_geometry(p);
     const dim3 grid(cl_blocks(p, g)), block(kClThreads);
-    switch (p.itype) {
-        case VIVIM_F32:  hipLaunchKernelGGL((conv1d_cl_fwd_kernel<float, kClE>), grid, block, 0, s, p, g); return true;
-        case VIVIM_F16:  hipLaunchKernelGGL((conv1d_cl_fwd_kernel<f16_t, kClE>), grid, block, 0, s, p, g); return true;
-        case VIVIM_BF16: hipLaunchKernelGGL((conv1d_cl_fwd_kernel<bf16_t, kClE>), grid, block, 0, s, p, g); return true;
-    }
-    return false;
+    return with_itype(p.itype, [&](auto t) { hipLaunchKernelGGL((conv1d_cl_fwd_kernel<decltype(t), kClE>), grid, block, 0, s, p, g); });
 }
 
 size_t conv_cl_bwd_det_slots(const vivim_conv_fwd_params& f) {
@@ -217,23 +212,13 @@ size_t conv_cl_bwd_det_slots(const vivim_conv_fwd_params& f) {
 bool conv_cl_bwd_det_launch(const vivim_conv_bwd_params& p, hipStream_t s) {
     const ClGeom g = cl_geometry(p.f);
     const dim3 grid(cl_blocks(p.f, g)), block(kClThreads);
-    switch (p.f.itype) {
-        case VIVIM_F32:  hipLaunchKernelGGL((conv1d_cl_bwd_kernel<float, kClE, true>), grid, block, 0, s, p, g); return true;
-        case VIVIM_F16:  hipLaunchKernelGGL((conv1d_cl_bwd_kernel<f16_t, kClE, true>), grid, block, 0, s, p, g); return true;
-        case VIVIM_BF16: hipLaunchKernelGGL((conv1d_cl_bwd_kernel<bf16_t, kClE, true>), grid, block, 0, s, p, g); return true;
-    }
-    return false;
+    return with_itype(p.f.itype, [&](auto t) { hipLaunchKernelGGL((conv1d_cl_bwd_kernel<decltype(t), kClE, true>), grid, block, 0, s, p, g); });
 }
 
 bool conv_cl_bwd_dispatch(const vivim_conv_bwd_params& p, hipStream_t s) {
     const ClGeom g = cl_geometry(p.f);
     const dim3 grid(cl_blocks(p.f, g)), block(kClThreads);
-    switch (p.f.itype) {
-        case VIVIM_F32:  hipLaunchKernelGGL((conv1d_cl_bwd_kernel<float, kClE>), grid, block, 0, s, p, g); return true;
-        case VIVIM_F16:  hipLaunchKernelGGL((conv1d_cl_bwd_kernel<f16_t, kClE>), grid, block, 0, s, p, g); return true;
-        case VIVIM_BF16: hipLaunchKernelGGL((conv1d_cl_bwd_kernel<bf16_t, kClE>), grid, block, 0, s, p, g); return true;
-    }
-    return false;
+    return with_itype(p.f.itype, [&](auto t) { hipLaunchKernelGGL((conv1d_cl_bwd_kernel<decltype(t), kClE>), grid, block, 0, s, p, g); });
 }
 
 }  // namespace vivim

@@ -20,7 +20,7 @@
 // per chunk instead of one per map) costs 187 VGPRs, two waves per SIMD, and ran slower, 180 us: the kernel is not bound by
 // the latency of a round trip.  12 of a pixel's 13 taps come from L2 (64 x 12 rows per tile where the tile's footprint is 38);
 // staging that footprint in LDS is the open experiment.
-#include "common.cuh"
+#include "ops.cuh"
 #include "seg_load.cuh"
 #include "up_tap.cuh"
 
@@ -176,12 +176,7 @@ static void dh_launch(const vivim_decode_head_params& p, hipStream_t stream) {
 }
 
 bool decode_head_dispatch(const vivim_decode_head_params& p, hipStream_t stream) {
-    switch (p.itype) {
-        case VIVIM_F32: dh_launch<float>(p, stream); return true;
-        case VIVIM_F16: dh_launch<f16_t>(p, stream); return true;
-        case VIVIM_BF16: dh_launch<bf16_t>(p, stream); return true;
-    }
-    return false;
+    return with_itype(p.itype, [&](auto t) { dh_launch<decltype(t)>(p, stream); });
 }
 
 }  // namespace vivim

@@ -9,7 +9,7 @@
 // access), direction 2 (frame interleave, token t*hw+p <-> p*nf+t) is element-wise: consecutive flat tokens are
 // nf elements apart there, the lines are shared between neighbouring threads and served by L2.
 // Pure data movement: HBM-bound, algorithmic bytes 4 * batch * channels * seqlen * sizeof(T) either way.
-#include "common.cuh"
+#include "ops.cuh"
 
 namespace vivim {
 
@@ -140,24 +140,16 @@ __global__ void __launch_bounds__(256) dir_tile_kernel(const vivim_dir_params p)
 
 template <bool GATHER>
 bool dir_dispatch(const vivim_dir_params& p, hipStream_t stream) {
-    const int E = p.itype == VIVIM_F32 ? 4 : 8;
+    const int E = vec_elems(p.itype);
     const int hw = p.seqlen / p.nframes;
     if (hw % E == 0 && p.nframes <= kDirMaxFrames && p.nframes > 1) {
         const dim3 grid((hw + 64 * E - 1) / (64 * E), p.channels, p.batch), block(256);
-        switch (p.itype) {
-            case VIVIM_F32: hipLaunchKernelGGL((dir_tile_kernel<float, GATHER>), grid, block, 0, stream, p); return true;
-            case VIVIM_F16: hipLaunchKernelGGL((dir_tile_kernel<f16_t, GATHER>), grid, block, 0, stream, p); return true;
-            case VIVIM_BF16: hipLaunchKernelGGL((dir_tile_kernel<bf16_t, GATHER>), grid, block, 0, stream, p); return true;
-        }
-        return false;
+        return with_itype(p.itype, [&](auto t) {
+            hipLaunchKernelGGL((dir_tile_kernel<decltype(t), GATHER>), grid, block, 0, stream, p);
+        });
     }
     const dim3 grid((p.seqlen / E + 255) / 256, p.channels, p.batch), block(256);
-    switch (p.itype) {
-        case VIVIM_F32: hipLaunchKernelGGL((dir_kernel<float, GATHER>), grid, block, 0, stream, p); return true;
-        case VIVIM_F16: hipLaunchKernelGGL((dir_kernel<f16_t, GATHER>), grid, block, 0, stream, p); return true;
-        case VIVIM_BF16: hipLaunchKernelGGL((dir_kernel<bf16_t, GATHER>), grid, block, 0, stream, p); return true;
-    }
-    return false;
+    return with_itype(p.itype, [&](auto t) { hipLaunchKernelGGL((dir_kernel<decltype(t), GATHER>), grid, block, 0, stream, p); });
 }
 template bool dir_dispatch<false>(const vivim_dir_params&, hipStream_t);
 template bool dir_dispatch<true>(const vivim_dir_params&, hipStream_t);

@@ -11,7 +11,7 @@
 // TW = 4 consecutive w positions: every load is a 16-byte vector, 8 neighbouring lanes cover 128 contiguous
 // bytes of one token, each loaded input vector feeds up to 3 of the 4 outputs, taps live in LDS as fp32.
 // Memory-bound: 2*s bytes per element forward (the 27x neighbour re-reads are L1/L2 hits).
-#include "det.cuh"
+#include "ops.cuh"
 
 namespace vivim {
 
@@ -210,7 +210,7 @@ __global__ void __launch_bounds__(kDwThreads) dwconv_wgrad_kernel(const vivim_dw
 }
 
 template <typename T>
-static bool dw_fwd(const vivim_dwconv_params& p, hipStream_t s) {
+static void dw_fwd(const vivim_dwconv_params& p, hipStream_t s) {
     constexpr int CV = 16 / (int)sizeof(T);
     const int wtiles = (p.width + kDwTW - 1) / kDwTW;
     const int ntiles = p.depth * p.height * wtiles;
@@ -223,7 +223,7 @@ static bool dw_fwd(const vivim_dwconv_params& p, hipStream_t s) {
             if (p.act == 1) hipLaunchKernelGGL((dwconv_fwd_kernel<T, 1, false, 1>), grid, dim3(kDwThreads), 0, s, p);
             else            hipLaunchKernelGGL((dwconv_fwd_kernel<T, 1, false, 2>), grid, dim3(kDwThreads), 0, s, p);
         }
-        return true;
+        return;
     }
     if (p.kd == 3) {
         if (p.flip) hipLaunchKernelGGL((dwconv_fwd_kernel<T, 3, true>), grid, dim3(kDwThreads), 0, s, p);
@@ -232,7 +232,6 @@ static bool dw_fwd(const vivim_dwconv_params& p, hipStream_t s) {
         if (p.flip) hipLaunchKernelGGL((dwconv_fwd_kernel<T, 1, true>), grid, dim3(kDwThreads), 0, s, p);
         else        hipLaunchKernelGGL((dwconv_fwd_kernel<T, 1, false>), grid, dim3(kDwThreads), 0, s, p);
     }
-    return true;
 }
 // Grid of the weight-gradient kernel: (blocks_x, channel groups, batch) and tiles per wave.
 static dim3 dw_wgrad_grid(const vivim_dwconv_wgrad_params& p, int& tpw_out) {
@@ -248,12 +247,11 @@ static dim3 dw_wgrad_grid(const vivim_dwconv_wgrad_params& p, int& tpw_out) {
     return dim3(blocks_x, cgroups, p.batch);
 }
 template <typename T, bool DET>
-static bool dw_wgrad(const vivim_dwconv_wgrad_params& p, hipStream_t s) {
+static void dw_wgrad(const vivim_dwconv_wgrad_params& p, hipStream_t s) {
     int tpw = 0;
     const dim3 grid = dw_wgrad_grid(p, tpw);
     if (p.kd == 3) hipLaunchKernelGGL((dwconv_wgrad_kernel<T, 3, DET>), grid, dim3(kDwThreads), 0, s, p, tpw);
     else           hipLaunchKernelGGL((dwconv_wgrad_kernel<T, 1, DET>), grid, dim3(kDwThreads), 0, s, p, tpw);
-    return true;
 }
 
 // vivim_dwconv_wgrad_det: batch * blocks_x slots of (kd * 9 + 1) * channels floats.
@@ -262,18 +260,12 @@ size_t dwconv_wgrad_det_workspace_bytes(const vivim_dwconv_wgrad_params& p) {
     const dim3 g = dw_wgrad_grid(p, tpw);
     return sizeof(float) * (size_t)g.x * g.z * (size_t)(p.kd * 9 + 1) * p.channels;
 }
-// 0 launched, 1 type not built, 2 workspace missing / too small / misaligned (nothing launched).
-int dwconv_wgrad_det_dispatch(const vivim_dwconv_wgrad_params& p, void* ws, size_t bytes, hipStream_t s) {
-    if (ws == nullptr || bytes < dwconv_wgrad_det_workspace_bytes(p) || reinterpret_cast<uintptr_t>(ws) % 16 != 0) return 2;
+// The deterministic protocol (det.cuh): the slot workspace is refused before anything is launched.
+Launch dwconv_wgrad_det_dispatch(const vivim_dwconv_wgrad_params& p, void* ws, size_t bytes, hipStream_t s) {
+    if (!det_ws_ok(ws, bytes, dwconv_wgrad_det_workspace_bytes(p))) return Launch::bad_workspace;
     vivim_dwconv_wgrad_params d = p;
     d.dwt = ws;
-    bool ok = false;
-    switch (p.itype) {
-        case VIVIM_F32: ok = dw_wgrad<float, true>(d, s); break;
-        case VIVIM_F16: ok = dw_wgrad<f16_t, true>(d, s); break;
-        case VIVIM_BF16: ok = dw_wgrad<bf16_t, true>(d, s); break;
-    }
-    if (!ok) return 1;
+    if (!with_itype(p.itype, [&](auto t) { dw_wgrad<decltype(t), true>(d, s); })) return Launch::unsupported;
     int tpw = 0;
     const dim3 g = dw_wgrad_grid(p, tpw);
     const int taps = p.kd * 9, C = p.channels;
@@ -281,24 +273,14 @@ int dwconv_wgrad_det_dispatch(const vivim_dwconv_wgrad_params& p, void* ws, size
     det_reduce(static_cast<const float*>(ws), (int)(g.x * g.z), det_out(static_cast<float*>(p.dwt), {taps, C}, {C, 1}), s, sstride);
     if (p.dbias)
         det_reduce(static_cast<const float*>(ws) + (int64_t)taps * C, (int)(g.x * g.z), det_out(static_cast<float*>(p.dbias), {C}, {1}), s, sstride);
-    return 0;
+    return Launch::ok;
 }
 
 bool dwconv_fwd_dispatch(const vivim_dwconv_params& p, hipStream_t s) {
-    switch (p.itype) {
-        case VIVIM_F32: return dw_fwd<float>(p, s);
-        case VIVIM_F16: return dw_fwd<f16_t>(p, s);
-        case VIVIM_BF16: return dw_fwd<bf16_t>(p, s);
-    }
-    return false;
+    return with_itype(p.itype, [&](auto t) { dw_fwd<decltype(t)>(p, s); });
 }
 bool dwconv_wgrad_dispatch(const vivim_dwconv_wgrad_params& p, hipStream_t s) {
-    switch (p.itype) {
-        case VIVIM_F32: return dw_wgrad<float, false>(p, s);
-        case VIVIM_F16: return dw_wgrad<f16_t, false>(p, s);
-        case VIVIM_BF16: return dw_wgrad<bf16_t, false>(p, s);
-    }
-    return false;
+    return with_itype(p.itype, [&](auto t) { dw_wgrad<decltype(t), false>(p, s); });
 }
 
 }  // namespace vivim

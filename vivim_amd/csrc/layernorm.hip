@@ -29,6 +29,7 @@
 // and writing dx), then writes the same tile out token-major as dbranch = s[b] * dx.
 // Add-only mode (no weight, NORM = false): the forward stops after x_new, the backward is the scaled transposed copy of dres.
 #include "layernorm.cuh"
+#include "ops.cuh"
 
 namespace vivim {
 

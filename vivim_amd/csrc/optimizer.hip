@@ -25,7 +25,7 @@
 // order and the results are those of the fp32 route fed the widened gradients, bit for bit.  A launch is homogeneous: the
 // caller orders its tables by type and no call straddles two.
 #include <math.h>
-#include "common.cuh"
+#include "ops.cuh"
 
 namespace vivim {
 

@@ -65,15 +65,6 @@ struct ScanEnv {
 };
 const ScanEnv& scan_env();
 
-// Calls fn(T{}) with the element type of `itype` (capi has validated it).
-template <typename F> inline void with_itype(int itype, F&& fn) {
-    switch (itype) {
-        case VIVIM_F32: fn(float{}); break;
-        case VIVIM_F16: fn(f16_t{}); break;
-        case VIVIM_BF16: fn(bf16_t{}); break;
-    }
-}
-
 // Every hipFuncSetAttribute a dynamic-LDS launch above 64 KB needs (a host-side table write, no synchronisation).
 template <typename K> inline void allow_smem(K kernel, size_t smem) {
     if (smem > 65536)

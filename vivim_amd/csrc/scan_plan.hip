@@ -3,6 +3,7 @@
 #include <algorithm>
 #include <atomic>
 #include "scan_plan.cuh"
+#include "ops.cuh"
 
 namespace vivim {
 
@@ -52,11 +53,9 @@ static bool rows_vec_ok(const void* ptr, std::initializer_list<int64_t> strides,
         if (s % epv) return false;
     return true;
 }
-static int esize(int itype) { return itype == VIVIM_F32 ? 4 : 2; }
-static int epv16(int itype) { return 16 / esize(itype); }
 // the forward's activation rows: u, delta, out (+ z, out_z)
 static bool fwd_rows_vec_ok(const vivim_ssm_fwd_params& f, int64_t epv, bool ptrs = true) {
-    const int es = esize(f.itype);
+    const int es = elem_bytes(f.itype);
     auto P = [&](const void* q) { return ptrs ? q : nullptr; };
     return rows_vec_ok(P(f.u), {f.u_batch_stride, f.u_d_stride}, epv, es) &&
            rows_vec_ok(P(f.delta), {f.delta_batch_stride, f.delta_d_stride}, epv, es) &&
@@ -65,15 +64,15 @@ static bool fwd_rows_vec_ok(const vivim_ssm_fwd_params& f, int64_t epv, bool ptr
                      rows_vec_ok(P(f.out_z), {f.out_z_batch_stride, f.out_z_d_stride}, epv, es)));
 }
 static bool b_rows_vec_ok(const vivim_ssm_fwd_params& f, int64_t epv) {
-    return rows_vec_ok(f.B, {f.B_batch_stride, f.B_group_stride, f.B_dstate_stride}, epv, esize(f.itype));
+    return rows_vec_ok(f.B, {f.B_batch_stride, f.B_group_stride, f.B_dstate_stride}, epv, elem_bytes(f.itype));
 }
 static bool c_rows_vec_ok(const vivim_ssm_fwd_params& f, int64_t epv) {
-    return rows_vec_ok(f.C, {f.C_batch_stride, f.C_group_stride, f.C_dstate_stride}, epv, esize(f.itype));
+    return rows_vec_ok(f.C, {f.C_batch_stride, f.C_group_stride, f.C_dstate_stride}, epv, elem_bytes(f.itype));
 }
 // the backward's activation rows: u, delta, dout, du, ddelta (+ z, out, dz, out_z when given)
 static bool bwd_rows_vec_ok(const vivim_ssm_bwd_params& p, int64_t epv) {
     const vivim_ssm_fwd_params& f = p.f;
-    const int es = esize(f.itype);
+    const int es = elem_bytes(f.itype);
     return rows_vec_ok(f.u, {f.u_batch_stride, f.u_d_stride}, epv, es) &&
            rows_vec_ok(f.delta, {f.delta_batch_stride, f.delta_d_stride}, epv, es) &&
            rows_vec_ok(p.dout, {p.dout_batch_stride, p.dout_d_stride}, epv, es) &&
@@ -94,7 +93,7 @@ static bool ls_span_ok(int64_t rows, int64_t row_stride, int64_t len, int es) {
 static bool ls_shape_ok(const vivim_ssm_fwd_params& f) {
     if (!(f.is_variable_B && f.is_variable_C && (f.dstate == 16 || f.dstate == 32 || f.dstate == 64) && f.dim % f.n_groups == 0))
         return false;
-    const int es = esize(f.itype);
+    const int es = elem_bytes(f.itype);
     // (the resource's size field carries the channel, 0xffff0000 + chu, and a lane that is off stores at offset 0xfffffff0,
     // which must stay >= that size: chu < 65520)
     if (f.dim > 65520 || !ls_span_ok(f.dim, f.u_d_stride, f.seqlen, es) || !ls_span_ok(f.dim, f.delta_d_stride, f.seqlen, es) ||
@@ -176,7 +175,7 @@ static bool chan_shape_ok(const vivim_ssm_fwd_params& f, int ck) {
         const int64_t least = ck < kChunk ? 150000 : 110000;
         if (cols < 8 || cols * f.seqlen < least) return false;
     }
-    return fwd_rows_vec_ok(f, epv16(f.itype), false);
+    return fwd_rows_vec_ok(f, vec_elems(f.itype), false);
 }
 // segments of whole tiles for about scan_env().chan_waves waves in flight; the fp32 B / C copy, then the carries
 static size_t chan_layout(const vivim_ssm_fwd_params& f, FwdPlan& q) {
@@ -217,7 +216,7 @@ static FwdPlan plan_scan_fwd(const vivim_ssm_fwd_params& f, bool launch) {
     if (!launch) return q;
 
     // lanes = channels: long, wide problems (or tuning 5); either row length
-    if (chan && fwd_rows_vec_ok(f, epv16(f.itype)) && f.workspace && (size_t)f.workspace_bytes >= chan_ws &&
+    if (chan && fwd_rows_vec_ok(f, vec_elems(f.itype)) && f.workspace && (size_t)f.workspace_bytes >= chan_ws &&
         (reinterpret_cast<uintptr_t>(f.workspace) & 63) == 0) {
         // Measured, VIVIM_CHAN_XCD=0 / 1 (profiles/r02_chan_xcd_ab.log): the re-numbering gains 2 - 5 % on the bf16 grouped
         // shapes and where two workgroups share a group's B / C rows (cfg 3 stage 1), and loses 2 - 10 % on fp32 problems
@@ -230,11 +229,11 @@ static FwdPlan plan_scan_fwd(const vivim_ssm_fwd_params& f, bool launch) {
     if (states) {                                           // lanes = states (short checkpoint rows)
         // out / out_z normally inherit delta's / z's strides, which ls_shape_ok has already accepted; otherwise the call
         // is "not implemented"
-        const int es = esize(f.itype);
+        const int es = elem_bytes(f.itype);
         if (!ls_span_ok(f.dim, f.out_d_stride, f.seqlen, es) || (f.z && !ls_span_ok(f.dim, f.out_z_d_stride, f.seqlen, es)))
             return q;
         q.family = FwdFamily::states;
-        q.bc_vec = b_rows_vec_ok(f, epv16(f.itype)) && c_rows_vec_ok(f, epv16(f.itype));
+        q.bc_vec = b_rows_vec_ok(f, vec_elems(f.itype)) && c_rows_vec_ok(f, vec_elems(f.itype));
         const bool seg = ws_ok(f.workspace, f.workspace_bytes, ls_ws);
         q.S = seg ? lsS : 1;
         q.seg = seg ? ls_seg : (f.seqlen + q.ck - 1) / q.ck;
@@ -243,7 +242,7 @@ static FwdPlan plan_scan_fwd(const vivim_ssm_fwd_params& f, bool launch) {
     // n-split: 8 waves per workgroup, dstate / 8 states per wave.  The kernel uses unconditional 16-byte vectors: every row
     // must be 16-byte aligned and the sequence a whole number of 8-token lanes; anything else takes the generic kernel.
     q.family = FwdFamily::generic;
-    const int epv = epv16(f.itype);
+    const int epv = vec_elems(f.itype);
     if (!f.is_variable_B || !f.is_variable_C || f.dstate % 8 != 0 || f.seqlen % 8 != 0 || !fwd_rows_vec_ok(f, epv) ||
         !b_rows_vec_ok(f, epv) || !c_rows_vec_ok(f, epv))
         return q;
@@ -263,17 +262,19 @@ static FwdPlan plan_scan_fwd(const vivim_ssm_fwd_params& f, bool launch) {
 
 size_t scan_fwd_workspace_bytes(const vivim_ssm_fwd_params& f) { return plan_scan_fwd(f, false).ws; }
 
-bool ssm_fwd_dispatch(const vivim_ssm_fwd_params& p, hipStream_t s) {
-    const FwdPlan q = plan_scan_fwd(p, true);
+// The launches of plan q on p, full or lean; false: no family is built for it.
+static bool launch_fwd_plan(const vivim_ssm_fwd_params& p, const FwdPlan& q, hipStream_t s, bool lean) {
     switch (q.family) {
-        case FwdFamily::chan: launch_fwd_chan(p, q, s); return true;
-        case FwdFamily::states: launch_ls_fwd(p, q, s); return true;
-        case FwdFamily::nsplit: launch_fwd_nsplit(p, q, s); return true;
-        case FwdFamily::generic: launch_fwd_generic(p, s); return true;
+        case FwdFamily::chan: launch_fwd_chan(p, q, s, lean); return true;
+        case FwdFamily::states: launch_ls_fwd(p, q, s, lean); return true;
+        case FwdFamily::nsplit: launch_fwd_nsplit(p, q, s, lean); return true;
+        case FwdFamily::generic: launch_fwd_generic(p, s, lean); return true;
         case FwdFamily::none: break;
     }
     return false;
 }
+
+bool ssm_fwd_dispatch(const vivim_ssm_fwd_params& p, hipStream_t s) { return launch_fwd_plan(p, plan_scan_fwd(p, true), s, false); }
 
 // The lean forward (vivim_selective_scan_fwd_lean): no checkpoints, no `out` beside `out_z`.  It is planned as the full call
 // on the same tensors would be -- same family, same cut of the token axis, hence the same bits -- with the `out` the full
@@ -289,14 +290,7 @@ bool ssm_fwd_lean_dispatch(const vivim_ssm_fwd_params& p, void* last_state, hipS
     const FwdPlan q = plan_scan_fwd(f, true);
     f = p;
     f.x = last_state;
-    switch (q.family) {
-        case FwdFamily::chan: launch_fwd_chan(f, q, s, true); return true;
-        case FwdFamily::states: launch_ls_fwd(f, q, s, true); return true;
-        case FwdFamily::nsplit: launch_fwd_nsplit(f, q, s, true); return true;
-        case FwdFamily::generic: launch_fwd_generic(f, s, true); return true;
-        case FwdFamily::none: break;
-    }
-    return false;
+    return launch_fwd_plan(f, q, s, true);
 }
 
 // ---- backward ----------------------------------------------------------------------------------------------------------
@@ -358,7 +352,7 @@ static BwdPlan plan_scan_bwd(const vivim_ssm_fwd_params& f, const vivim_ssm_bwd_
     if (ls_shape_ok(f) && q.ck == ls_ckpt_len(f) && (tv == kBwdAuto || tv == kBwdStates1 || tv == kBwdStates2)) {
         // Which main kernel a shape gets is decided from sizes alone: dstate 16 and tuning 0 / 5 take the second generation,
         // 4 the first.  A call whose rows then fail its vector checks runs the first generation on the same segmentation.
-        const bool ls2_wanted = f.dstate == 16 && f.seqlen % epv16(f.itype) == 0 && (tv == kBwdAuto || tv == kBwdStates2);
+        const bool ls2_wanted = f.dstate == 16 && f.seqlen % vec_elems(f.itype) == 0 && (tv == kBwdAuto || tv == kBwdStates2);
         q.W = ls_bwd_waves(f);
         const int cpw = (4 / (f.dstate / 16)) * kLsCPR;
         const int bpg = (f.dim / f.n_groups + q.W * cpw - 1) / (q.W * cpw);
@@ -375,7 +369,7 @@ static BwdPlan plan_scan_bwd(const vivim_ssm_fwd_params& f, const vivim_ssm_bwd_
         if (!p) return q;
         q.family = BwdFamily::generic;                     // (reads the short checkpoint rows)
         {   // the tensors only the backward sees
-            const int es = esize(f.itype);
+            const int es = elem_bytes(f.itype);
             if (f.x == nullptr || !ls_span_ok(f.dim, p->dout_d_stride, f.seqlen, es) ||
                 !ls_span_ok(f.dim, p->du_d_stride, f.seqlen, es) || !ls_span_ok(f.dim, p->ddelta_d_stride, f.seqlen, es))
                 return q;
@@ -388,13 +382,13 @@ static BwdPlan plan_scan_bwd(const vivim_ssm_fwd_params& f, const vivim_ssm_bwd_
             q.S = 1;
             q.seg = (f.seqlen + ls_ckpt_len(f) - 1) / ls_ckpt_len(f);
         }
-        const int epv = epv16(f.itype);
+        const int epv = vec_elems(f.itype);
         q.bc_vec = b_rows_vec_ok(f, epv) && c_rows_vec_ok(f, epv);
         q.ls2 = ls2_wanted && bwd_rows_vec_ok(*p, epv);
         // The closed-form pre-pass (ssm_bwd_prepass_kernel) reads delta, dout, z and C with K-token vectors.  Measured: half
         // the time of the recurrence form (cfg 3 grouped stage 0: 989 against 1931 us).
         q.K = (q.seg * 16) % 512 == 0 && f.seqlen % 8 == 0 ? 8 : 4;
-        const int es = esize(f.itype), pv = (q.K * es >= 16 ? 16 : q.K * es) / es;
+        const int es = elem_bytes(f.itype), pv = (q.K * es >= 16 ? 16 : q.K * es) / es;
         q.closed_prepass = q.S > 1 && q.ls2 && (q.seg * 16) % 256 == 0 && f.seqlen % q.K == 0 &&
                            rows_vec_ok(f.delta, {f.delta_batch_stride, f.delta_d_stride}, pv, es) &&
                            rows_vec_ok(p->dout, {p->dout_batch_stride, p->dout_d_stride}, pv, es) &&
@@ -421,7 +415,7 @@ static BwdPlan plan_scan_bwd(const vivim_ssm_fwd_params& f, const vivim_ssm_bwd_
     q.family = BwdFamily::generic;
     // the fast kernel reads one checkpoint row per kChunk tokens, with unconditional K-element vectors: rows aligned to the
     // vector size, seqlen a whole number of lanes
-    const int es = esize(f.itype), epv = (q.K * es >= 16 ? 16 : q.K * es) / es;
+    const int es = elem_bytes(f.itype), epv = (q.K * es >= 16 ? 16 : q.K * es) / es;
     if (!q.K || f.x == nullptr || tv == kBwdGeneric || q.ck != kChunk || f.seqlen % q.K != 0 || !bwd_rows_vec_ok(*p, epv) ||
         !b_rows_vec_ok(f, epv) || !c_rows_vec_ok(f, epv))
         return q;
@@ -503,14 +497,14 @@ size_t scan_bwd_det_call_workspace_bytes(const vivim_ssm_bwd_params& p) {
     return scan_det_layout(p.f, q.family, q.S, q.W).bytes;
 }
 
-// 0: launched; 1: the family is not built; 2: workspace missing or too small (nothing launched).
-int ssm_bwd_det_dispatch(const vivim_ssm_bwd_params& p, void* det_ws, size_t det_ws_bytes, hipStream_t s) {
+// The deterministic protocol (det.cuh): a family that is not built and the slot workspace are refused before any launch.
+Launch ssm_bwd_det_dispatch(const vivim_ssm_bwd_params& p, void* det_ws, size_t det_ws_bytes, hipStream_t s) {
     const vivim_ssm_fwd_params& f = p.f;
     BwdPlan q = plan_scan_bwd(f, &p);
-    if (q.family == BwdFamily::none) return 1;
+    if (q.family == BwdFamily::none) return Launch::unsupported;
     det_tokens_width(f, &p, q);
     const ScanDetLayout l = scan_det_layout(f, q.family, q.S, q.W);
-    if (det_ws == nullptr || det_ws_bytes < l.bytes || reinterpret_cast<uintptr_t>(det_ws) % 16 != 0) return 2;
+    if (!det_ws_ok(det_ws, det_ws_bytes, l.bytes)) return Launch::bad_workspace;
     float* wA = static_cast<float*>(det_ws);
     float* wD = wA + l.nA * f.dim * f.dstate;
     float* wb = wD + l.nA * f.dim;
@@ -537,7 +531,7 @@ int ssm_bwd_det_dispatch(const vivim_ssm_bwd_params& p, void* det_ws, size_t det
         case BwdFamily::states: launch_ls_bwd(d, q, s, true); break;
         case BwdFamily::tokens: launch_bwd_fast(d, q, s, true); break;
         case BwdFamily::generic: launch_bwd_generic(d, q.ck, s, true); break;
-        case BwdFamily::none: return 1;
+        case BwdFamily::none: return Launch::unsupported;
     }
     det_reduce(wA, (int)l.nA, det_out(static_cast<float*>(p.dA), {f.dim, f.dstate}, {p.dA_d_stride, p.dA_dstate_stride}), s);
     if (p.dD) det_reduce(wD, (int)l.nA, det_out(static_cast<float*>(p.dD), {f.dim}, {1}), s);
@@ -550,7 +544,7 @@ int ssm_bwd_det_dispatch(const vivim_ssm_bwd_params& p, void* det_ws, size_t det
         bc(wB, p.dB, p.dB_batch_stride, p.dB_group_stride, p.dB_dstate_stride);
         bc(wC, p.dC, p.dC_batch_stride, p.dC_group_stride, p.dC_dstate_stride);
     }
-    return 0;
+    return Launch::ok;
 }
 
 bool ssm_bwd_dispatch(const vivim_ssm_bwd_params& p, hipStream_t s) {

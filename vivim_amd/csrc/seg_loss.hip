@@ -12,7 +12,7 @@
 // slot order, writes the loss and, per (image, class), the two Tversky gradient factors the backward needs.
 // seg_loss_bwd_kernel recomputes the softmax with the same tiling and writes dlogits in the logits' type.
 // Labels are only ever COMPARED with the class index: a label outside [0, C) is a pixel that belongs to no class.
-#include "common.cuh"
+#include "ops.cuh"
 #include "seg_load.cuh"      // sl_load, sl_labels, sl_aligned16: shared with seg_metrics.hip
 
 namespace vivim {
@@ -21,7 +21,7 @@ constexpr int kSlThreads = 256;      // 4 waves per workgroup
 constexpr int kSlMaxBlocks = 64;     // workgroups per image (grid-stride loop beyond): keeps the finalise kernel tiny
 
 static int sl_blocks_per_image(const vivim_seg_loss_params& p) {
-    const int64_t per_block = (int64_t)kSlThreads * (p.itype == VIVIM_F32 ? 4 : 8);
+    const int64_t per_block = (int64_t)kSlThreads * vec_elems(p.itype);
     const int64_t b = (p.pixels + per_block - 1) / per_block;
     return (int)(b < kSlMaxBlocks ? b : kSlMaxBlocks);
 }
@@ -250,12 +250,8 @@ static bool sl_classes(const vivim_seg_loss_params& p, bool bwd, hipStream_t str
 }
 
 bool seg_loss_dispatch(const vivim_seg_loss_params& p, bool bwd, hipStream_t stream) {
-    switch (p.itype) {
-        case VIVIM_F32: return sl_classes<float>(p, bwd, stream);
-        case VIVIM_F16: return sl_classes<f16_t>(p, bwd, stream);
-        case VIVIM_BF16: return sl_classes<bf16_t>(p, bwd, stream);
-    }
-    return false;
+    bool built = false;                  // false: no kernel for this class count
+    return with_itype(p.itype, [&](auto t) { built = sl_classes<decltype(t)>(p, bwd, stream); }) && built;
 }
 
 }  // namespace vivim

@@ -13,7 +13,7 @@
 // present in image n (tp + fn > 0) into state[c][0..5] and 1 into state[c][6], in fp64: the state is bit-repeatable.
 // Labels are only ever COMPARED with the class index: a label outside [0, C) is a pixel of no class -- a false positive of the
 // class predicted there and nothing else.
-#include "common.cuh"
+#include "ops.cuh"
 #include "seg_load.cuh"
 
 namespace vivim {
@@ -22,7 +22,7 @@ constexpr int kSmThreads = 256;      // 4 waves per workgroup
 constexpr int kSmMaxBlocks = 64;     // workgroups per image (grid-stride loop beyond): keeps the finalise kernel tiny
 
 static int sm_blocks_per_image(const vivim_seg_metrics_params& p) {
-    const int64_t per_block = (int64_t)kSmThreads * (p.itype == VIVIM_F32 ? 4 : 8);
+    const int64_t per_block = (int64_t)kSmThreads * vec_elems(p.itype);
     const int64_t b = (p.pixels + per_block - 1) / per_block;
     return (int)(b < kSmMaxBlocks ? b : kSmMaxBlocks);
 }
@@ -197,12 +197,8 @@ static bool sm_classes(const vivim_seg_metrics_params& p, hipStream_t stream) {
 }
 
 bool seg_metrics_dispatch(const vivim_seg_metrics_params& p, hipStream_t stream) {
-    switch (p.itype) {
-        case VIVIM_F32: return sm_classes<float>(p, stream);
-        case VIVIM_F16: return sm_classes<f16_t>(p, stream);
-        case VIVIM_BF16: return sm_classes<bf16_t>(p, stream);
-    }
-    return false;
+    bool built = false;                  // false: no kernel for this class count
+    return with_itype(p.itype, [&](auto t) { built = sm_classes<decltype(t)>(p, stream); }) && built;
 }
 
 }  // namespace vivim

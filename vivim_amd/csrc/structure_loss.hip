@@ -14,9 +14,8 @@
 // channel and thread, wave_sum, one LDS step across the waves, and the workgroup STORES its 4 * C floats into slot (image, tile)
 // of the workspace -- no atomics, the order of every sum depends on the shape alone.  sl_finalize adds the slots in slot order
 // in fp64.  The backward kernel recomputes k, w and the sigmoid with the same tiling and writes dlogits in the logits' type.
-#include "common.cuh"
+#include "ops.cuh"
 #include "seg_load.cuh"      // sl_load, sl_labels, sl_aligned16
-#include "../../include/vivim_hip_ext.h"
 
 namespace vivim {
 
@@ -262,12 +261,7 @@ static void st_launch(const vivim_structure_loss_params& p, bool bwd, hipStream_
 }
 
 bool structure_loss_dispatch(const vivim_structure_loss_params& p, bool bwd, hipStream_t stream) {
-    switch (p.itype) {
-        case VIVIM_F32: st_launch<float>(p, bwd, stream); return true;
-        case VIVIM_F16: st_launch<f16_t>(p, bwd, stream); return true;
-        case VIVIM_BF16: st_launch<bf16_t>(p, bwd, stream); return true;
-    }
-    return false;
+    return with_itype(p.itype, [&](auto t) { st_launch<decltype(t)>(p, bwd, stream); });
 }
 
 }  // namespace vivim

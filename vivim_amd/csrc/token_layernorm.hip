@@ -24,7 +24,7 @@
 // entry points run the arithmetic they always ran.  E is then one 16-byte vector of the NARROWER of the two types, so that the
 // wider stream moves in two 16-byte accesses per chunk.
 #include <algorithm>
-#include "common.cuh"
+#include "ops.cuh"
 
 namespace vivim {
 
@@ -285,7 +285,6 @@ __global__ void __launch_bounds__(kWave * kTlnRedWaves) tln_slot_sum_kernel(cons
     else if (dbias) dbias[col - C] = s;
 }
 
-static int tln_isize(int t) { return t == VIVIM_F32 ? 4 : 2; }
 
 static int tln_slots(int64_t rows) { return (int)std::min<int64_t>(kTlnMaxSlots, (rows + 3) / 4); }
 size_t token_layernorm_bwd_workspace_bytes(const vivim_token_layernorm_params& p) {
@@ -352,8 +351,9 @@ bool token_layernorm_dispatch(const vivim_token_layernorm_params& p, bool bwd, h
     a.x_row_stride = p.x_row_stride, a.y_row_stride = p.y_row_stride, a.dy_row_stride = p.dy_row_stride, a.dx_row_stride = p.dx_row_stride;
     a.x = p.x, a.weight = p.weight, a.bias = p.bias, a.y = p.y, a.mean = p.mean, a.rstd = p.rstd;
     a.dy = p.dy, a.dx = p.dx, a.dweight = p.dweight, a.dbias = p.dbias, a.workspace = p.workspace;
+    if (bwd && !p.dweight && !p.dbias) a.workspace = nullptr;       // nothing to sum: the kernel stores no slot
     // 16-byte accesses: whole vectors of x per row, and every address and row stride of this call on a 16-byte boundary
-    const int isz = tln_isize(p.itype), osz = tln_isize(p.otype);
+    const int isz = elem_bytes(p.itype), osz = elem_bytes(p.otype);
     bool vec = p.channels % (16 / isz) == 0 && tln_s16(p.x, p.x_row_stride, isz) && tln_s16(p.weight, 0, 4);
     if (!bwd) vec = vec && tln_s16(p.y, p.y_row_stride, osz) && tln_s16(p.bias, 0, 4);
     else vec = vec && tln_s16(p.dy, p.dy_row_stride, osz) && tln_s16(p.dx, p.dx_row_stride, isz);
@@ -379,7 +379,7 @@ bool token_add_norm_dispatch(const vivim_token_add_norm_params& p, bool bwd, hip
     TlnArgs a = {};
     a.rows = p.rows, a.channels = p.channels, a.rows_per_sample = p.rows_per_sample, a.rms = p.rms, a.eps = p.eps;
     a.weight = p.weight, a.bias = p.bias, a.mean = p.mean, a.rstd = p.rstd, a.scale = p.scale;
-    const int bsz = tln_isize(p.btype), rsz = tln_isize(p.rtype);
+    const int bsz = elem_bytes(p.btype), rsz = elem_bytes(p.rtype);
     bool vec = p.channels % (16 / std::min(bsz, rsz)) == 0 && tln_s16(p.weight, 0, 4);
     if (!bwd) {
         a.branch = p.branch, a.branch_row_stride = p.branch_row_stride;
@@ -392,7 +392,8 @@ bool token_add_norm_dispatch(const vivim_token_add_norm_params& p, bool bwd, hip
         if (p.weight != nullptr) {
             a.x = p.res_out, a.x_row_stride = p.res_out_row_stride;
             a.dy = p.dy, a.dy_row_stride = p.dy_row_stride;
-            a.dweight = p.dweight, a.dbias = p.dbias, a.workspace = p.workspace;
+            a.dweight = p.dweight, a.dbias = p.dbias;
+            a.workspace = p.dweight || p.dbias ? p.workspace : nullptr;      // nothing to sum: the kernel stores no slot
         }
         a.dres = p.dres, a.dres_row_stride = p.dres_row_stride;
         a.dx = p.dres_in, a.dx_row_stride = p.dres_in_row_stride;

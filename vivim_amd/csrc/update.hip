@@ -3,7 +3,7 @@
 // launches are latency-bound (batch * dim threads), so the only design rule is coalescing: consecutive threads are
 // consecutive channels, a thread's state row (width or dstate elements) is contiguous in the usual layouts, and a
 // wave therefore touches one contiguous block.
-#include "common.cuh"
+#include "ops.cuh"
 
 namespace vivim {
 

@@ -14,7 +14,7 @@
 // lanes over output columns (coalesced reads of dy) into an fp32 LDS tile of kUpTileH input rows, then a horizontal pass out of
 // LDS -- and walks a column window wider than the tile in chunks, in ascending order.
 // Every grid is one-dimensional (blockIdx.x decoded on the scalar unit), so N * C planes are not bound by the y / z limits.
-#include "common.cuh"
+#include "ops.cuh"
 #include "seg_load.cuh"
 #include "up_tap.cuh"
 
@@ -179,7 +179,7 @@ static bool up_cl_vec(const vivim_upsample_params& p, bool bwd, int64_t elem) {
 // workgroups of the launch (the capi check keeps it within a 31-bit grid)
 int64_t upsample_blocks(const vivim_upsample_params& p, bool bwd) {
     if (p.layout == 1) {
-        const int64_t elem = p.itype == VIVIM_F32 ? 4 : 2, E = up_cl_vec(p, bwd, elem) ? 16 / elem : 1;
+        const int64_t elem = elem_bytes(p.itype), E = up_cl_vec(p, bwd, elem) ? 16 / elem : 1;
         const int64_t rows = bwd ? p.in_h : p.out_h, cols = bwd ? p.in_w : p.out_w;
         return (int64_t)p.batch * rows * up_ceil_div(cols * (p.channels / E), kUpThreads);
     }
@@ -215,12 +215,7 @@ static void up_launch(const vivim_upsample_params& p, bool bwd, hipStream_t stre
 }
 
 bool upsample_dispatch(const vivim_upsample_params& p, bool bwd, hipStream_t stream) {
-    switch (p.itype) {
-        case VIVIM_F32: up_launch<float>(p, bwd, stream); return true;
-        case VIVIM_F16: up_launch<f16_t>(p, bwd, stream); return true;
-        case VIVIM_BF16: up_launch<bf16_t>(p, bwd, stream); return true;
-    }
-    return false;
+    return with_itype(p.itype, [&](auto t) { up_launch<decltype(t)>(p, bwd, stream); });
 }
 
 }  // namespace vivim

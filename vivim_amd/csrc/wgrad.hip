@@ -17,7 +17,7 @@
 // stage-0 products took 166 / 103 us, with sixteen 24 / 22 (profiles/r03_wgrad_sweep.txt; torch.bmm: 74 / 63).  (Adding the four waves of a workgroup up in LDS first
 // was tried: 64 ds_add_f32 per lane cost 20-38 us, more than the global atomics they saved.)  Rows beyond M / N are read from
 // the last valid row and dropped.  HBM-bound by design: both operands once (a again per column tile of b).
-#include "common.cuh"
+#include "ops.cuh"
 
 namespace vivim {
 
