@@ -1,8 +1,9 @@
 /* vivim_hip_ext.h -- entry points of libvivim_hip.so added after ABI version 8.
  *
  * include/vivim_hip.h is frozen at version 8: its structs, its functions, vivim_sizeof and vivim_abi_version() stay as they are.
- * Whatever is added afterwards is declared here, exported from the same library and bound by the same parser
- * (vivim_amd/_lib.py: parse_header, into EXT_STRUCT_NAMES / EXT_ENTRY_POINTS), so this file is written in the same restricted C:
+ * This file holds the structure loss, the first addition since; a later feature declares its interface in a header of its own
+ * (vivim_hip_ext_<feature>.h; vivim_amd/_lib.py: EXTENSIONS).  All are exported from the same library and bound by the same parser
+ * (parse_header; this one into EXT_STRUCT_NAMES / EXT_ENTRY_POINTS), so this file is written in the same restricted C:
  * fixed-width fields, explicit padding, one `typedef struct { ... } vivim_*;` per params struct, plain function declarations.
  * Every struct declared here opens with `struct_bytes`: the caller sets it to sizeof of the struct as it compiled it, the
  * entry points refuse any other value, and there is no vivim_sizeof row.

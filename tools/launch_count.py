@@ -2,13 +2,15 @@
 one whole train step, by kernel name -- the step is host-bound, so launches are what it pays for.
     python tools/launch_count.py [--dim 64] [--batch 3] [--frames 5] [--hw 4096] [--step] [--fused-loss] [--backbone-layernorm]
                                   [--backbone-add-norm] [--fp16] [--clip-grad-norm X] [--fused-optimizer] [--master-weights]
+                                  [--head-concat]
 --fused-loss (with --step) counts the step with train_step(fused_loss=True) as well, and the loss alone (forward + backward on
 the step's logits shape) both ways.  --backbone-layernorm (with --step) builds the model with fast_backbone_layernorm=True,
 --backbone-add-norm with fused_backbone_add_norm=True.  --fp16 and --clip-grad-norm X (with --step) count the step under fp16
 autocast with the dynamic loss scale and with gradient clipping; --fused-optimizer counts that step with
 make_optimizer(fused_step=True) as well (the optimizer phase on the device: csrc/optimizer.hip), and --master-weights (with both)
 counts it once more, last, with the model's Linear / Conv2d parameters lowered to the autocast dtype and
-make_optimizer(fused_step=True, master_weights=True): autocast's per-parameter casts are gone."""
+make_optimizer(fused_step=True, master_weights=True): autocast's per-parameter casts are gone.  --head-concat counts one Vivim.decode call (forward + backward, train mode, bf16
+autocast, the bench's head shape) with Vivim(fused_head_concat=...) off and on."""
 import argparse
 import collections
 import os
@@ -56,6 +58,7 @@ def main():
     ap.add_argument("--clip-grad-norm", type=float, default=None)
     ap.add_argument("--fused-optimizer", action="store_true")
     ap.add_argument("--master-weights", action="store_true")
+    ap.add_argument("--head-concat", action="store_true")
     a = ap.parse_args()
     dev = torch.device("cuda:0")
     from vivim_amd.mamba_simple import Mamba
@@ -68,6 +71,22 @@ def main():
             y = m(x, nframes=a.frames)
         y.float().square().mean().backward()
     show(f"Mamba v3 block dim {a.dim} L {a.frames * a.hw} batch {a.batch}", *launches(block))
+    if a.head_concat:
+        from vivim_amd import train_step as ts
+        head = ts.build_model(3, dev, fused_head_concat=True).train()
+        g = torch.Generator().manual_seed(15)
+        states = tuple(torch.randn(a.batch * a.frames, c, 64 >> s, 64 >> s, generator=g).to(dev)
+                       for s, c in enumerate((64, 128, 320, 512)))
+        for switch in (False, True):
+            def decode(switch=switch):
+                head.fused_head_concat = switch
+                head.zero_grad(set_to_none=True)
+                with torch.autocast("cuda", dtype=torch.bfloat16):
+                    out = head.decode(states, a.batch, a.frames)
+                out.float().square().mean().backward()
+            show(f"Vivim.decode forward + backward, ({a.batch * a.frames}; 64^2 ... 8^2) bf16, fused_head_concat={switch}",
+                 *launches(decode), top=40)
+        del head, states
     if a.step:
         from vivim_amd import train_step as ts
         model = ts.build_model(3, dev, fast_backbone_layernorm=a.backbone_layernorm, fused_backbone_add_norm=a.backbone_add_norm)

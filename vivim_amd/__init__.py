@@ -20,6 +20,9 @@ def __getattr__(name):
     if name in ("fused_decode_head", "fold_decode_head"):     # the eval-mode decode head (decode_head.py), likewise
         from . import decode_head
         return getattr(decode_head, name)
+    if name == "upsample_concat":                      # the training decode head's upsample + dropout + concat (head_concat.py), likewise
+        from . import head_concat
+        return head_concat.upsample_concat
     if name in ("FusedStepAdamW", "lower_params", "raise_params"):   # the device-side clip + AdamW step (optimizer.py), likewise
         from . import optimizer
         return getattr(optimizer, name)

@@ -2,8 +2,9 @@
 
 The header is the one description of the ABI: it is parsed once, at import, into the params structs, the entry-point table
 and the constants below.  The parser refuses whatever it does not understand instead of guessing.  That header is frozen at
-ABI version 8; what was added since is declared in include/vivim_hip_ext.h, parsed the same way into EXT_STRUCT_NAMES and
-EXT_ENTRY_POINTS, and exported from the same library: `call` and `launch` take a name of either table.
+ABI version 8; what was added since is declared in extension headers, one per feature (EXTENSIONS: include/vivim_hip_ext.h, parsed
+into EXT_STRUCT_NAMES and EXT_ENTRY_POINTS, and include/vivim_hip_ext_head.h), parsed the same way and exported from the same
+library: `call` and `launch` take a name of any table.
 
 The library is the product: if it is missing or fails to load this module raises -- there is no
 PyTorch/CPU fallback anywhere in vivim_amd.
@@ -43,6 +44,12 @@ STRUCT_NAMES = {
 # The same table for include/vivim_hip_ext.h.  vivim_hip.h is frozen at version 8 (and with it the tables derived from it below);
 # a struct added since is declared there, opens with `struct_bytes` and has no vivim_sizeof row.
 EXT_STRUCT_NAMES = {"vivim_structure_loss_params": "StructureLossParams"}
+# Every extension header, by file name under include/: (C struct -> Python class, entry points).  A feature added after the
+# structure loss brings a header of its own, vivim_hip_ext_<feature>.h; the entry points are filled in below, where the headers are parsed.
+EXTENSIONS = {
+    "vivim_hip_ext.h": (EXT_STRUCT_NAMES, {}),
+    "vivim_hip_ext_head.h": ({"vivim_head_concat_params": "HeadConcatParams"}, {}),
+}
 
 # One entry per exported function: its params struct (or None), the ctypes types of the arguments between `params` and
 # `stream` in the C signature, whether a stream comes last, and the restype.
@@ -53,7 +60,7 @@ _FIELD_TYPES = {"int32_t": i32, "int64_t": i64, "float": ctypes.c_float, "double
                 "const int64_t *": ctypes.POINTER(i64)}
 _ARG_TYPES = {"void *": vp, "size_t": ctypes.c_size_t, "int": ctypes.c_int}
 _RESTYPES = {"int": ctypes.c_int, "size_t": ctypes.c_size_t, "const char *": ctypes.c_char_p}
-_DIRECTIVES = r"\s*#\s*(include|define|ifndef\s+VIVIM_HIP(_EXT)?_H|endif)\b"        # what may stand outside a struct
+_DIRECTIVES = r"\s*#\s*(include|define|ifndef\s+VIVIM_HIP(_[A-Z0-9]+)*_H|endif)\b"        # what may stand outside a struct
 
 
 def _refuse(what, text):
@@ -160,10 +167,17 @@ EXPORTS = tuple(ENTRY_POINTS)
 ABI_VERSION = _consts["VIVIM_ABI_VERSION"]
 F32, F16, BF16 = _consts["VIVIM_F32"], _consts["VIVIM_F16"], _consts["VIVIM_BF16"]
 OPT_CHUNK, OPT_MAX_TENSORS, OPT_STATE_WORDS = (_consts["VIVIM_OPT_" + n] for n in ("CHUNK", "MAX_TENSORS", "STATE_WORDS"))
-_, _ext_classes, EXT_ENTRY_POINTS = parse_header(_read_header(EXT_HEADER), EXT_STRUCT_NAMES)
-if any(_has_sizeof_row(c) for c in _ext_classes.values()) or set(EXT_ENTRY_POINTS) & set(ENTRY_POINTS):
-    raise ImportError(f"{EXT_HEADER}: a struct that does not open with struct_bytes, or a function vivim_hip.h already declares")
-globals().update(_ext_classes)                          # StructureLossParams
+ALL_ENTRY_POINTS = dict(ENTRY_POINTS)                    # every table: what lib() binds and `call` takes
+for _file, (_names, _entries) in EXTENSIONS.items():
+    _path = os.path.join(os.path.dirname(HEADER), _file)
+    _, _ext_classes, _parsed = parse_header(_read_header(_path), _names)
+    if any(_has_sizeof_row(c) for c in _ext_classes.values()) or set(_parsed) & set(ALL_ENTRY_POINTS) \
+            or set(_ext_classes) & set(globals()):
+        raise ImportError(f"{_path}: a struct that does not open with struct_bytes, or a name another header already declares")
+    _entries.update(_parsed)
+    ALL_ENTRY_POINTS.update(_parsed)
+    globals().update(_ext_classes)                      # StructureLossParams, HeadConcatParams
+EXT_ENTRY_POINTS = EXTENSIONS[os.path.basename(EXT_HEADER)][1]         # the structure-loss table
 
 _lib = None
 
@@ -189,7 +203,7 @@ def lib():
         # and every launch of ours then fails with "no ROCm-capable device is detected" (seen with build() followed by
         # smoke() in one process)
         L = ctypes.CDLL(SO_PATH)
-        for name, e in {**ENTRY_POINTS, **EXT_ENTRY_POINTS}.items():
+        for name, e in ALL_ENTRY_POINTS.items():
             fn = getattr(L, name)
             fn.argtypes = ([ctypes.POINTER(e.struct)] if e.struct else []) + list(e.extra) + ([vp] if e.stream else [])
             fn.restype = e.restype
@@ -248,6 +262,10 @@ def algorithmic_bytes(name, P):
         px = sum(P.map_h[s] * P.map_w[s] for s in range(P.n_maps))
         return (P.batch * (px * P.hidden + P.classes * P.out_h * P.out_w) * _ISIZE[P.itype]
                 + 4 * (P.hidden + P.classes * P.hidden + P.classes))
+    if name.startswith("vivim_head_concat"):                            # the maps, the masks, the concat: once each, either direction
+        px = P.out_h * P.out_w
+        maps = sum(P.map_c[s] * (P.map_h[s] * P.map_w[s] + px) for s in range(P.n_maps)) * _ISIZE[P.itype]
+        return P.batch * (maps + sum(P.map_c[s] * px for s in range(P.n_maps) if P.keep[s]))
     if name.startswith("vivim_upsample"):                               # the small and the large tensor once, either direction
         return P.batch * P.channels * (P.in_h * P.in_w + P.out_h * P.out_w) * _ISIZE[P.itype]
     if name.startswith("vivim_seg_metrics"):                            # logits, labels, the prediction map if wanted, the counts

@@ -7,6 +7,7 @@
 #pragma once
 #include "det.cuh"
 #include "../../include/vivim_hip_ext.h"
+#include "../../include/vivim_hip_ext_head.h"
 
 namespace vivim {
 
@@ -79,6 +80,10 @@ int64_t upsample_blocks(const vivim_upsample_params&, bool bwd);
 bool decode_head_dispatch(const vivim_decode_head_params&, hipStream_t);
 int64_t decode_head_blocks(const vivim_decode_head_params&);
 int decode_head_max_hidden();
+
+// ---- the training head's upsample + dropout + concat: head_concat.hip
+bool head_concat_dispatch(const vivim_head_concat_params&, bool bwd, hipStream_t);
+int64_t head_concat_blocks(const vivim_head_concat_params&, bool bwd);
 
 // ---- fused clip + AdamW step, plain and with fp32 masters: optimizer.hip
 void opt_grad_stats_launch(const vivim_opt_step_params&, hipStream_t);

@@ -1,5 +1,6 @@
 // up_tap.cuh -- the one tap function of bilinear upsampling (align_corners = False), shared by the upsampling kernels
-// (upsample.hip) and the fused decode head (decode_head.hip): an output index becomes (i0, i1, l0, l1) with ATen's fp32 arithmetic.
+// (upsample.hip), the fused decode head (decode_head.hip) and the training head's concat (head_concat.hip): an output index becomes
+// (i0, i1, l0, l1) with ATen's fp32 arithmetic.  Below it, what the gather-form backwards share: which outputs tap an input index.
 #pragma once
 #include "common.cuh"
 
@@ -21,6 +22,20 @@ __device__ __forceinline__ UpTap up_tap(int o, float r, int n_in) {
     t.l1 = src - (float)t.i0;
     t.l0 = 1.0f - t.l1;
     return t;
+}
+
+__device__ __forceinline__ bool up_hits(const UpTap& t, int i) { return t.i0 == i || t.i1 == i; }
+__device__ __forceinline__ float up_weight(const UpTap& t, int i) { return (t.i0 == i ? t.l0 : 0.0f) + (t.i1 == i ? t.l1 : 0.0f); }
+
+// Output indices that can tap input index i: exactly those with src in (i - 1, i + 1), o in (A, B) with
+// A = ((2i - 1) n_out - n_in) / (2 n_in) and B = ((2i + 3) n_out - n_in) / (2 n_in); two more on either side cover the fp32
+// rounding of src.  (2 n_in + 3) n_out fits 31 bits (host check).  Every output whose src is clamped to 0 names i0 = 0 and, with
+// l1 = 0, i1 = 1: the window of i <= 1 starts at output 0.
+__device__ __forceinline__ void up_window(int i, int n_in, int n_out, int& lo, int& hi) {
+    const int a = ((2 * i - 1) * n_out - n_in) / (2 * n_in) - 2;
+    const int b = ((2 * i + 3) * n_out - n_in) / (2 * n_in) + 2;
+    lo = i <= 1 || a < 0 ? 0 : a;
+    hi = b > n_out - 1 ? n_out - 1 : b;
 }
 
 }  // namespace vivim

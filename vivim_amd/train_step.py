@@ -54,7 +54,7 @@ def recall_focused_loss(logits, targets, num_classes, gamma=2.0, onehot=None, al
 
 def build_model(num_classes=3, device="cuda", mamba_kwargs=None, drop_path_rate=0.2, fast_backbone_dwconv=True,
                 fused_upsample=False, fused_decode_head=False, fast_backbone_layernorm=False, fused_backbone_add_norm=False,
-                low_precision_params=None):
+                low_precision_params=None, fused_head_concat=False):
     """Vivim with a randomly initialised SegFormer-b3 backbone (no hub access on the GPU box).  The two
     parameter groups that never receive a gradient in Vivim's forward -- the SegFormer 150-class classifier
     and the per-stage encoder layer norms (vivim.py:211-212, 325) -- are frozen so DDP needs no
@@ -64,13 +64,14 @@ def build_model(num_classes=3, device="cuda", mamba_kwargs=None, drop_path_rate=
     csrc/token_layernorm.hip, and `fused_backbone_add_norm`: the SegFormer blocks' residual adds fused with the LayerNorm that
     reads the sum (vivim._run_stage).  `low_precision_params` (torch.float16 / torch.bfloat16, opt-in): the nn.Linear / nn.Conv2d
     parameters outside the Mamba layers are stored in that dtype once the model is on the device (optimizer.lower_params);
-    such a model trains under autocast to that dtype with `make_optimizer(model, fused_step=True, master_weights=True)`."""
+    such a model trains under autocast to that dtype with `make_optimizer(model, fused_step=True, master_weights=True)`.
+    `fused_head_concat`: the training decode head's upsampling, dropout and concat as one kernel each way (head_concat.py)."""
     from .vivim import Vivim, segformer_b3_random
     model = Vivim(in_chans=3, out_chans=num_classes, backbone=segformer_b3_random(),
                   drop_path_rate=drop_path_rate, mamba_kwargs=mamba_kwargs,
                   fast_backbone_dwconv=fast_backbone_dwconv, fused_upsample=fused_upsample,
                   fused_decode_head=fused_decode_head, fast_backbone_layernorm=fast_backbone_layernorm,
-                  fused_backbone_add_norm=fused_backbone_add_norm)
+                  fused_backbone_add_norm=fused_backbone_add_norm, fused_head_concat=fused_head_concat)
     from .dp import freeze_unused
     freeze_unused(model)
     model = model.to(device)

@@ -32,6 +32,14 @@ Differences from the reference, all additive:
     stage with every residual add fused with the LayerNorm that reads the sum (`_run_stage`; layernorm.add_layer_norm_tm /
     add_tm, csrc/token_layernorm.hip): DropPath is a per-sample factor inside the kernel, the stream is read and written once
     per site.  Same Parameters and keys; off by default, `VIVIM_NO_FUSED_LAYERNORM=1` opts out again.
+  * `Vivim(..., fused_head_concat=True)` (also on train_step.build_model) runs the part of the decode head between the
+    projections and linear_fuse -- per map upsampling, the coin-flipped dropout, torch.cat and, under autocast, the cast -- as one
+    kernel forward and one backward (head_concat.py, csrc/head_concat.hip) wherever the eval-mode head above does not apply:
+    training and every grad-mode forward.  linear_fuse is handed a channels-last tensor in the dtype it would have cast to; the
+    full-size fp32 maps and the fp32 concat never exist.  The CPU coin flips are the stock route's, one per map in the same order;
+    the dropout masks are drawn on the device from F.dropout's distribution but not with its bits (as `DropPath` above against
+    SegformerDropPath: the same distribution and scaling, another random stream).  Off by default, `VIVIM_NO_HEAD_CONCAT=1` opts
+    out again; tensors the kernels do not take run the stock path unchanged.
   * timm is not required: DropPath / trunc_normal_ are the torch equivalents.
 """
 import math
@@ -44,6 +52,7 @@ import torch.nn.functional as F
 
 from . import decode_head as _dh
 from . import dwconv as _dw
+from . import head_concat as _hc
 from . import layernorm as _ln
 from . import upsample as _up
 from .mamba_simple import Mamba
@@ -475,9 +484,10 @@ class Vivim(nn.Module):
                  conv_block: bool = True, res_block: bool = True, spatial_dims=2, with_edge=False,
                  dropout_rate=0.3, backbone=None, mamba_kwargs=None, fast_backbone_dwconv=False,
                  fused_upsample=False, fused_decode_head=False, fast_backbone_layernorm=False,
-                 fused_backbone_add_norm=False) -> None:
+                 fused_backbone_add_norm=False, fused_head_concat=False) -> None:
         super().__init__()
         self.fused_upsample = fused_upsample
+        self.fused_head_concat = fused_head_concat
         self.fused_decode_head = fused_decode_head
         self.hidden_size = hidden_size
         self.in_chans, self.out_chans = in_chans, out_chans
@@ -518,20 +528,34 @@ class Vivim(nn.Module):
             return _dh.eval_decode(self, encoder_hidden_states)
         batch_size = encoder_hidden_states[-1].shape[0]
         size0 = encoder_hidden_states[0].shape[2:]
+        projections = self._decoder_projections()
+        project = lambda state, mlp: mlp(state).permute(0, 2, 1).reshape(batch_size, -1, state.shape[2], state.shape[3])   # noqa: E731
+        states = None
+        if self.fused_head_concat and not os.environ.get("VIVIM_NO_HEAD_CONCAT"):
+            # upsampling, dropout, concat and autocast's cast as one kernel each way (head_concat.py).  The projections are the
+            # stock path's, and so are the coins: one torch.rand(1) per map in stage order, so the CPU RNG leaves either route
+            # in the same state.  The masks themselves are drawn on the device, from F.dropout's distribution but not its bits.
+            states = [project(state, mlp) for state, mlp in zip(encoder_hidden_states, projections)]
+            if _hc.supported(states[::-1], size0):
+                coins = [torch.rand(1).item() > 0.5 for _ in states]
+                p = [self.dropout_rate / 2 if coin and self.training else None for coin in coins]
+                return self._decode_tail(_hc.upsample_concat(states[::-1], size0, p[::-1]))
         feats = ()
-        for state, mlp in zip(encoder_hidden_states, self._decoder_projections()):
-            height, width = state.shape[2], state.shape[3]
-            state = mlp(state).permute(0, 2, 1).reshape(batch_size, -1, height, width)
+        for i, (state, mlp) in enumerate(zip(encoder_hidden_states, projections)):
+            state = states[i] if states is not None else project(state, mlp)
             state = self._upsample(state, size0)
             if torch.rand(1).item() > 0.5:          # per-map dropout coin flip on the CPU RNG (vivim.py:310-312)
                 state = F.dropout(state, p=self.dropout_rate / 2, training=self.training)
             feats += (state,)
+        return self._decode_tail(torch.cat(feats[::-1], dim=1))
+
+    def _decode_tail(self, concat):
         # linear_fuse / out stay nn.Conv2d on MIOpen, as in the reference.  They were batched GEMMs for a while (+18%
         # frames/s): the library GEMM for 768 x 3072 x 61440 bf16 on the channels-last concat (hipBLASLt picks
         # Custom_Cijk_Alik_Bljk_BBS_BH_Bias_HA_S_SAV_NTD_SK3_UserArgs_MT256x256x64) dies with a GPU memory access fault
         # in no_grad forwards and, with other allocation sizes, in training; no BLAS backend / workspace setting
         # avoided it.
-        hidden = self.decoder.linear_fuse(torch.cat(feats[::-1], dim=1))
+        hidden = self.decoder.linear_fuse(concat)
         hidden = self.decoder.activation(self.decoder.batch_norm(hidden))
         hidden = self.decoder.dropout(self.decoder.dropout(hidden))   # applied twice (vivim.py:319-322)
         hidden = self.feature_dropout(hidden)
