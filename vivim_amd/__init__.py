@@ -14,6 +14,9 @@ def __getattr__(name):
     if name in ("SegMetricsTracker", "seg_confusion_counts"):
         from . import seg_metrics
         return getattr(seg_metrics, name)
+    if name in ("BinaryMetricsTracker", "binary_image_metrics"):      # the binary recipe's validation metrics (binary_metrics.py), likewise
+        from . import binary_metrics
+        return getattr(binary_metrics, name)
     if name == "bilinear_upsample":                    # the decode head's upsampling (upsample.py), likewise
         from . import upsample
         return upsample.bilinear_upsample

@@ -279,6 +279,10 @@ def algorithmic_bytes(name, P):
         n = P.batch * P.pixels
         return (n * ((2 if name.endswith("bwd") else 1) * P.classes * _ISIZE[P.itype] + (8 if P.ttype == 0 else 1))
                 + 8 * P.batch * P.classes)
+    if name.startswith("vivim_binary_metrics"):                         # pred and gt read by three launches | values, histograms, state
+        n = P.batch * P.height * P.width
+        return (3 * n * (_ISIZE[P.ptype] + _ISIZE.get(P.gtype, 1)) + P.batch * (72 + (4096 if P.hist else 0))
+                + (160 if P.state else 0))
     if name.startswith("vivim_selective_scan"):
         s = _ISIZE[f.itype]
         act = f.batch * f.dim * f.seqlen * s

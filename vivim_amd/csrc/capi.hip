@@ -1007,4 +1007,54 @@ int vivim_head_concat_bwd(const vivim_head_concat_params* p, void* stream) {
     return after_launch(fn);
 }
 
+// ---- include/vivim_hip_ext_binary_metrics.h: the validation metrics of the binary recipe ----
+
+// every refusal that needs no workspace, before any launch; `fn` names the caller in the message
+static int check_binary_metrics(const vivim_binary_metrics_params* p, const char* fn) {
+    if (p == nullptr) return fail(VIVIM_ERR_INVALID, "%s: params is NULL", fn);
+    if (int rc = check_struct_bytes(fn, "vivim_binary_metrics_params", p->struct_bytes, sizeof(*p))) return rc;
+    if (!dtype_ok(p->ptype)) return fail(VIVIM_ERR_INVALID, "%s: ptype = %d: pred is fp32 / fp16 / bf16 (0 / 1 / 2)", fn, p->ptype);
+    if (!dtype_ok(p->gtype) && p->gtype != 3)
+        return fail(VIVIM_ERR_INVALID, "%s: gtype = %d: gt is fp32 / fp16 / bf16 (0 / 1 / 2) or uint8 / bool (3)", fn, p->gtype);
+    if (p->batch <= 0 || p->height <= 0 || p->width <= 0)
+        return fail(VIVIM_ERR_INVALID, "%s: batch = %d, height = %d, width = %d: every size must be positive", fn, p->batch, p->height, p->width);
+    const int64_t pixels = (int64_t)p->height * p->width;
+    if (pixels < 2) return fail(VIVIM_ERR_INVALID, "%s: height * width = %lld: the metrics need at least 2 pixels", fn, (long long)pixels);
+    // the kernels index inside an image and build their grid with 32-bit integers (a thread counts up to 8 pixels past the end)
+    if (pixels > INT32_MAX - 4096 || (int64_t)p->batch * 32 > INT32_MAX)
+        return fail(VIVIM_ERR_INVALID, "%s: batch = %d, height * width = %lld: the index range overflows int32", fn, p->batch, (long long)pixels);
+    if (p->pred_batch_stride < pixels || p->gt_batch_stride < pixels)
+        return fail(VIVIM_ERR_INVALID, "%s: pred_batch_stride = %lld, gt_batch_stride = %lld: an image has %lld elements", fn,
+                    (long long)p->pred_batch_stride, (long long)p->gt_batch_stride, (long long)pixels);
+    return VIVIM_OK;
+}
+
+size_t vivim_binary_metrics_workspace_bytes(const vivim_binary_metrics_params* p) {
+    if (check_binary_metrics(p, "binary_metrics_workspace_bytes") != VIVIM_OK) return 0;
+    return vivim::binary_metrics_workspace_bytes(*p);
+}
+
+int vivim_binary_metrics(const vivim_binary_metrics_params* p, void* stream) {
+    const char* fn = "binary_metrics";
+    if (int rc = check_binary_metrics(p, fn)) return rc;
+    if (p->pred == nullptr || !aligned(p->pred, elem_bytes(p->ptype)))
+        return fail(VIVIM_ERR_INVALID, "%s: pred at %p: need a %d-byte aligned pointer", fn, p->pred, elem_bytes(p->ptype));
+    const int gbytes = p->gtype == 3 ? 1 : elem_bytes(p->gtype);
+    if (p->gt == nullptr || !aligned(p->gt, gbytes))
+        return fail(VIVIM_ERR_INVALID, "%s: gt at %p: need a %d-byte aligned pointer", fn, p->gt, gbytes);
+    if (p->thresholds == nullptr || !aligned(p->thresholds, 4))
+        return fail(VIVIM_ERR_INVALID, "%s: thresholds at %p: need 256 fp32 thresholds at a 4-byte aligned pointer", fn, p->thresholds);
+    if (p->values == nullptr || !aligned(p->values, 8))
+        return fail(VIVIM_ERR_INVALID, "%s: values at %p: need an 8-byte aligned pointer to (batch, 9) fp64", fn, p->values);
+    if (p->hist != nullptr && !aligned(p->hist, 4))
+        return fail(VIVIM_ERR_INVALID, "%s: hist at %p: need NULL or a 4-byte aligned pointer", fn, p->hist);
+    if (p->state != nullptr && !aligned(p->state, 8))
+        return fail(VIVIM_ERR_INVALID, "%s: state at %p: need NULL or an 8-byte aligned pointer to 10 fp64", fn, p->state);
+    const size_t need = vivim::binary_metrics_workspace_bytes(*p);
+    if (int rc = check_workspace(fn, "vivim_binary_metrics_workspace_bytes", p->workspace, p->workspace_bytes, 8, need)) return rc;
+    if (!vivim::binary_metrics_dispatch(*p, as_stream(stream)))
+        return fail(VIVIM_ERR_UNSUPPORTED, "%s not implemented for type %d", fn, p->ptype);
+    return after_launch(fn);
+}
+
 }  // extern "C"

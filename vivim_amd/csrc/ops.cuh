@@ -8,6 +8,7 @@
 #include "det.cuh"
 #include "../../include/vivim_hip_ext.h"
 #include "../../include/vivim_hip_ext_head.h"
+#include "../../include/vivim_hip_ext_binary_metrics.h"
 
 namespace vivim {
 
@@ -84,6 +85,10 @@ int decode_head_max_hidden();
 // ---- the training head's upsample + dropout + concat: head_concat.hip
 bool head_concat_dispatch(const vivim_head_concat_params&, bool bwd, hipStream_t);
 int64_t head_concat_blocks(const vivim_head_concat_params&, bool bwd);
+
+// ---- validation metrics of the binary recipe: binary_metrics.hip
+bool binary_metrics_dispatch(const vivim_binary_metrics_params&, hipStream_t);
+size_t binary_metrics_workspace_bytes(const vivim_binary_metrics_params&);
 
 // ---- fused clip + AdamW step, plain and with fp32 masters: optimizer.hip
 void opt_grad_stats_launch(const vivim_opt_step_params&, hipStream_t);

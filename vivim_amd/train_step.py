@@ -258,3 +258,28 @@ def eval_step(model, clip, onehot, num_classes, tracker=None, amp_dtype=torch.bf
         if tracker is not None:
             tracker.update(logits, target)
     return loss.detach()
+
+
+def eval_step_binary(model, clip, mask, tracker=None, amp_dtype=torch.bfloat16, fused_loss=False, frames="center"):
+    """eval_step for the binary (one-channel) recipe: forward under no_grad + autocast, the structure loss (structure_loss, or
+    structure_loss_fused with `fused_loss=True`) on the selected frames -- "center" takes the middle frame of every clip, the
+    reference's `[nf // 2::nf]`, "all" every frame -- and, when a `tracker` (binary_metrics.BinaryMetricsTracker) is given, its
+    update with the binarised prediction `(sigmoid(logits) > 0.5).float()` and the mask, as the reference's validation step
+    collects them: launches on the device, no host synchronisation.  clip (B, nf, 3, H, W), mask (B, nf, 1, H, W) of zeros and
+    ones.  Returns the detached loss."""
+    from . import structure_loss as sl
+    assert frames in ("center", "all"), frames
+    check_autocast_dtype(model, amp_dtype)
+    if model.training:
+        model.eval()
+    with torch.no_grad():
+        with torch.autocast("cuda", dtype=amp_dtype, enabled=amp_dtype != torch.float32):
+            logits = model(clip)                               # (B*nf, 1, H, W)
+        nf = mask.shape[1]
+        target = mask.reshape(mask.shape[0] * nf, *mask.shape[2:])
+        if frames == "center":
+            logits, target = logits[nf // 2::nf], target[nf // 2::nf]
+        loss = (sl.structure_loss_fused if fused_loss else sl.structure_loss)(logits, target)
+        if tracker is not None:
+            tracker.update((torch.sigmoid(logits) > 0.5).float(), target)
+    return loss.detach()
