@@ -33,7 +33,7 @@ for st, (dim, stride) in enumerate(zip((64, 128, 320, 512), (4, 8, 16, 32))):
     xz = torch.randn(2 * D, B, L, device=dev).to(dt).transpose(0, 1)          # (B, 2D, L), strides (L, B*L, 1)
     o3 = torch.randn(B, 3, D, L, device=dev).to(dt)
     ts = timeit(lambda: dirmap._scatter(xz, nf, D, 1.0))
-    tg = timeit(lambda: dirmap._gather(o3.view(B, 1, 3, D, L), nf, 1.0 / 3.0))
+    tg = timeit(lambda: dirmap._gather(o3.view(B, 1, 3, D, L), nf, 1.0 / 3.0, channel_major=True))   # as combine_directions calls it
     tg2 = timeit(lambda: dirmap._gather(dirmap._scatter(xz, nf, D, 1.0), nf, 1.0))   # backward of stack_directions: (B, 2, 3, D, L)
     tot_s += ts
     tot_g += tg

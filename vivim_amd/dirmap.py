@@ -4,7 +4,7 @@
                                        [.., 0] = xz, [.., 1] = xz.flip(-1),
                                        [.., 2] = the frame interleave t*hw+p -> p*nf+t   (mamba_simple.py:231, 245-247)
     combine_directions(o3, nframes)    (B, 3, D, L) -> (B, D, L): (o3[:,0] + o3[:,1].flip(-1) + interleave^-1(o3[:,2])) / 3
-                                       (mamba_simple.py:261-264)
+                                       (mamba_simple.py:261-264), channel-major in memory too (see _gather)
 Each reads its input once; each is the other's gradient (up to the scale)."""
 import torch
 
@@ -36,12 +36,17 @@ def _scatter(flat, nframes, csplit, scale):
     return stacked
 
 
-def _gather(stacked, nframes, scale):
-    """stacked (B, H, 3, csplit, L), unit L stride -> flat (B, H * csplit, L) contiguous."""
+def _gather(stacked, nframes, scale, channel_major=False):
+    """stacked (B, H, 3, csplit, L), unit L stride -> flat (B, H * csplit, L): contiguous, or with `channel_major` the
+    permuted view of a (H * csplit, B, L) buffer (batch stride L), whose token-major transpose is a (B * L, channels)
+    matrix with unit row stride -- a transposed GEMM operand as it stands, not something to copy first."""
     if stacked.stride(-1) != 1:
         stacked = stacked.contiguous()
     B, H, _, csplit, L = stacked.shape
-    flat = _lib.empty((B, H * csplit, L), stacked.dtype, stacked.device)
+    if channel_major:
+        flat = _lib.empty((H * csplit, B, L), stacked.dtype, stacked.device).permute(1, 0, 2)
+    else:
+        flat = _lib.empty((B, H * csplit, L), stacked.dtype, stacked.device)
     _lib.launch("vivim_dir_gather", _params(flat, stacked, nframes, csplit, scale, stacked, flat), stacked.device)
     return flat
 
@@ -62,7 +67,9 @@ class _CombineFn(torch.autograd.Function):
     def forward(ctx, o3, nframes):
         ctx.nframes = nframes
         B, _, D, L = o3.shape
-        return _gather(o3.view(B, 1, 3, D, L), nframes, 1.0 / 3.0)
+        # channel-major like the sum of the three separate calls' outputs: out_proj then runs the same GEMMs, forward and
+        # weight gradient, on the same operand layout as the three-call composition, and F.linear has nothing to copy
+        return _gather(o3.view(B, 1, 3, D, L), nframes, 1.0 / 3.0, channel_major=True)
 
     @staticmethod
     def backward(ctx, g):
