@@ -1,12 +1,13 @@
 /* vivim_hip_ext.h -- entry points of libvivim_hip.so added after ABI version 8.
  *
- * include/vivim_hip.h is frozen at version 8: its structs, its functions, vivim_sizeof and vivim_abi_version() stay as they are.
- * This file holds the structure loss, the first addition since; a later feature declares its interface in a header of its own
- * (vivim_hip_ext_<feature>.h; vivim_amd/_lib.py: EXTENSIONS).  All are exported from the same library and bound by the same parser
- * (parse_header; this one into EXT_STRUCT_NAMES / EXT_ENTRY_POINTS), so this file is written in the same restricted C:
- * fixed-width fields, explicit padding, one `typedef struct { ... } vivim_*;` per params struct, plain function declarations.
- * Every struct declared here opens with `struct_bytes`: the caller sets it to sizeof of the struct as it compiled it, the
- * entry points refuse any other value, and there is no vivim_sizeof row.
+ * The first extension header, hence no feature in its name: it holds the structure loss.
+ * include/vivim_hip.h is frozen at ABI version 8: its structs, its functions, vivim_sizeof and
+ * vivim_abi_version() stay as they are.  A feature added after version 8 gets a header of its own, include/vivim_hip_ext_<feature>.h,
+ * a row in EXTENSIONS of vivim_amd/_lib.py, and a params struct that opens with `struct_bytes`: the caller sets it to sizeof of the
+ * struct as it compiled it, the entry points refuse any other value, and there is no vivim_sizeof row.  Every such header is
+ * exported from the same library, parsed by the same parser (parse_header) and bound by the same loop (lib()), so it is written in
+ * the same restricted C: fixed-width fields, explicit padding, one `typedef struct { ... } vivim_*;` per params struct, plain
+ * function declarations.
  *
  * The conventions of vivim_hip.h hold: every call returns VIVIM_OK or an error code with a message in vivim_last_error(),
  * checks its arguments on the host before any launch, and enqueues on `stream` (a hipStream_t) without synchronising. */

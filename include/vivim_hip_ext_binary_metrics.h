@@ -2,9 +2,13 @@
  * (dice, jaccard, precision, recall, F, specificity over 256 thresholds), S-measure, mean E-measure and MAE of a batch of
  * probability maps against their masks (csrc/binary_metrics.hip; vivim_amd/binary_metrics.py, whose docstring is the definition).
  *
- * A per-feature extension header like vivim_hip_ext_head.h: the same restricted C, exported from the same library and parsed by
- * the same parser (vivim_amd/_lib.py: parse_header).  Its binding table lives in the feature module, vivim_amd/binary_metrics.py,
- * not in _lib.EXTENSIONS.  The struct opens with `struct_bytes` and has no vivim_sizeof row.
+ * An extension header.  include/vivim_hip.h is frozen at ABI version 8: its structs, its functions, vivim_sizeof and
+ * vivim_abi_version() stay as they are.  A feature added after version 8 gets a header of its own, include/vivim_hip_ext_<feature>.h,
+ * a row in EXTENSIONS of vivim_amd/_lib.py, and a params struct that opens with `struct_bytes`: the caller sets it to sizeof of the
+ * struct as it compiled it, the entry points refuse any other value, and there is no vivim_sizeof row.  Every such header is
+ * exported from the same library, parsed by the same parser (parse_header) and bound by the same loop (lib()), so it is written in
+ * the same restricted C: fixed-width fields, explicit padding, one `typedef struct { ... } vivim_*;` per params struct, plain
+ * function declarations.
  *
  * The conventions of vivim_hip.h hold: every call returns VIVIM_OK or an error code with a message in vivim_last_error(),
  * checks its arguments on the host before any launch, and enqueues on `stream` (a hipStream_t) without synchronising. */

@@ -1,11 +1,12 @@
 /* vivim_hip_ext_head.h -- the training decode head's entry points of libvivim_hip.so: upsample + dropout + concat in one launch.
  *
- * A per-feature extension header.  include/vivim_hip.h is frozen at ABI version 8 and include/vivim_hip_ext.h holds the structure
- * loss alone; a feature added since declares its interface in a header of its own, named vivim_hip_ext_<feature>.h, exported from
- * the same library and bound by the same parser (vivim_amd/_lib.py: parse_header, through the EXTENSIONS registry).  The same
- * restricted C: fixed-width fields, no holes, one `typedef struct { ... } vivim_*;` per params struct, plain function declarations.
- * The struct opens with `struct_bytes` (sizeof of the struct as the caller compiled it; the entry points refuse any other value)
- * and has no vivim_sizeof row.
+ * An extension header.  include/vivim_hip.h is frozen at ABI version 8: its structs, its functions, vivim_sizeof and
+ * vivim_abi_version() stay as they are.  A feature added after version 8 gets a header of its own, include/vivim_hip_ext_<feature>.h,
+ * a row in EXTENSIONS of vivim_amd/_lib.py, and a params struct that opens with `struct_bytes`: the caller sets it to sizeof of the
+ * struct as it compiled it, the entry points refuse any other value, and there is no vivim_sizeof row.  Every such header is
+ * exported from the same library, parsed by the same parser (parse_header) and bound by the same loop (lib()), so it is written in
+ * the same restricted C: fixed-width fields, explicit padding, one `typedef struct { ... } vivim_*;` per params struct, plain
+ * function declarations.
  *
  * The conventions of vivim_hip.h hold: every call returns VIVIM_OK or an error code with a message in vivim_last_error(),
  * checks its arguments on the host before any launch, and enqueues on `stream` (a hipStream_t) without synchronising. */

@@ -1,25 +1,24 @@
-"""CPU: the binary recipe's validation metrics below the GPU.  include/vivim_hip_ext_binary_metrics.h parses into the feature
-module's own table and leaves every table of _lib as it was; the struct's layout is the C compiler's; the library exports the two
-symbols; every host-side refusal carries its message; the eager composition and binary_metrics_cases.restate64 reproduce the
+"""CPU: the binary recipe's validation metrics below the GPU.  include/vivim_hip_ext_binary_metrics.h parses into its row of
+_lib.EXTENSIONS (what the registry as a whole holds: test_abi_extensions.py); the struct's layout is the C compiler's; the library
+exports the two symbols; every host-side refusal carries its message; the eager composition and binary_metrics_cases.restate64 reproduce the
 fixtures written by the reference's own classes; the tracker and eval_step_binary on the CPU."""
 import ctypes
+import functools
 import os
-import subprocess
 
 import numpy as np
 import pytest
 import torch
 
 import binary_metrics_cases as bc
+from abi_cases import PTR, layout_matches_c, refused
 from conftest import ROOT
-from test_abi_header import _compiler
 from vivim_amd import _lib
 from vivim_amd import binary_metrics as bm
 
 HEADER = os.path.join(ROOT, "include", "vivim_hip_ext_binary_metrics.h")
 NAMES = ("vivim_binary_metrics_workspace_bytes", "vivim_binary_metrics")
-P = bm.BinaryMetricsParams
-PTR = 4096          # a 16-byte aligned non-null "address": nothing is launched, so nothing reads it
+P = _lib.BinaryMetricsParams
 FIELDS = ["struct_bytes", "batch", "height", "width", "ptype", "gtype", "pred_batch_stride", "gt_batch_stride", "pred", "gt",
           "thresholds", "values", "hist", "state", "workspace", "workspace_bytes"]
 FIXTURES = bc.fixtures()
@@ -36,51 +35,23 @@ def test_the_header_parses_into_one_struct_and_two_entries():
     ptr = ctypes.POINTER(classes["BinaryMetricsParams"])
     assert parsed[NAMES[0]] == _lib.Entry(None, (ptr,), False, ctypes.c_size_t)
     assert parsed[NAMES[1]] == _lib.Entry(None, (ptr,), True, ctypes.c_int)
-    assert tuple(bm.ENTRY_POINTS) == NAMES and bm.STRUCT_NAMES == {"vivim_binary_metrics_params": "BinaryMetricsParams"}
+    names, entries = _lib.EXTENSIONS["vivim_hip_ext_binary_metrics.h"]
+    assert names == {"vivim_binary_metrics_params": "BinaryMetricsParams"} and tuple(entries) == NAMES
+    assert entries == {NAMES[0]: _lib.Entry(None, (ctypes.POINTER(P),), False, ctypes.c_size_t),
+                       NAMES[1]: _lib.Entry(None, (ctypes.POINTER(P),), True, ctypes.c_int)}
     assert [n for n, _ in P._fields_] == FIELDS and ctypes.sizeof(P) == 104
     types = dict(P._fields_)
     assert types["pred_batch_stride"] is ctypes.c_int64 and types["thresholds"] is ctypes.c_void_p and types["gtype"] is ctypes.c_int32
 
 
-def test_the_tables_of_lib_are_what_they_were():
-    import test_abi_header as th
-    assert list(_lib.EXTENSIONS) == ["vivim_hip_ext.h", "vivim_hip_ext_head.h"]
-    assert _lib.ABI_VERSION == 8 and len(_lib.ENTRY_POINTS) == 53 and len(_lib.ALL_ENTRY_POINTS) == 53 + 3 + 2
-    assert len(_lib.STRUCT_NAMES) == 20 and len(_lib.STRUCTS) == 15 and _lib.EXPORTS == tuple(_lib.ENTRY_POINTS)
-    assert list(_lib.STRUCT_NAMES.values()) == list(th.LAYOUTS) and set(_lib.ENTRY_POINTS) == set(th.ENTRIES)
-    assert not set(NAMES) & set(_lib.ALL_ENTRY_POINTS) and not hasattr(_lib, "BinaryMetricsParams")
-    for header in ("vivim_hip.h", "vivim_hip_ext.h", "vivim_hip_ext_head.h"):
-        assert "binary_metrics" not in open(os.path.join(ROOT, "include", header)).read()
-
-
 def test_the_library_exports_the_two_symbols():
-    bm._bind()
     L = _lib.lib()
     assert getattr(L, NAMES[0]).argtypes == [ctypes.POINTER(P)] and getattr(L, NAMES[0]).restype is ctypes.c_size_t
     assert getattr(L, NAMES[1]).argtypes == [ctypes.POINTER(P), ctypes.c_void_p] and getattr(L, NAMES[1]).restype is ctypes.c_int
 
 
 def test_layout_matches_the_c_compiler(tmp_path):
-    """The generated-C method of test_abi_header.py::test_layouts_match_the_c_compiler, for this header."""
-    cc = _compiler()
-    if cc is None:
-        pytest.skip("no C compiler (neither cc nor the Makefile's hipcc)")
-    c_name = "vivim_binary_metrics_params"
-    lines = ["#include <stdio.h>", "#include <stddef.h>", '#include "vivim_hip_ext_binary_metrics.h"', "int main(void) {",
-             f'    printf("- %zu\\n", sizeof({c_name}));']
-    for field, _ in P._fields_:
-        lines.append(f'    printf("{field} %zu %zu\\n", offsetof({c_name}, {field}), sizeof((({c_name} *)0)->{field}));')
-    lines += ["    return 0;", "}"]
-    src, exe = tmp_path / "layout.c", tmp_path / "layout"
-    src.write_text("\n".join(lines) + "\n")
-    subprocess.run(cc + ["-I", os.path.dirname(HEADER), "-o", str(exe), str(src)], check=True, capture_output=True, text=True)
-    out = subprocess.run([str(exe)], check=True, capture_output=True, text=True).stdout.split("\n")
-    assert out[:-1] == [f"- {ctypes.sizeof(P)}"] + [f"{n} {getattr(P, n).offset} {getattr(P, n).size}" for n, _ in P._fields_]
-    end = 0
-    for n, _ in P._fields_:                                  # no holes
-        assert getattr(P, n).offset == end, n
-        end += getattr(P, n).size
-    assert ctypes.sizeof(P) == end
+    layout_matches_c("vivim_hip_ext_binary_metrics.h", "vivim_binary_metrics_params", P, tmp_path)
 
 
 # ---- refusals
@@ -98,23 +69,11 @@ def _good(**over):
     return p
 
 
-def _refused(p, code=1):
-    """The refusal of vivim_binary_metrics for `p`: its return code, and its text directly and through _lib.call; the workspace
-    query answers 0 for what it refuses itself."""
-    bm._bind()
-    L = _lib.lib()
-    assert L.vivim_binary_metrics(ctypes.byref(p) if p is not None else None, None) == code
-    direct = L.vivim_last_error().decode()
-    if p is not None:
-        with pytest.raises(RuntimeError) as info:
-            _lib.call("vivim_binary_metrics", p, 0)
-        assert str(info.value) == direct
-    assert direct
-    return direct
+# the refusal of vivim_binary_metrics for `p` (the workspace query answers 0 for what it refuses itself)
+_refused = functools.partial(refused, "vivim_binary_metrics")
 
 
 def test_refusals_before_any_launch():
-    bm._bind()
     L = _lib.lib()
     assert "binary_metrics: params is NULL" in _refused(None)
     assert "struct_bytes = 0, this library's vivim_binary_metrics_params has 104" in _refused(_good(struct_bytes=0))

@@ -1,19 +1,19 @@
-"""CPU: the training decode head's concat op below the GPU.  The per-feature extension header include/vivim_hip_ext_head.h parses into
-its own table and leaves every earlier table as it was; the struct's layout is the C compiler's; every host-side refusal of the two
-entry points, with its message, directly and through _lib.call; `supported` on CPU and meta tensors; the switch's keyword; on the
-CPU the switch changes neither a bit nor the RNG state; the stock composition against the fp64 reference; and the kernels'
-arithmetic restated in torch fp32 (head_concat_cases.restate32) held to the GPU test's bounds on the GPU test's inputs."""
+"""CPU: the training decode head's concat op below the GPU.  The extension header include/vivim_hip_ext_head.h parses into its row
+of _lib.EXTENSIONS (what the registry as a whole holds: test_abi_extensions.py); the struct's layout is the C compiler's; every
+host-side refusal of the two entry points, with its message, directly and through _lib.call; `supported` on CPU and meta tensors;
+the switch's keyword; on the CPU the switch changes neither a bit nor the RNG state; the stock composition against the fp64
+reference; and the kernels' arithmetic restated in torch fp32 (head_concat_cases.restate32) held to the GPU test's bounds on the GPU
+test's inputs."""
 import ctypes
 import inspect
 import os
-import subprocess
 
 import pytest
 import torch
 
 import head_concat_cases as hc
+from abi_cases import PTR, layout_matches_c, refused as _refused
 from conftest import ROOT
-from test_abi_header import _compiler
 from test_gpu_upsample import RHO
 from vivim_amd import _lib
 from vivim_amd import head_concat
@@ -21,8 +21,8 @@ from vivim_amd import head_concat
 HEAD_HEADER = os.path.join(ROOT, "include", "vivim_hip_ext_head.h")
 NAMES = ("vivim_head_concat_fwd", "vivim_head_concat_bwd")
 STRUCTURE_LOSS = ("vivim_structure_loss_workspace_bytes", "vivim_structure_loss_fwd", "vivim_structure_loss_bwd")
+BINARY_METRICS = ("vivim_binary_metrics_workspace_bytes", "vivim_binary_metrics")
 P = _lib.HeadConcatParams
-PTR = 4096          # a 16-byte aligned non-null "address": nothing is launched, so nothing reads it
 FIELDS = ["struct_bytes", "batch", "n_maps", "out_h", "out_w", "itype", "map_c", "map_h", "map_w", "chan_off", "scale",
           "map_batch_stride", "dmap_batch_stride", "keep_batch_stride", "out_batch_stride", "out_pixel_stride", "maps", "keep", "out",
           "dout", "dmaps"]
@@ -43,19 +43,9 @@ def test_the_header_parses_into_its_own_table():
     assert types["keep_batch_stride"] is ctypes.c_int64 * 4 and types["out_pixel_stride"] is ctypes.c_int64
     text = open(HEAD_HEADER).read()
     assert "#ifndef VIVIM_HIP_EXT_HEAD_H" in text and '#include "vivim_hip.h"' in text
-    assert list(_lib.EXTENSIONS) == ["vivim_hip_ext.h", "vivim_hip_ext_head.h"]
-    assert set(_lib.ALL_ENTRY_POINTS) == set(_lib.ENTRY_POINTS) | set(STRUCTURE_LOSS) | set(NAMES)
-
-
-def test_the_earlier_tables_are_what_they_were():
-    import test_abi_header as th
-    assert _lib.ABI_VERSION == 8 and len(_lib.ENTRY_POINTS) == 53 and len(_lib.STRUCT_NAMES) == 20 and len(_lib.STRUCTS) == 15
-    assert list(_lib.STRUCT_NAMES.values()) == list(th.LAYOUTS) and set(_lib.ENTRY_POINTS) == set(th.ENTRIES)
-    assert tuple(_lib.EXT_ENTRY_POINTS) == STRUCTURE_LOSS and _lib.EXT_STRUCT_NAMES == {"vivim_structure_loss_params": "StructureLossParams"}
-    assert _lib.EXTENSIONS["vivim_hip_ext.h"] == (_lib.EXT_STRUCT_NAMES, _lib.EXT_ENTRY_POINTS)
-    assert not set(NAMES) & (set(_lib.EXPORTS) | set(_lib.EXT_ENTRY_POINTS))
-    for header in ("vivim_hip.h", "vivim_hip_ext.h"):
-        assert "head_concat" not in open(os.path.join(ROOT, "include", header)).read()
+    assert list(_lib.EXTENSIONS) == ["vivim_hip_ext.h", "vivim_hip_ext_head.h", "vivim_hip_ext_binary_metrics.h"]
+    assert set(_lib.ALL_ENTRY_POINTS) == set(_lib.ENTRY_POINTS) | set(STRUCTURE_LOSS) | set(NAMES) | set(BINARY_METRICS)
+    assert len(_lib.ALL_ENTRY_POINTS) == 60
 
 
 def test_the_parser_admits_the_new_guard_and_nothing_else():
@@ -75,26 +65,7 @@ def test_the_library_exports_the_two_symbols():
 
 
 def test_layout_matches_the_c_compiler(tmp_path):
-    """The generated-C method of test_abi_header.py::test_layouts_match_the_c_compiler, for this header."""
-    cc = _compiler()
-    if cc is None:
-        pytest.skip("no C compiler (neither cc nor the Makefile's hipcc)")
-    c_name = "vivim_head_concat_params"
-    lines = ["#include <stdio.h>", "#include <stddef.h>", '#include "vivim_hip_ext_head.h"', "int main(void) {",
-             f'    printf("- %zu\\n", sizeof({c_name}));']
-    for field, _ in P._fields_:
-        lines.append(f'    printf("{field} %zu %zu\\n", offsetof({c_name}, {field}), sizeof((({c_name} *)0)->{field}));')
-    lines += ["    return 0;", "}"]
-    src, exe = tmp_path / "layout.c", tmp_path / "layout"
-    src.write_text("\n".join(lines) + "\n")
-    subprocess.run(cc + ["-I", os.path.dirname(HEAD_HEADER), "-o", str(exe), str(src)], check=True, capture_output=True, text=True)
-    out = subprocess.run([str(exe)], check=True, capture_output=True, text=True).stdout.split("\n")
-    assert out[:-1] == [f"- {ctypes.sizeof(P)}"] + [f"{n} {getattr(P, n).offset} {getattr(P, n).size}" for n, _ in P._fields_]
-    end = 0
-    for n, _ in P._fields_:                                  # no holes
-        assert getattr(P, n).offset == end, n
-        end += getattr(P, n).size
-    assert ctypes.sizeof(P) == end
+    layout_matches_c("vivim_hip_ext_head.h", "vivim_head_concat_params", P, tmp_path)
 
 
 # ---- refusals
@@ -118,19 +89,6 @@ def _good(**over):
         else:
             setattr(p, k, v)
     return p
-
-
-def _refused(name, p, code=1):
-    """The refusal of `name` for `p`: its return code directly, and its text both directly and through _lib.call."""
-    L = _lib.lib()
-    assert getattr(L, name)(ctypes.byref(p) if p is not None else None, None) == code
-    direct = L.vivim_last_error().decode()
-    if p is not None:
-        with pytest.raises(RuntimeError) as info:
-            _lib.call(name, p, 0)
-        assert str(info.value) == direct
-    assert direct
-    return direct
 
 
 @pytest.mark.parametrize("name", NAMES)

@@ -5,11 +5,11 @@ what it does not understand."""
 import ctypes
 import os
 import re
-import shutil
 import subprocess
 
 import pytest
 
+from abi_cases import compiler
 from conftest import ROOT
 from vivim_amd import _lib
 
@@ -288,21 +288,11 @@ def test_the_derived_tables_equal_the_mirrors_they_replaced():
     assert _lib.EXPORTS == tuple(_lib.ENTRY_POINTS)
 
 
-def _compiler():
-    cc = shutil.which("cc")
-    if cc:
-        return [cc]
-    makefile = open(os.path.join(ROOT, "vivim_amd", "csrc", "Makefile")).read()
-    m = re.search(r"^HIPCC\s*[?:]?=\s*(\S+)", makefile, flags=re.M)
-    hipcc = shutil.which(m[1] if m else "hipcc") or shutil.which("hipcc")
-    return [hipcc, "-x", "c"] if hipcc else None
-
-
 def test_layouts_match_the_c_compiler(tmp_path):
     """A C program generated from the parsed structs prints sizeof of every struct and offsetof / sizeof of every field as the
     compiler sees the header.  The field names come from the parse: a field it dropped leaves a gap in the offsets or the size,
     one it reordered or mistyped lands on another offset, one it invented does not compile."""
-    cc = _compiler()
+    cc = compiler()
     if cc is None:
         pytest.skip("no C compiler (neither cc nor the Makefile's hipcc)")
     lines = ["#include <stdio.h>", "#include <stddef.h>", '#include "vivim_hip.h"', "int main(void) {"]

@@ -1,13 +1,12 @@
-"""CPU: the structure loss below the GPU.  The extension header include/vivim_hip_ext.h parses into its own tables and leaves the
-version-8 tables as they were; the struct's layout is the C compiler's; every host-side refusal of the three entry points, with its
-message, through _lib.call and directly; the eager functions against the reference's formula written out per pixel in fp64 and
-against the fixtures the reference's own functions produced (tests/golden/structloss_*.npz); the kernels' arithmetic restated in
-torch fp32 (structure_loss_cases.restate32) held to the GPU test's bounds on the GPU test's inputs; and the CPU side of `supported`
-and of the `criterion` keyword."""
+"""CPU: the structure loss below the GPU.  The extension header include/vivim_hip_ext.h parses into its row of _lib.EXTENSIONS (what
+the registry as a whole holds: test_abi_extensions.py); the struct's layout is the C compiler's; every host-side refusal of the three
+entry points, with its message, through _lib.call and directly; the eager functions against the reference's formula written out per
+pixel in fp64 and against the fixtures the reference's own functions produced (tests/golden/structloss_*.npz); the kernels'
+arithmetic restated in torch fp32 (structure_loss_cases.restate32) held to the GPU test's bounds on the GPU test's inputs; and the
+CPU side of `supported` and of the `criterion` keyword."""
 import ctypes
 import inspect
 import os
-import subprocess
 
 import numpy as np
 import pytest
@@ -15,72 +14,44 @@ import torch
 import torch.nn.functional as F
 
 import structure_loss_cases as sc
+from abi_cases import PTR, layout_matches_c, refused as _refused
 from conftest import GOLDEN, ROOT
-from test_abi_header import _compiler
 from vivim_amd import _lib
 from vivim_amd import structure_loss as sl
 
-EXT_HEADER = os.path.join(ROOT, "include", "vivim_hip_ext.h")
+HEADER = os.path.join(ROOT, "include", "vivim_hip_ext.h")
 NAMES = ("vivim_structure_loss_workspace_bytes", "vivim_structure_loss_fwd", "vivim_structure_loss_bwd")
 P = _lib.StructureLossParams
-PTR = 4096          # a 16-byte aligned non-null "address": nothing is launched, so nothing reads it
 
 
 # ---- the header and the tables
 
 def test_the_extension_header_parses_into_its_own_tables():
-    consts, classes, entries = _lib.parse_header(open(EXT_HEADER).read(), _lib.EXT_STRUCT_NAMES)
+    struct_names, entry_points = _lib.EXTENSIONS["vivim_hip_ext.h"]
+    consts, classes, entries = _lib.parse_header(open(HEADER).read(), struct_names)
     assert consts == {} and list(classes) == ["StructureLossParams"] and tuple(entries) == NAMES
-    assert tuple(_lib.EXT_ENTRY_POINTS) == NAMES and _lib.EXT_STRUCT_NAMES == {"vivim_structure_loss_params": "StructureLossParams"}
+    assert tuple(entry_points) == NAMES and struct_names == {"vivim_structure_loss_params": "StructureLossParams"}
     size_t, c_int, ptr = ctypes.c_size_t, ctypes.c_int, ctypes.POINTER(P)
-    assert _lib.EXT_ENTRY_POINTS == {NAMES[0]: _lib.Entry(None, (ptr,), False, size_t), NAMES[1]: _lib.Entry(None, (ptr,), True, c_int),
-                                     NAMES[2]: _lib.Entry(None, (ptr,), True, c_int)}
+    assert entry_points == {NAMES[0]: _lib.Entry(None, (ptr,), False, size_t), NAMES[1]: _lib.Entry(None, (ptr,), True, c_int),
+                            NAMES[2]: _lib.Entry(None, (ptr,), True, c_int)}
     assert [n for n, _ in P._fields_] == [
         "struct_bytes", "batch", "classes", "height", "width", "itype", "ttype", "first_class", "eps", "_pad0", "logits_batch_stride",
         "logits_c_stride", "dlogits_batch_stride", "dlogits_c_stride", "target_batch_stride", "logits", "target", "loss", "coef",
         "workspace", "workspace_bytes", "grad_out", "dlogits"]
     assert ctypes.sizeof(P) == 144 and dict(P._fields_)["eps"] is ctypes.c_float
-    text = open(EXT_HEADER).read()
+    text = open(HEADER).read()
     assert "#ifndef VIVIM_HIP_EXT_H" in text and '#include "vivim_hip.h"' in text
-
-
-def test_the_version_8_tables_are_what_they_were():
-    import test_abi_header as th
-    assert _lib.ABI_VERSION == 8 and len(_lib.ENTRY_POINTS) == 53 and len(_lib.STRUCT_NAMES) == 20 and len(_lib.STRUCTS) == 15
-    assert list(_lib.STRUCT_NAMES.values()) == list(th.LAYOUTS) and [c.__name__ for c in _lib.STRUCTS] == th.STRUCTS
-    assert set(_lib.ENTRY_POINTS) == set(th.ENTRIES) and _lib.EXPORTS == tuple(_lib.ENTRY_POINTS)
-    assert not set(NAMES) & set(_lib.EXPORTS) and "StructureLossParams" not in _lib.STRUCT_NAMES.values()
-    assert "structure" not in open(os.path.join(ROOT, "include", "vivim_hip.h")).read()
 
 
 def test_the_library_exports_the_three_symbols():
     L = _lib.lib()
     for n in NAMES:
         fn = getattr(L, n)
-        assert fn.argtypes[0] is ctypes.POINTER(P) and fn.restype is _lib.EXT_ENTRY_POINTS[n].restype
+        assert fn.argtypes[0] is ctypes.POINTER(P) and fn.restype is _lib.ALL_ENTRY_POINTS[n].restype
 
 
 def test_layout_matches_the_c_compiler(tmp_path):
-    """The generated-C method of test_abi_header.py::test_layouts_match_the_c_compiler, for the extension header."""
-    cc = _compiler()
-    if cc is None:
-        pytest.skip("no C compiler (neither cc nor the Makefile's hipcc)")
-    c_name = "vivim_structure_loss_params"
-    lines = ["#include <stdio.h>", "#include <stddef.h>", '#include "vivim_hip_ext.h"', "int main(void) {",
-             f'    printf("- %zu\\n", sizeof({c_name}));']
-    for field, _ in P._fields_:
-        lines.append(f'    printf("{field} %zu %zu\\n", offsetof({c_name}, {field}), sizeof((({c_name} *)0)->{field}));')
-    lines += ["    return 0;", "}"]
-    src, exe = tmp_path / "layout.c", tmp_path / "layout"
-    src.write_text("\n".join(lines) + "\n")
-    subprocess.run(cc + ["-I", os.path.dirname(EXT_HEADER), "-o", str(exe), str(src)], check=True, capture_output=True, text=True)
-    out = subprocess.run([str(exe)], check=True, capture_output=True, text=True).stdout.split("\n")
-    assert out[:-1] == [f"- {ctypes.sizeof(P)}"] + [f"{n} {getattr(P, n).offset} {getattr(P, n).size}" for n, _ in P._fields_]
-    end = 0
-    for n, _ in P._fields_:                                  # explicit padding, no holes
-        assert getattr(P, n).offset == end, n
-        end += getattr(P, n).size
-    assert ctypes.sizeof(P) == end
+    layout_matches_c("vivim_hip_ext.h", "vivim_structure_loss_params", P, tmp_path)
 
 
 # ---- refusals
@@ -97,19 +68,6 @@ def _good(**over):
     if "workspace_bytes" not in over:
         p.workspace_bytes = _lib.lib().vivim_structure_loss_workspace_bytes(p)
     return p
-
-
-def _refused(name, p, code=1):
-    """The refusal of `name` for `p`: its return code directly, and its text both directly and through _lib.call."""
-    L = _lib.lib()
-    assert getattr(L, name)(ctypes.byref(p) if p is not None else None, None) == code
-    direct = L.vivim_last_error().decode()
-    if p is not None:
-        with pytest.raises(RuntimeError) as info:
-            _lib.call(name, p, 0)
-        assert str(info.value) == direct
-    assert direct
-    return direct
 
 
 @pytest.mark.parametrize("name", NAMES[1:])

@@ -1,13 +1,9 @@
-"""ctypes binding of libvivim_hip.so (C ABI: include/vivim_hip.h).
+"""ctypes binding of libvivim_hip.so (C ABI: include/vivim_hip.h, frozen at ABI version 8, and the extension headers next to it).
 
-The header is the one description of the ABI: it is parsed once, at import, into the params structs, the entry-point table
-and the constants below.  The parser refuses whatever it does not understand instead of guessing.  That header is frozen at
-ABI version 8; what was added since is declared in extension headers, one per feature (EXTENSIONS: include/vivim_hip_ext.h, parsed
-into EXT_STRUCT_NAMES and EXT_ENTRY_POINTS, and include/vivim_hip_ext_head.h), parsed the same way and exported from the same
-library: `call` and `launch` take a name of any table.
-
-The library is the product: if it is missing or fails to load this module raises -- there is no
-PyTorch/CPU fallback anywhere in vivim_amd.
+Each header is the one description of what it declares: parsed once, at import, into params structs, entry points and constants,
+by a parser that refuses whatever it does not understand instead of guessing.  A feature added after version 8 gets
+include/vivim_hip_ext_<feature>.h, a row in EXTENSIONS and a struct that opens with `struct_bytes`; `lib()` binds all tables in one
+loop.  The library is the product: if it is missing or fails to load this module raises -- no PyTorch/CPU fallback in vivim_amd.
 """
 import collections
 import ctypes
@@ -21,7 +17,6 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(_HERE, "csrc")
 SO_PATH = os.environ.get("VIVIM_LIB") or os.path.join(CSRC, "libvivim_hip.so")   # VIVIM_LIB: A/B builds
 HEADER = os.path.join(os.path.dirname(_HERE), "include", "vivim_hip.h")
-EXT_HEADER = os.path.join(os.path.dirname(_HERE), "include", "vivim_hip_ext.h")    # what was added after ABI version 8
 
 i32, i64, vp = ctypes.c_int32, ctypes.c_int64, ctypes.c_void_p
 
@@ -41,15 +36,10 @@ STRUCT_NAMES = {
     "vivim_token_add_norm_params": "TokenAddNormParams", "vivim_opt_step_params": "OptStepParams",
     "vivim_opt_mw_params": "OptMwParams",
 }
-# The same table for include/vivim_hip_ext.h.  vivim_hip.h is frozen at version 8 (and with it the tables derived from it below);
-# a struct added since is declared there, opens with `struct_bytes` and has no vivim_sizeof row.
-EXT_STRUCT_NAMES = {"vivim_structure_loss_params": "StructureLossParams"}
-# Every extension header, by file name under include/: (C struct -> Python class, entry points).  A feature added after the
-# structure loss brings a header of its own, vivim_hip_ext_<feature>.h; the entry points are filled in below, where the headers are parsed.
-EXTENSIONS = {
-    "vivim_hip_ext.h": (EXT_STRUCT_NAMES, {}),
-    "vivim_hip_ext_head.h": ({"vivim_head_concat_params": "HeadConcatParams"}, {}),
-}
+# The same table per extension header, by file name under include/ in the order added: (C struct -> Python class, entry points).
+EXTENSIONS = {"vivim_hip_ext.h": ({"vivim_structure_loss_params": "StructureLossParams"}, {}),
+              "vivim_hip_ext_head.h": ({"vivim_head_concat_params": "HeadConcatParams"}, {}),
+              "vivim_hip_ext_binary_metrics.h": ({"vivim_binary_metrics_params": "BinaryMetricsParams"}, {})}
 
 # One entry per exported function: its params struct (or None), the ctypes types of the arguments between `params` and
 # `stream` in the C signature, whether a stream comes last, and the restype.
@@ -63,8 +53,8 @@ _RESTYPES = {"int": ctypes.c_int, "size_t": ctypes.c_size_t, "const char *": cty
 _DIRECTIVES = r"\s*#\s*(include|define|ifndef\s+VIVIM_HIP(_[A-Z0-9]+)*_H|endif)\b"        # what may stand outside a struct
 
 
-def _refuse(what, text):
-    raise ValueError(f"vivim_hip.h: {what}: {' '.join(text.split())!r}")
+def _refuse(header, what, text):
+    raise ValueError(f"{header}: {what}: {' '.join(text.split())!r}")
 
 
 def _ctype(text):
@@ -72,13 +62,13 @@ def _ctype(text):
     return re.sub(r"\s*\*\s*", " *", " ".join(text.split()))
 
 
-def _declarator(text, table, context):
+def _declarator(text, table, context, header):
     """'const void *u' -> ('u', c_void_p), 'int32_t map_h[4]' -> ('map_h', c_int32 * 4), the type looked up in `table`."""
     m = re.fullmatch(r"([\w\s*]*?)(\w+)\s*(?:\[\s*(\d+)\s*\])?", text.strip())
     if not m:                                                           # a bit-field, a function pointer, ...
-        _refuse("cannot parse the declarator", context)
+        _refuse(header, "cannot parse the declarator", context)
     if _ctype(m[1]) not in table:
-        _refuse(f"unknown type {_ctype(m[1])!r}", context)
+        _refuse(header, f"unknown type {_ctype(m[1])!r}", context)
     ctype = table[_ctype(m[1])]
     return m[2], (ctype * int(m[3]) if m[3] else ctype)
 
@@ -87,10 +77,10 @@ def _has_sizeof_row(cls):
     return cls._fields_[0][0] != "struct_bytes"       # such a struct states its own sizeof and the entry point checks it
 
 
-def parse_header(text, names=STRUCT_NAMES):
+def parse_header(text, names=STRUCT_NAMES, header="vivim_hip.h"):
     """-> (constants, classes, entry points) of a header written like include/vivim_hip.h: the `#define VIVIM_* <int>` and
     enumerator values by name; one ctypes.Structure per `typedef struct { ... } vivim_*;`, by Python name in the order of
-    `names`; one Entry per function declaration, in header order.  ValueError on anything else: it never guesses."""
+    `names`; one Entry per function declaration, in header order.  ValueError naming `header` on anything else: it never guesses."""
     text = re.sub(r"/\*.*?\*/", " ", text, flags=re.S)
     consts = {k: int(v) for k, v in re.findall(r"^[ \t]*#[ \t]*define[ \t]+(VIVIM_\w+)[ \t]+(-?\d+)[ \t]*$", text, flags=re.M)}
     by_c_name = {}
@@ -98,22 +88,22 @@ def parse_header(text, names=STRUCT_NAMES):
     def struct(m):
         body, c_name = m[1], m[2]
         if "{" in body or "#" in body:
-            _refuse("nested braces or a preprocessor line in a struct", m[0])
+            _refuse(header, "nested braces or a preprocessor line in a struct", m[0])
         if c_name not in names:
-            _refuse("a struct without a Python name in STRUCT_NAMES", c_name)
+            _refuse(header, "a struct without a Python name in STRUCT_NAMES", c_name)
         types = {**_FIELD_TYPES, **by_c_name}                           # an earlier struct may be a field, by value
         fields = []
         for stmt in filter(None, (s.strip() for s in body.split(";"))):
-            base = re.match(r"(?:const\s+)?\w+", stmt) or _refuse("cannot parse the field", stmt)
+            base = re.match(r"(?:const\s+)?\w+", stmt) or _refuse(header, "cannot parse the field", stmt)
             first, *more = stmt.split(",")                              # `const void *u, *delta`: the stars belong to the names
             for decl in [first] + [f"{base[0]} {d}" for d in more]:
-                fields.append(_declarator(decl, types, stmt))
+                fields.append(_declarator(decl, types, stmt, header))
         by_c_name[c_name] = type(names[c_name], (ctypes.Structure,), {"_fields_": fields, "__module__": __name__})
         return " "
 
     def enum(m):
         for item in filter(None, (s.strip() for s in m[1].split(","))):
-            kv = re.fullmatch(r"(\w+)\s*=\s*(-?\d+)", item) or _refuse("cannot parse the enumerator", item)
+            kv = re.fullmatch(r"(\w+)\s*=\s*(-?\d+)", item) or _refuse(header, "cannot parse the enumerator", item)
             consts[kv[1]] = int(kv[2])
         return " "
 
@@ -121,18 +111,18 @@ def parse_header(text, names=STRUCT_NAMES):
     text = re.sub(r"(?:typedef\s+)?enum\s*\{([^{}]*)\}\s*\w*\s*;", enum, text)
     missing = [c for c in names if c not in by_c_name]
     if missing:
-        _refuse("STRUCT_NAMES names structs the header does not have", ", ".join(missing))
+        _refuse(header, "STRUCT_NAMES names structs the header does not have", ", ".join(missing))
     text = re.sub(r"^[ \t]*#[ \t]*ifdef[ \t]+__cplusplus\b.*?^[ \t]*#[ \t]*endif\b", " ", text, flags=re.S | re.M)   # extern "C"
     for line in re.findall(r"^[ \t]*#.*$", text, flags=re.M):
         if not re.match(_DIRECTIVES, line):
-            _refuse("a preprocessor line it does not know", line)
+            _refuse(header, "a preprocessor line it does not know", line)
     text = re.sub(r"^[ \t]*#.*$", " ", text, flags=re.M)
 
     entries = {}
     for decl in filter(None, (s.strip() for s in text.split(";"))):     # what is left: function declarations
-        m = re.fullmatch(r"([\w\s*]+?)(\w+)\s*\(([\w\s*,]*)\)", decl) or _refuse("cannot parse the declaration", decl)
+        m = re.fullmatch(r"([\w\s*]+?)(\w+)\s*\(([\w\s*,]*)\)", decl) or _refuse(header, "cannot parse the declaration", decl)
         if _ctype(m[1]) not in _RESTYPES:
-            _refuse(f"unknown return type {_ctype(m[1])!r}", decl)
+            _refuse(header, f"unknown return type {_ctype(m[1])!r}", decl)
         args = [] if m[3].strip() == "void" else [a.strip() for a in m[3].split(",")]
         stream = bool(args) and re.fullmatch(r"void\s*\*\s*stream", args[-1]) is not None
         args = args[:-1] if stream else args
@@ -140,9 +130,9 @@ def parse_header(text, names=STRUCT_NAMES):
         for k, arg in enumerate(args):
             p = re.fullmatch(r"const\s+(vivim_\w+)\s*\*\s*\w+", arg) if k == 0 else None
             if not p:
-                extra.append(_declarator(arg, _ARG_TYPES, decl)[1])
+                extra.append(_declarator(arg, _ARG_TYPES, decl, header)[1])
             elif p[1] not in by_c_name:
-                _refuse(f"unknown struct {p[1]}", decl)
+                _refuse(header, f"unknown struct {p[1]}", decl)
             elif _has_sizeof_row(by_c_name[p[1]]):
                 params = by_c_name[p[1]]
             else:
@@ -160,6 +150,23 @@ def _read_header(path=None):
         raise ImportError(f"{path} cannot be read ({e}): the binding is derived from it") from e
 
 
+def load_extensions(extensions, include_dir, taken_entries, taken_classes):
+    """Parse every header of `extensions` (a table like EXTENSIONS) under `include_dir`, fill in each row's entry points, return
+    (classes, entry points) of all rows.  ImportError naming the file: a struct that does not open with `struct_bytes`, a name taken."""
+    classes, entries = {}, {}
+    for file, (names, own) in extensions.items():
+        _, new, parsed = parse_header(_read_header(os.path.join(include_dir, file)), names, file)
+        bad = [f"{n} does not open with struct_bytes" for n, c in new.items() if _has_sizeof_row(c)]
+        bad += [f"another header already declares {n}" for n in parsed if n in taken_entries or n in entries]
+        bad += [f"the name {n} is already taken" for n in new if n in taken_classes or n in classes]
+        if bad:
+            raise ImportError(f"{file}: {'; '.join(bad)}")
+        own.update(parsed)
+        entries.update(parsed)
+        classes.update(new)
+    return classes, entries
+
+
 _consts, _classes, ENTRY_POINTS = parse_header(_read_header())
 globals().update(_classes)                              # SsmFwdParams ... OptMwParams, the classes STRUCT_NAMES names
 STRUCTS = tuple(c for c in _classes.values() if _has_sizeof_row(c))    # in vivim_sizeof order
@@ -167,17 +174,9 @@ EXPORTS = tuple(ENTRY_POINTS)
 ABI_VERSION = _consts["VIVIM_ABI_VERSION"]
 F32, F16, BF16 = _consts["VIVIM_F32"], _consts["VIVIM_F16"], _consts["VIVIM_BF16"]
 OPT_CHUNK, OPT_MAX_TENSORS, OPT_STATE_WORDS = (_consts["VIVIM_OPT_" + n] for n in ("CHUNK", "MAX_TENSORS", "STATE_WORDS"))
-ALL_ENTRY_POINTS = dict(ENTRY_POINTS)                    # every table: what lib() binds and `call` takes
-for _file, (_names, _entries) in EXTENSIONS.items():
-    _path = os.path.join(os.path.dirname(HEADER), _file)
-    _, _ext_classes, _parsed = parse_header(_read_header(_path), _names)
-    if any(_has_sizeof_row(c) for c in _ext_classes.values()) or set(_parsed) & set(ALL_ENTRY_POINTS) \
-            or set(_ext_classes) & set(globals()):
-        raise ImportError(f"{_path}: a struct that does not open with struct_bytes, or a name another header already declares")
-    _entries.update(_parsed)
-    ALL_ENTRY_POINTS.update(_parsed)
-    globals().update(_ext_classes)                      # StructureLossParams, HeadConcatParams
-EXT_ENTRY_POINTS = EXTENSIONS[os.path.basename(EXT_HEADER)][1]         # the structure-loss table
+_classes, _entries = load_extensions(EXTENSIONS, os.path.dirname(HEADER), ENTRY_POINTS, globals())
+globals().update(_classes)                              # StructureLossParams, HeadConcatParams, BinaryMetricsParams
+ALL_ENTRY_POINTS = {**ENTRY_POINTS, **_entries}         # every table: what lib() binds and `call` takes
 
 _lib = None
 

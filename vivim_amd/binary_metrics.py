@@ -43,36 +43,17 @@ Tracker.  `state` is fp64 (10,): the sums of the nine values over the images see
 Additive across batches and ranks (all_reduce it) and bit-repeatable: the device path has no float atomics and adds its partial
 sums in a fixed order.  get_results() returns the nine means under the names the reference logs."""
 import ctypes
-import os
 
 import numpy as np
 import torch
 
 from . import _lib
-from ._lib import ITYPE
+from ._lib import ITYPE, BinaryMetricsParams
 
 VALUES = ("Dice", "Jaccard", "Precision", "Recall", "Fmeasure", "specificity", "Smeasure", "Emeasure", "MAE")
-HEADER = os.path.join(os.path.dirname(_lib.HEADER), "vivim_hip_ext_binary_metrics.h")
-STRUCT_NAMES = {"vivim_binary_metrics_params": "BinaryMetricsParams"}
-# This feature owns its binding table: _lib's tables (EXTENSIONS, ALL_ENTRY_POINTS, ...) are pinned by the ABI tests at what they
-# held before it, so the header is parsed here, by the same parser, and the two symbols are bound on first use.
-_, _classes, ENTRY_POINTS = _lib.parse_header(_lib._read_header(HEADER), STRUCT_NAMES)
-BinaryMetricsParams = _classes["BinaryMetricsParams"]
 _GTYPE = {**ITYPE, torch.uint8: 3, torch.bool: 3}
 _EPS = float(np.spacing(1))
-_bound = False
 _thresholds = {}
-
-
-def _bind():
-    global _bound
-    if not _bound:
-        L = _lib.lib()
-        for name, e in ENTRY_POINTS.items():
-            fn = getattr(L, name)
-            fn.argtypes = ([ctypes.POINTER(e.struct)] if e.struct else []) + list(e.extra) + ([_lib.vp] if e.stream else [])
-            fn.restype = e.restype
-        _bound = True
 
 
 def thresholds(device):
@@ -197,7 +178,6 @@ def _eager(pred, gt, return_hist):
 
 
 def _run(pred, gt, return_hist, state):
-    _bind()
     N, H, W = pred.shape
     dev = pred.device
     P = BinaryMetricsParams()

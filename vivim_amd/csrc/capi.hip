@@ -1,4 +1,5 @@
-// capi.hip -- the extern "C" boundary of libvivim_hip.so (see include/vivim_hip.h).
+// capi.hip -- the extern "C" boundary of libvivim_hip.so (see include/vivim_hip.h, frozen at ABI version 8, and one
+// include/vivim_hip_ext_<feature>.h per feature added since).
 // Host-side checks mirror the TORCH_CHECKs of the reference bindings that still make sense below the
 // tensor layer (selective_scan.cpp:233-304, 352-438; causal_conv1d.cpp:135-163, 198-238).
 #include <hip/hip_runtime.h>
@@ -860,7 +861,7 @@ int vivim_opt_adamw_mw(const vivim_opt_mw_params* p, void* stream) {
     return after_launch(fn);
 }
 
-// ---- include/vivim_hip_ext.h: what was added after ABI version 8 ----
+// ---- include/vivim_hip_ext.h: the structure loss, the first feature added after ABI version 8 ----
 
 static bool structure_loss_sizes_ok(const vivim_structure_loss_params* p) {
     return p->batch > 0 && p->classes > 0 && p->height > 0 && p->width > 0;

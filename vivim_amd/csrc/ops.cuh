@@ -6,6 +6,7 @@
 // kernel is built for the call's types (capi has refused those, so this is a second line), a *_det_dispatch a Launch (det.cuh).
 #pragma once
 #include "det.cuh"
+// every extension header: one per feature added after ABI version 8, each includes vivim_hip.h
 #include "../../include/vivim_hip_ext.h"
 #include "../../include/vivim_hip_ext_head.h"
 #include "../../include/vivim_hip_ext_binary_metrics.h"
