@@ -29,6 +29,10 @@ def __getattr__(name):
     if name in ("FusedStepAdamW", "lower_params", "raise_params"):   # the device-side clip + AdamW step (optimizer.py), likewise
         from . import optimizer
         return getattr(optimizer, name)
+    # checkpoint, exact resume and the cosine schedule (checkpoint.py), likewise
+    if name in ("CosineSchedule", "TrainState", "save_checkpoint", "load_checkpoint", "load_model_weights"):
+        from . import checkpoint
+        return getattr(checkpoint, name)
     # the structure loss (structure_loss.py), likewise.  `vivim_amd.structure_loss` itself is that module, so the eager binary
     # form is reached as vivim_amd.structure_loss.structure_loss
     if name in ("multiclass_structure_loss", "structure_loss_fused", "multiclass_structure_loss_fused"):
