@@ -18,8 +18,7 @@
 //   5 bm_state_kernel     state[k] += values[n][k] for n ascending
 // No float atomics; fp64 partial sums meet in a fixed order (xor butterfly inside a wave, waves in order, slots in order).  A
 // thread owns E consecutive pixels (16 bytes of pred) per step and loads them as vectors where the address allows.
-#include "ops.cuh"
-#include "common.cuh"
+#include "capi.cuh"
 
 namespace vivim {
 
@@ -58,7 +57,7 @@ static BmLayout bm_layout(const vivim_binary_metrics_params& p) {
     return L;
 }
 
-size_t binary_metrics_workspace_bytes(const vivim_binary_metrics_params& p) { return bm_layout(p).total; }
+static size_t binary_metrics_workspace_bytes(const vivim_binary_metrics_params& p) { return bm_layout(p).total; }
 
 // what the kernels get besides the params: the parts of the workspace
 struct BmWs {
@@ -453,7 +452,7 @@ template <typename T> static void bm_launch(const vivim_binary_metrics_params& p
     if (p.state) hipLaunchKernelGGL(bm_state_kernel, dim3(1), dim3(kWave), 0, stream, p);
 }
 
-bool binary_metrics_dispatch(const vivim_binary_metrics_params& p, hipStream_t stream) {
+static bool binary_metrics_dispatch(const vivim_binary_metrics_params& p, hipStream_t stream) {
     const BmLayout L = bm_layout(p);
     char* base = static_cast<char*>(p.workspace);
     BmWs w;
@@ -466,3 +465,54 @@ bool binary_metrics_dispatch(const vivim_binary_metrics_params& p, hipStream_t s
 }
 
 }  // namespace vivim
+
+// ---- the C entry points
+// every refusal that needs no workspace, before any launch; `fn` names the caller in the message
+static int check_binary_metrics(const vivim_binary_metrics_params* p, const char* fn) {
+    if (p == nullptr) return fail(VIVIM_ERR_INVALID, "%s: params is NULL", fn);
+    if (int rc = check_struct_bytes(fn, "vivim_binary_metrics_params", p->struct_bytes, sizeof(*p))) return rc;
+    if (!dtype_ok(p->ptype)) return fail(VIVIM_ERR_INVALID, "%s: ptype = %d: pred is fp32 / fp16 / bf16 (0 / 1 / 2)", fn, p->ptype);
+    if (!dtype_ok(p->gtype) && p->gtype != 3)
+        return fail(VIVIM_ERR_INVALID, "%s: gtype = %d: gt is fp32 / fp16 / bf16 (0 / 1 / 2) or uint8 / bool (3)", fn, p->gtype);
+    if (p->batch <= 0 || p->height <= 0 || p->width <= 0)
+        return fail(VIVIM_ERR_INVALID, "%s: batch = %d, height = %d, width = %d: every size must be positive", fn, p->batch, p->height, p->width);
+    const int64_t pixels = (int64_t)p->height * p->width;
+    if (pixels < 2) return fail(VIVIM_ERR_INVALID, "%s: height * width = %lld: the metrics need at least 2 pixels", fn, (long long)pixels);
+    // the kernels index inside an image and build their grid with 32-bit integers (a thread counts up to 8 pixels past the end)
+    if (pixels > INT32_MAX - 4096 || (int64_t)p->batch * vivim::kBmMaxBlocks > INT32_MAX)
+        return fail(VIVIM_ERR_INVALID, "%s: batch = %d, height * width = %lld: the index range overflows int32", fn, p->batch, (long long)pixels);
+    if (p->pred_batch_stride < pixels || p->gt_batch_stride < pixels)
+        return fail(VIVIM_ERR_INVALID, "%s: pred_batch_stride = %lld, gt_batch_stride = %lld: an image has %lld elements", fn,
+                    (long long)p->pred_batch_stride, (long long)p->gt_batch_stride, (long long)pixels);
+    return VIVIM_OK;
+}
+
+extern "C" {
+
+size_t vivim_binary_metrics_workspace_bytes(const vivim_binary_metrics_params* p) {
+    if (check_binary_metrics(p, "binary_metrics_workspace_bytes") != VIVIM_OK) return 0;
+    return vivim::binary_metrics_workspace_bytes(*p);
+}
+
+int vivim_binary_metrics(const vivim_binary_metrics_params* p, void* stream) {
+    const char* fn = "binary_metrics";
+    if (int rc = check_binary_metrics(p, fn)) return rc;
+    if (p->pred == nullptr || !aligned(p->pred, elem_bytes(p->ptype)))
+        return fail(VIVIM_ERR_INVALID, "%s: pred at %p: need a %d-byte aligned pointer", fn, p->pred, elem_bytes(p->ptype));
+    const int gbytes = p->gtype == 3 ? 1 : elem_bytes(p->gtype);
+    if (p->gt == nullptr || !aligned(p->gt, gbytes))
+        return fail(VIVIM_ERR_INVALID, "%s: gt at %p: need a %d-byte aligned pointer", fn, p->gt, gbytes);
+    if (p->thresholds == nullptr || !aligned(p->thresholds, 4))
+        return fail(VIVIM_ERR_INVALID, "%s: thresholds at %p: need 256 fp32 thresholds at a 4-byte aligned pointer", fn, p->thresholds);
+    if (p->values == nullptr || !aligned(p->values, 8))
+        return fail(VIVIM_ERR_INVALID, "%s: values at %p: need an 8-byte aligned pointer to (batch, 9) fp64", fn, p->values);
+    if (p->hist != nullptr && !aligned(p->hist, 4))
+        return fail(VIVIM_ERR_INVALID, "%s: hist at %p: need NULL or a 4-byte aligned pointer", fn, p->hist);
+    if (p->state != nullptr && !aligned(p->state, 8))
+        return fail(VIVIM_ERR_INVALID, "%s: state at %p: need NULL or an 8-byte aligned pointer to 10 fp64", fn, p->state);
+    const size_t need = vivim::binary_metrics_workspace_bytes(*p);
+    if (int rc = check_workspace(fn, "vivim_binary_metrics_workspace_bytes", p->workspace, p->workspace_bytes, 8, need)) return rc;
+    return after_dispatch(vivim::binary_metrics_dispatch(*p, as_stream(stream)), fn, "%s not implemented for type %d", fn, p->ptype);
+}
+
+}  // extern "C"

@@ -11,11 +11,14 @@
 //   * conv1d_{fwd,bwd}_kernel: everything else (ragged or unaligned rows, rows of one tile: stage 3's 320 tokens).  One
 //     tile per wave; halos move between neighbouring lanes with wave shuffles, the two lanes at the wave edges fetch
 //     theirs with guarded scalar loads.
-#include "ops.cuh"
+#include "capi.cuh"
+#include "conv1d_cl.cuh"
 
 namespace vivim {
 
 constexpr int kConvThreads = 256;
+// causal_conv1d.cpp:151: is_channel_last = x.stride(1) == 1 && x.stride(2) > 1; such tensors go to conv1d_cl.hip
+static bool conv_channel_last(const vivim_conv_fwd_params& f) { return f.x_c_stride == 1 && f.x_l_stride > 1; }
 
 // Which (channel, tile) a wave works on.  Long rows: the workgroup's four waves take four consecutive 64*E-token tiles of
 // the row blockIdx.y.  PACK (rows shorter than four tiles -- Vivim's stages 2 and 3: 1280 and 320 tokens): the waves of
@@ -481,11 +484,11 @@ static size_t conv_bwd_det_slots(const vivim_conv_fwd_params& f) {
     return (size_t)g.x * g.z;
 }
 // A slot holds dweight (dim, width), then dbias (dim).
-size_t conv_bwd_det_workspace_bytes(const vivim_conv_fwd_params& f) {
+static size_t conv_bwd_det_workspace_bytes(const vivim_conv_fwd_params& f) {
     return sizeof(float) * conv_bwd_det_slots(f) * (size_t)f.dim * (f.width + 1);
 }
 // The deterministic protocol (det.cuh): the slot workspace is refused before anything is launched.
-Launch conv_bwd_det_dispatch(const vivim_conv_bwd_params& p, void* ws, size_t bytes, hipStream_t s) {
+static Launch conv_bwd_det_dispatch(const vivim_conv_bwd_params& p, void* ws, size_t bytes, hipStream_t s) {
     const vivim_conv_fwd_params& f = p.f;
     if (!det_ws_ok(ws, bytes, conv_bwd_det_workspace_bytes(f))) return Launch::bad_workspace;
     vivim_conv_bwd_params d = p;
@@ -502,13 +505,72 @@ Launch conv_bwd_det_dispatch(const vivim_conv_bwd_params& p, void* ws, size_t by
     return Launch::ok;
 }
 
-bool conv_fwd_dispatch(const vivim_conv_fwd_params& p, hipStream_t s) {
+static bool conv_fwd_dispatch(const vivim_conv_fwd_params& p, hipStream_t s) {
     if (conv_channel_last(p)) return conv_cl_fwd_dispatch(p, s);
     return with_conv_types(p, [&](auto t, auto w) { launch_conv_fwd<decltype(t), decltype(w)>(p, s); });
 }
-bool conv_bwd_dispatch(const vivim_conv_bwd_params& p, hipStream_t s) {
+static bool conv_bwd_dispatch(const vivim_conv_bwd_params& p, hipStream_t s) {
     if (conv_channel_last(p.f)) return conv_cl_bwd_dispatch(p, s);
     return with_conv_types(p.f, [&](auto t, auto w) { launch_conv_bwd<decltype(t), decltype(w)>(p, s); });
 }
 
 }  // namespace vivim
+
+// ---- the C entry points.  The checks mirror the TORCH_CHECKs of the reference binding that still make sense below the
+// tensor layer (causal_conv1d.cpp:135-163, 198-238).
+using vivim::conv_channel_last;
+
+static int check_conv(const vivim_conv_fwd_params* p) {
+    VCHECK(p != nullptr);
+    VCHECK(dtype_ok(p->itype) && dtype_ok(p->wtype));
+    VCHECK(p->batch > 0 && p->dim > 0 && p->seqlen > 0);
+    VCHECK(p->batch <= 65535 && p->dim <= 65535);
+    if (!(p->width >= 2 && p->width <= 4))          // causal_conv1d.cpp:157
+        return fail(VIVIM_ERR_INVALID, "causal_conv1d only supports width between 2 and 4");
+    VCHECK(p->x && p->weight);
+    if (p->x_l_stride != 1 && p->x_c_stride != 1)   // causal_conv1d.cpp:151-152
+        return fail(VIVIM_ERR_INVALID, "causal_conv1d: x must have unit stride along seqlen or along channels");
+    return VIVIM_OK;
+}
+
+static int check_conv_bwd(const vivim_conv_bwd_params* p) {
+    VCHECK(p != nullptr);
+    if (int rc = check_conv(&p->f)) return rc;
+    VCHECK(p->dout && p->dx && p->dweight);
+    const bool cl = conv_channel_last(p->f);
+    if (cl) { VCHECK(p->dout_c_stride == 1 && p->dx_c_stride == 1); }      // causal_conv1d.cpp:221, 237
+    else    { VCHECK(p->dout_l_stride == 1 && p->dx_l_stride == 1); }      // causal_conv1d.cpp:220, 236
+    VCHECK((p->f.bias == nullptr) == (p->dbias == nullptr));
+    return VIVIM_OK;
+}
+
+extern "C" {
+
+int vivim_causal_conv1d_fwd(const vivim_conv_fwd_params* p, void* stream) {
+    if (int rc = check_conv(p)) return rc;
+    VCHECK(p->out != nullptr);
+    const bool cl = conv_channel_last(*p);
+    if (cl) { VCHECK(p->out_c_stride == 1); } else { VCHECK(p->out_l_stride == 1); }
+    return after_dispatch(vivim::conv_fwd_dispatch(*p, as_stream(stream)), "causal_conv1d_fwd",
+                          "causal_conv1d_fwd not implemented for input type %d / weight type %d", p->itype, p->wtype);
+}
+
+size_t vivim_causal_conv1d_bwd_det_workspace_bytes(const vivim_conv_fwd_params* f) {
+    return check_conv(f) == VIVIM_OK ? vivim::conv_bwd_det_workspace_bytes(*f) : 0;
+}
+
+int vivim_causal_conv1d_bwd_det(const vivim_conv_bwd_params* p, void* det_ws, size_t det_ws_bytes, void* stream) {
+    if (int rc = check_conv_bwd(p)) return rc;
+    const size_t need = vivim::conv_bwd_det_workspace_bytes(p->f);
+    return after_det_dispatch(vivim::conv_bwd_det_dispatch(*p, det_ws, det_ws_bytes, as_stream(stream)), "causal_conv1d_bwd_det",
+                              "vivim_causal_conv1d_bwd_det_workspace_bytes", det_ws, det_ws_bytes, need,
+                              "causal_conv1d_bwd_det not implemented for input type %d / weight type %d", p->f.itype, p->f.wtype);
+}
+
+int vivim_causal_conv1d_bwd(const vivim_conv_bwd_params* p, void* stream) {
+    if (int rc = check_conv_bwd(p)) return rc;
+    return after_dispatch(vivim::conv_bwd_dispatch(*p, as_stream(stream)), "causal_conv1d_bwd",
+                          "causal_conv1d_bwd not implemented for input type %d / weight type %d", p->f.itype, p->f.wtype);
+}
+
+}  // extern "C"

@@ -7,7 +7,7 @@
 // tokens, keeps the last three rows of its channels in registers as the sliding window and walks its chunk row by row.
 // Every row access of a wave is one contiguous run of 64 * E elements; there is no shared memory and no barrier.  The halo
 // costs three extra rows per chunk (forward) or six (backward).  Not on Vivim's path (its x has unit seqlen stride).
-#include "ops.cuh"
+#include "conv1d_cl.cuh"
 
 namespace vivim {
 

@@ -20,7 +20,7 @@
 // per chunk instead of one per map) costs 187 VGPRs, two waves per SIMD, and ran slower, 180 us: the kernel is not bound by
 // the latency of a round trip.  12 of a pixel's 13 taps come from L2 (64 x 12 rows per tile where the tile's footprint is 38);
 // staging that footprint in LDS is the open experiment.
-#include "ops.cuh"
+#include "capi.cuh"
 #include "seg_load.cuh"
 #include "up_tap.cuh"
 
@@ -29,7 +29,7 @@ namespace vivim {
 constexpr int kDhWaves = 4;
 constexpr int kDhThreads = kDhWaves * kWave;
 constexpr int kDhTile = 8;               // output pixels per tile edge; wave w owns rows w and w + 4
-constexpr int kDhMaxHidden = 1024;       // capi.hip refuses more
+constexpr int kDhMaxHidden = 1024;       // check_decode_head refuses more
 constexpr int kDhMaxClasses = 8;
 
 struct DhRatios {
@@ -142,12 +142,10 @@ __global__ void __launch_bounds__(kDhThreads) decode_head_kernel(const vivim_dec
 }
 
 // ---- host ---------------------------------------------------------------------------------------------------------------------
-// workgroups of the launch (the capi check keeps it within a 31-bit grid)
-int64_t decode_head_blocks(const vivim_decode_head_params& p) {
+// workgroups of the launch (check_decode_head keeps it within a 31-bit grid)
+static int64_t decode_head_blocks(const vivim_decode_head_params& p) {
     return (int64_t)p.batch * ((p.out_h + kDhTile - 1) / kDhTile) * ((p.out_w + kDhTile - 1) / kDhTile);
 }
-
-int decode_head_max_hidden() { return kDhMaxHidden; }
 
 // whether the maps may be read in 16-byte vectors: hidden a whole number of them, every base and batch stride aligned
 static bool dh_vec(const vivim_decode_head_params& p, int64_t elem) {
@@ -175,8 +173,49 @@ static void dh_launch(const vivim_decode_head_params& p, hipStream_t stream) {
     else dh_launch_e<T, 1>(p, r, stream);
 }
 
-bool decode_head_dispatch(const vivim_decode_head_params& p, hipStream_t stream) {
+static bool decode_head_dispatch(const vivim_decode_head_params& p, hipStream_t stream) {
     return with_itype(p.itype, [&](auto t) { dh_launch<decltype(t)>(p, stream); });
 }
 
 }  // namespace vivim
+
+// ---- the C entry point
+// every refusal of the fused decode head, before any launch
+static int check_decode_head(const vivim_decode_head_params* p) {
+    using vivim::kDhMaxHidden;
+    VCHECK(p != nullptr);
+    if (int rc = check_struct_bytes("decode_head_fwd", "vivim_decode_head_params", p->struct_bytes, sizeof(*p))) return rc;
+    VCHECK(dtype_ok(p->itype));
+    VCHECK(p->batch > 0 && p->hidden > 0 && p->classes > 0 && p->out_h > 0 && p->out_w > 0);
+    VCHECK(p->n_maps >= 1 && p->n_maps <= 4);
+    static_assert(vivim::kDhMaxClasses == 8, "the next check words the kernel's limit");
+    VCHECK(p->classes <= 8);
+    if (p->hidden > kDhMaxHidden)
+        return fail(VIVIM_ERR_INVALID, "decode_head_fwd: hidden = %d: bias and w_out are kept in LDS, which holds up to %d channels",
+                    p->hidden, kDhMaxHidden);
+    const uintptr_t ib = elem_bytes(p->itype);
+    // the kernel indexes inside an image, and builds its grid, with 32-bit integers
+    VCHECK((int64_t)p->classes * p->out_h * p->out_w <= INT32_MAX);
+    for (int s = 0; s < p->n_maps; ++s) {
+        VCHECK(p->map_h[s] > 0 && p->map_w[s] > 0);
+        if (p->map_h[s] > p->out_h || p->map_w[s] > p->out_w)
+            return fail(VIVIM_ERR_UNSUPPORTED, "decode_head_fwd: map %d is (%d, %d), the output (%d, %d): upsampling only", s, p->map_h[s],
+                        p->map_w[s], p->out_h, p->out_w);
+        VCHECK((int64_t)p->hidden * p->map_h[s] * p->map_w[s] <= INT32_MAX);
+    }
+    for (int s = 0; s < p->n_maps; ++s) VCHECK(p->maps[s] != nullptr && aligned(p->maps[s], ib));
+    VCHECK(p->bias != nullptr && aligned(p->bias, 4));
+    VCHECK(p->w_out != nullptr && aligned(p->w_out, 4));
+    VCHECK(aligned(p->b_out, 4));                                   // NULL: zeros
+    VCHECK(p->logits != nullptr && aligned(p->logits, ib));
+    for (int s = 0; s < p->n_maps; ++s) VCHECK(p->map_batch_stride[s] >= (int64_t)p->hidden * p->map_h[s] * p->map_w[s]);
+    VCHECK(p->logits_batch_stride >= (int64_t)p->classes * p->out_h * p->out_w);
+    VCHECK(vivim::decode_head_blocks(*p) <= INT32_MAX);
+    return VIVIM_OK;
+}
+
+extern "C" int vivim_decode_head_fwd(const vivim_decode_head_params* p, void* stream) {
+    if (int rc = check_decode_head(p)) return rc;
+    return after_dispatch(vivim::decode_head_dispatch(*p, as_stream(stream)), "decode_head_fwd",
+                          "decode_head_fwd not implemented for type %d", p->itype);
+}

@@ -35,7 +35,8 @@ inline int64_t det_numel(const DetOut& o) { return o.size[0] * o.size[1] * o.siz
 // out[i] += sum over s < slots of ws[s * slot_stride + i], s ascending (det.hip); slot_stride 0: numel.
 void det_reduce(const float* ws, int slots, const DetOut& o, hipStream_t stream, int64_t slot_stride = 0);
 
-// What a *_det_dispatch reports to capi.hip, which words the refusal: nothing was launched unless it is `ok`.
+// What a *_det_dispatch reports to its entry point, where after_det_dispatch (capi.cuh) words the refusal: nothing was
+// launched unless it is `ok`.
 enum class Launch { ok, unsupported, bad_workspace };
 // The slot workspace of a call: present, 16-byte aligned and of at least `need` bytes.
 inline bool det_ws_ok(const void* ws, size_t bytes, size_t need) {

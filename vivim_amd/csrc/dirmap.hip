@@ -9,7 +9,7 @@
 // access), direction 2 (frame interleave, token t*hw+p <-> p*nf+t) is element-wise: consecutive flat tokens are
 // nf elements apart there, the lines are shared between neighbouring threads and served by L2.
 // Pure data movement: HBM-bound, algorithmic bytes 4 * batch * channels * seqlen * sizeof(T) either way.
-#include "ops.cuh"
+#include "capi.cuh"
 
 namespace vivim {
 
@@ -139,7 +139,7 @@ __global__ void __launch_bounds__(256) dir_tile_kernel(const vivim_dir_params p)
 }
 
 template <bool GATHER>
-bool dir_dispatch(const vivim_dir_params& p, hipStream_t stream) {
+static bool dir_dispatch(const vivim_dir_params& p, hipStream_t stream) {
     const int E = vec_elems(p.itype);
     const int hw = p.seqlen / p.nframes;
     if (hw % E == 0 && p.nframes <= kDirMaxFrames && p.nframes > 1) {
@@ -151,7 +151,35 @@ bool dir_dispatch(const vivim_dir_params& p, hipStream_t stream) {
     const dim3 grid((p.seqlen / E + 255) / 256, p.channels, p.batch), block(256);
     return with_itype(p.itype, [&](auto t) { hipLaunchKernelGGL((dir_kernel<decltype(t), GATHER>), grid, block, 0, stream, p); });
 }
-template bool dir_dispatch<false>(const vivim_dir_params&, hipStream_t);
-template bool dir_dispatch<true>(const vivim_dir_params&, hipStream_t);
 
 }  // namespace vivim
+
+// ---- the C entry points
+static int check_dir(const vivim_dir_params* p) {
+    VCHECK(p != nullptr);
+    VCHECK(p->itype == VIVIM_F32 || p->itype == VIVIM_F16 || p->itype == VIVIM_BF16);
+    VCHECK(p->batch > 0 && p->channels > 0 && p->seqlen > 0 && p->nframes > 0 && p->csplit > 0);
+    VCHECK(p->batch <= 65535 && p->channels <= 65535);
+    VCHECK(p->seqlen % p->nframes == 0 && p->channels % p->csplit == 0);
+    VCHECK(p->src && p->dst);
+    const int64_t e = vec_elems(p->itype);                      // 16-byte vectors on both sides
+    VCHECK(p->seqlen % e == 0);
+    VCHECK(aligned16(p->src) && aligned16(p->dst));
+    VCHECK(p->flat_batch_stride % e == 0 && p->flat_c_stride % e == 0 && p->stk_batch_stride % e == 0 &&
+           p->stk_half_stride % e == 0 && p->stk_dir_stride % e == 0 && p->stk_c_stride % e == 0);
+    return VIVIM_OK;
+}
+
+extern "C" {
+
+int vivim_dir_scatter(const vivim_dir_params* p, void* stream) {
+    if (int rc = check_dir(p)) return rc;
+    return after_dispatch(vivim::dir_dispatch<false>(*p, as_stream(stream)), "dir_scatter", "dir_scatter: bad itype");
+}
+
+int vivim_dir_gather(const vivim_dir_params* p, void* stream) {
+    if (int rc = check_dir(p)) return rc;
+    return after_dispatch(vivim::dir_dispatch<true>(*p, as_stream(stream)), "dir_gather", "dir_gather: bad itype");
+}
+
+}  // extern "C"

@@ -11,7 +11,7 @@
 // TW = 4 consecutive w positions: every load is a 16-byte vector, 8 neighbouring lanes cover 128 contiguous
 // bytes of one token, each loaded input vector feeds up to 3 of the 4 outputs, taps live in LDS as fp32.
 // Memory-bound: 2*s bytes per element forward (the 27x neighbour re-reads are L1/L2 hits).
-#include "ops.cuh"
+#include "capi.cuh"
 
 namespace vivim {
 
@@ -255,13 +255,13 @@ static void dw_wgrad(const vivim_dwconv_wgrad_params& p, hipStream_t s) {
 }
 
 // vivim_dwconv_wgrad_det: batch * blocks_x slots of (kd * 9 + 1) * channels floats.
-size_t dwconv_wgrad_det_workspace_bytes(const vivim_dwconv_wgrad_params& p) {
+static size_t dwconv_wgrad_det_workspace_bytes(const vivim_dwconv_wgrad_params& p) {
     int tpw = 0;
     const dim3 g = dw_wgrad_grid(p, tpw);
     return sizeof(float) * (size_t)g.x * g.z * (size_t)(p.kd * 9 + 1) * p.channels;
 }
 // The deterministic protocol (det.cuh): the slot workspace is refused before anything is launched.
-Launch dwconv_wgrad_det_dispatch(const vivim_dwconv_wgrad_params& p, void* ws, size_t bytes, hipStream_t s) {
+static Launch dwconv_wgrad_det_dispatch(const vivim_dwconv_wgrad_params& p, void* ws, size_t bytes, hipStream_t s) {
     if (!det_ws_ok(ws, bytes, dwconv_wgrad_det_workspace_bytes(p))) return Launch::bad_workspace;
     vivim_dwconv_wgrad_params d = p;
     d.dwt = ws;
@@ -276,11 +276,69 @@ Launch dwconv_wgrad_det_dispatch(const vivim_dwconv_wgrad_params& p, void* ws, s
     return Launch::ok;
 }
 
-bool dwconv_fwd_dispatch(const vivim_dwconv_params& p, hipStream_t s) {
+static bool dwconv_fwd_dispatch(const vivim_dwconv_params& p, hipStream_t s) {
     return with_itype(p.itype, [&](auto t) { dw_fwd<decltype(t)>(p, s); });
 }
-bool dwconv_wgrad_dispatch(const vivim_dwconv_wgrad_params& p, hipStream_t s) {
+static bool dwconv_wgrad_dispatch(const vivim_dwconv_wgrad_params& p, hipStream_t s) {
     return with_itype(p.itype, [&](auto t) { dw_wgrad<decltype(t), false>(p, s); });
 }
 
 }  // namespace vivim
+
+// ---- the C entry points
+static int check_dw_dims(int batch, int depth, int height, int width, int channels, int kd, int itype) {
+    VCHECK(dtype_ok(itype));
+    VCHECK(batch > 0 && depth > 0 && height > 0 && width > 0 && channels > 0);
+    VCHECK(kd == 1 || kd == 3);
+    VCHECK(batch <= 65535);
+    return VIVIM_OK;
+}
+
+static int check_dw_wgrad(const vivim_dwconv_wgrad_params* p) {
+    VCHECK(p != nullptr);
+    if (int rc = check_dw_dims(p->batch, p->depth, p->height, p->width, p->channels, p->kd, p->itype)) return rc;
+    VCHECK(p->x && p->dy && p->dwt);
+    VCHECK(p->channels % 2 == 0 && p->x_token_stride % 2 == 0 && p->x_batch_stride % 2 == 0 &&
+           p->dy_token_stride % 2 == 0 && p->dy_batch_stride % 2 == 0);
+    VCHECK(aligned(p->x, 8) && aligned(p->dy, 8));
+    return VIVIM_OK;
+}
+
+extern "C" {
+
+int vivim_dwconv_fwd(const vivim_dwconv_params* p, void* stream) {
+    VCHECK(p != nullptr);
+    if (int rc = check_dw_dims(p->batch, p->depth, p->height, p->width, p->channels, p->kd, p->itype)) return rc;
+    VCHECK(p->x && p->wt && p->y);
+    const int64_t cv = vec_elems(p->itype);
+    VCHECK(p->channels % cv == 0 && p->x_token_stride % cv == 0 && p->x_batch_stride % cv == 0 &&
+           p->y_token_stride % cv == 0 && p->y_batch_stride % cv == 0);
+    VCHECK(aligned16(p->x) && aligned16(p->y));
+    VCHECK(p->act >= 0 && p->act <= 2 && (p->act == 0 || p->flip == 0));
+    if (p->act == 2)
+        VCHECK(p->aux && aligned16(p->aux) && p->aux_token_stride % cv == 0 &&
+               p->aux_batch_stride % cv == 0);
+    return after_dispatch(vivim::dwconv_fwd_dispatch(*p, as_stream(stream)), "dwconv_fwd", "dwconv_fwd not implemented for input type %d", p->itype);
+}
+
+size_t vivim_dwconv_wgrad_det_workspace_bytes(const vivim_dwconv_wgrad_params* p) {
+    if (!p || p->batch <= 0 || p->depth <= 0 || p->height <= 0 || p->width <= 0 || p->channels <= 0 || (p->kd != 1 && p->kd != 3))
+        return 0;
+    return vivim::dwconv_wgrad_det_workspace_bytes(*p);
+}
+
+int vivim_dwconv_wgrad_det(const vivim_dwconv_wgrad_params* p, void* det_ws, size_t det_ws_bytes, void* stream) {
+    if (int rc = check_dw_wgrad(p)) return rc;
+    const size_t need = vivim::dwconv_wgrad_det_workspace_bytes(*p);
+    return after_det_dispatch(vivim::dwconv_wgrad_det_dispatch(*p, det_ws, det_ws_bytes, as_stream(stream)), "dwconv_wgrad_det",
+                              "vivim_dwconv_wgrad_det_workspace_bytes", det_ws, det_ws_bytes, need,
+                              "dwconv_wgrad_det not implemented for input type %d", p->itype);
+}
+
+int vivim_dwconv_wgrad(const vivim_dwconv_wgrad_params* p, void* stream) {
+    if (int rc = check_dw_wgrad(p)) return rc;
+    return after_dispatch(vivim::dwconv_wgrad_dispatch(*p, as_stream(stream)), "dwconv_wgrad",
+                          "dwconv_wgrad not implemented for input type %d", p->itype);
+}
+
+}  // extern "C"

@@ -17,7 +17,7 @@
 // the large maps' streaming work overlaps them.
 // Per-map fields are picked with compile-time indices (hc_select): a runtime index into a kernel argument's arrays would go through
 // scratch memory.
-#include "ops.cuh"
+#include "capi.cuh"
 #include "seg_load.cuh"
 #include "up_tap.cuh"
 
@@ -206,8 +206,8 @@ static int64_t hc_units(const vivim_head_concat_params& p, int64_t elem) {
     return units;
 }
 
-// workgroups of the launch (the capi check keeps it within a 31-bit grid)
-int64_t head_concat_blocks(const vivim_head_concat_params& p, bool bwd) {
+// workgroups of the launch (check_head_concat keeps it within a 31-bit grid)
+static int64_t head_concat_blocks(const vivim_head_concat_params& p, bool bwd) {
     const int64_t elem = elem_bytes(p.itype);
     if (!bwd) return (int64_t)p.batch * p.out_h * hc_ceil_div(p.out_w * hc_units(p, elem), kHcThreads);
     int64_t blocks = 0;
@@ -260,8 +260,88 @@ static void hc_launch(const vivim_head_concat_params& p, bool bwd, hipStream_t s
     }
 }
 
-bool head_concat_dispatch(const vivim_head_concat_params& p, bool bwd, hipStream_t stream) {
+static bool head_concat_dispatch(const vivim_head_concat_params& p, bool bwd, hipStream_t stream) {
     return with_itype(p.itype, [&](auto t) { hc_launch<decltype(t)>(p, bwd, stream); });
 }
 
 }  // namespace vivim
+
+// ---- the C entry points
+// every refusal the forward and the backward of the head concat share, before any launch
+static int check_head_concat(const vivim_head_concat_params* p, const char* fn, bool bwd) {
+    if (p == nullptr) return fail(VIVIM_ERR_INVALID, "%s: params is NULL", fn);
+    if (int rc = check_struct_bytes(fn, "vivim_head_concat_params", p->struct_bytes, sizeof(*p))) return rc;
+    if (p->n_maps < 1 || p->n_maps > 4) return fail(VIVIM_ERR_INVALID, "%s: n_maps = %d: one to four maps", fn, p->n_maps);
+    if (!dtype_ok(p->itype)) return fail(VIVIM_ERR_INVALID, "%s: itype = %d: the maps are fp32 / fp16 / bf16 (0 / 1 / 2)", fn, p->itype);
+    if (p->batch <= 0 || p->out_h <= 0 || p->out_w <= 0)
+        return fail(VIVIM_ERR_INVALID, "%s: batch = %d, out_h = %d, out_w = %d: every size must be positive", fn, p->batch, p->out_h, p->out_w);
+    for (int s = 0; s < p->n_maps; ++s)
+        if (p->map_c[s] <= 0 || p->map_h[s] <= 0 || p->map_w[s] <= 0)
+            return fail(VIVIM_ERR_INVALID, "%s: map %d: map_c = %d, map_h = %d, map_w = %d: every size must be positive", fn, s, p->map_c[s],
+                        p->map_h[s], p->map_w[s]);
+    for (int s = 0; s < p->n_maps; ++s)
+        if (p->map_h[s] > p->out_h || p->map_w[s] > p->out_w)
+            return fail(VIVIM_ERR_UNSUPPORTED, "%s: map %d is (%d, %d), the output (%d, %d): upsampling only", fn, s, p->map_h[s], p->map_w[s],
+                        p->out_h, p->out_w);
+    for (int s = 0; s < p->n_maps; ++s) {
+        if (p->chan_off[s] < 0 || (int64_t)p->chan_off[s] + p->map_c[s] > p->out_pixel_stride)
+            return fail(VIVIM_ERR_INVALID, "%s: map %d: channels [%d, %lld) lie outside a pixel of out_pixel_stride = %lld", fn, s, p->chan_off[s],
+                        (long long)p->chan_off[s] + p->map_c[s], (long long)p->out_pixel_stride);
+        for (int t = 0; t < s; ++t)
+            if (p->chan_off[s] < p->chan_off[t] + p->map_c[t] && p->chan_off[t] < p->chan_off[s] + p->map_c[s])
+                return fail(VIVIM_ERR_INVALID, "%s: the channel blocks of maps %d and %d overlap: [%d, %d) and [%d, %d)", fn, t, s, p->chan_off[t],
+                            p->chan_off[t] + p->map_c[t], p->chan_off[s], p->chan_off[s] + p->map_c[s]);
+    }
+    const uintptr_t ib = elem_bytes(p->itype);
+    const void* big = bwd ? p->dout : p->out;
+    if (big == nullptr || !aligned(big, ib))
+        return fail(VIVIM_ERR_INVALID, "%s: %s at %p: need a %d-byte aligned pointer", fn, bwd ? "dout" : "out", big, (int)ib);
+    for (int s = 0; s < p->n_maps; ++s) {
+        const void* q = bwd ? p->dmaps[s] : p->maps[s];
+        if (q == nullptr || !aligned(q, ib))
+            return fail(VIVIM_ERR_INVALID, "%s: %s[%d] at %p: need a %d-byte aligned pointer", fn, bwd ? "dmaps" : "maps", s, q, (int)ib);
+    }
+    for (int s = 0; s < p->n_maps; ++s)
+        if (!(p->scale[s] >= 1.0f) || p->scale[s] > FLT_MAX)                                      // NaN fails the first test
+            return fail(VIVIM_ERR_INVALID, "%s: scale[%d] = %g: 1 / (1 - p) is finite and at least 1", fn, s, (double)p->scale[s]);
+    // a batch holds its images one after the other without overlap
+    const int64_t out_image = (int64_t)p->out_h * p->out_w * p->out_pixel_stride;
+    if (p->out_batch_stride < out_image)
+        return fail(VIVIM_ERR_INVALID, "%s: out_batch_stride = %lld: an image of out has %lld elements", fn, (long long)p->out_batch_stride,
+                    (long long)out_image);
+    for (int s = 0; s < p->n_maps; ++s) {
+        const int64_t image = (int64_t)p->map_c[s] * p->map_h[s] * p->map_w[s], mask = (int64_t)p->map_c[s] * p->out_h * p->out_w;
+        const int64_t have = bwd ? p->dmap_batch_stride[s] : p->map_batch_stride[s];
+        if (have < image)
+            return fail(VIVIM_ERR_INVALID, "%s: %s[%d] = %lld: an image of map %d has %lld elements", fn,
+                        bwd ? "dmap_batch_stride" : "map_batch_stride", s, (long long)have, s, (long long)image);
+        if (p->keep[s] != nullptr && p->keep_batch_stride[s] < mask)
+            return fail(VIVIM_ERR_INVALID, "%s: keep_batch_stride[%d] = %lld: a mask of map %d has %lld bytes", fn, s,
+                        (long long)p->keep_batch_stride[s], s, (long long)mask);
+    }
+    // the kernels index inside an image, and build their windows and their grid, with 32-bit integers
+    // (a row's last workgroup counts up to kHcThreads - 1 positions past its end)
+    bool fits = out_image <= INT32_MAX - vivim::kHcThreads && (int64_t)p->batch * p->out_h <= INT32_MAX;
+    for (int s = 0; s < p->n_maps; ++s)
+        fits = fits && (2 * (int64_t)p->map_h[s] + 3) * p->out_h <= INT32_MAX && (2 * (int64_t)p->map_w[s] + 3) * p->out_w <= INT32_MAX;
+    if (!fits || vivim::head_concat_blocks(*p, bwd) > INT32_MAX)
+        return fail(VIVIM_ERR_INVALID, "%s: batch = %d, out (%d, %d), out_pixel_stride = %lld: the index range overflows int32", fn, p->batch,
+                    p->out_h, p->out_w, (long long)p->out_pixel_stride);
+    return VIVIM_OK;
+}
+
+extern "C" {
+
+int vivim_head_concat_fwd(const vivim_head_concat_params* p, void* stream) {
+    const char* fn = "head_concat_fwd";
+    if (int rc = check_head_concat(p, fn, false)) return rc;
+    return after_dispatch(vivim::head_concat_dispatch(*p, false, as_stream(stream)), fn, "%s not implemented for type %d", fn, p->itype);
+}
+
+int vivim_head_concat_bwd(const vivim_head_concat_params* p, void* stream) {
+    const char* fn = "head_concat_bwd";
+    if (int rc = check_head_concat(p, fn, true)) return rc;
+    return after_dispatch(vivim::head_concat_dispatch(*p, true, as_stream(stream)), fn, "%s not implemented for type %d", fn, p->itype);
+}
+
+}  // extern "C"

@@ -29,7 +29,7 @@
 // and writing dx), then writes the same tile out token-major as dbranch = s[b] * dx.
 // Add-only mode (no weight, NORM = false): the forward stops after x_new, the backward is the scaled transposed copy of dres.
 #include "layernorm.cuh"
-#include "ops.cuh"
+#include "capi.cuh"
 
 namespace vivim {
 
@@ -290,7 +290,7 @@ static int layernorm_tile_tokens(const vivim_add_layernorm_params& p) {
     }
     return 8;
 }
-size_t add_layernorm_bwd_workspace_bytes(const vivim_add_layernorm_params& p) {
+static size_t add_layernorm_bwd_workspace_bytes(const vivim_add_layernorm_params& p) {
     const int TT = layernorm_tile_tokens(p);
     return (size_t)p.batch * ((p.seqlen + TT - 1) / TT) * 2 * p.channels * sizeof(float);
 }
@@ -335,7 +335,7 @@ static bool aln_pair(const vivim_add_layernorm_params& p, bool bwd, hipStream_t 
     return false;
 }
 
-bool add_layernorm_dispatch(const vivim_add_layernorm_params& p, bool bwd, hipStream_t stream) {
+static bool add_layernorm_dispatch(const vivim_add_layernorm_params& p, bool bwd, hipStream_t stream) {
     if (p.channels > kLnMaxC) return false;
     if (p.btype == p.itype) {
         switch (p.itype) {
@@ -365,9 +365,9 @@ static vivim_add_layernorm_params ln_plain(const vivim_layernorm_params& p) {
     q.dy = p.dy; q.dx = p.dx; q.dweight = p.dweight; q.dbias = p.dbias; q.workspace = p.workspace;
     return q;
 }
-size_t layernorm_bwd_workspace_bytes(const vivim_layernorm_params& p) { return add_layernorm_bwd_workspace_bytes(ln_plain(p)); }
+static size_t layernorm_bwd_workspace_bytes(const vivim_layernorm_params& p) { return add_layernorm_bwd_workspace_bytes(ln_plain(p)); }
 
-bool layernorm_dispatch(const vivim_layernorm_params& p, bool bwd, hipStream_t stream) {
+static bool layernorm_dispatch(const vivim_layernorm_params& p, bool bwd, hipStream_t stream) {
     if (p.channels > kLnMaxC) return false;
     const vivim_add_layernorm_params q = ln_plain(p);
     // the output / incoming-gradient side is f32 (what autocast makes of layer_norm) or the input's own type
@@ -387,3 +387,93 @@ bool layernorm_dispatch(const vivim_layernorm_params& p, bool bwd, hipStream_t s
 }
 
 }  // namespace vivim
+
+// ---- the C entry points
+using vivim::kLnMaxC;
+
+static int check_layernorm(const vivim_layernorm_params* p) {
+    VCHECK(p != nullptr);
+    VCHECK(dtype_ok(p->itype) && (p->otype == VIVIM_F32 || p->otype == p->itype));
+    VCHECK(p->batch > 0 && p->seqlen > 0 && p->channels > 0 && p->batch <= 65535);
+    if (p->channels > kLnMaxC)
+        return fail(VIVIM_ERR_UNSUPPORTED, "layernorm_cm: more than %d channels do not fit the backward's two LDS tiles", kLnMaxC);
+    const int64_t e = vec_elems(p->itype);                       // 16-byte vectors along the tokens of x / dx
+    VCHECK(p->seqlen % e == 0 && p->x_batch_stride % e == 0 && p->x_c_stride % e == 0);
+    VCHECK(p->x && aligned16(p->x) && p->mean && p->rstd);
+    return VIVIM_OK;
+}
+
+// what the forward and the backward of the residual-add LayerNorm share; `e` <- elements per 16-byte vector of x / x_new / dres / dx
+static int check_add_layernorm(const vivim_add_layernorm_params* p, int64_t* e) {
+    VCHECK(p != nullptr);
+    VCHECK(dtype_ok(p->itype) && dtype_ok(p->btype) && (p->weight == nullptr || dtype_ok(p->otype)));
+    VCHECK(p->batch > 0 && p->seqlen > 0 && p->channels > 0 && p->batch <= 65535);
+    if (p->channels > kLnMaxC)
+        return fail(VIVIM_ERR_UNSUPPORTED, "add_layernorm_cm: more than %d channels do not fit the backward's two LDS tiles", kLnMaxC);
+    if (p->btype != p->itype && p->itype != VIVIM_F32)
+        return fail(VIVIM_ERR_UNSUPPORTED, "add_layernorm_cm: branch type %d with x type %d is not built (the branch has x's type, or x is f32)",
+                    p->btype, p->itype);
+    if (p->weight && p->otype != VIVIM_F32 && p->otype != p->itype)
+        return fail(VIVIM_ERR_UNSUPPORTED, "add_layernorm_cm: output type %d with x type %d is not built (f32 or x's type)", p->otype, p->itype);
+    *e = vec_elems(p->itype);
+    VCHECK(p->seqlen % *e == 0);
+    return VIVIM_OK;
+}
+
+extern "C" {
+
+int vivim_layernorm_cm_fwd(const vivim_layernorm_params* p, void* stream) {
+    if (int rc = check_layernorm(p)) return rc;
+    VCHECK(p->y != nullptr);
+    return after_dispatch(vivim::layernorm_dispatch(*p, false, as_stream(stream)), "layernorm_cm_fwd",
+                          "layernorm_cm_fwd not implemented for input type %d / output type %d", p->itype, p->otype);
+}
+
+size_t vivim_layernorm_bwd_workspace_bytes(const vivim_layernorm_params* p) {
+    return p && p->batch > 0 && p->seqlen > 0 && p->channels > 0 ? vivim::layernorm_bwd_workspace_bytes(*p) : 0;
+}
+
+int vivim_layernorm_cm_bwd(const vivim_layernorm_params* p, void* stream) {
+    if (int rc = check_layernorm(p)) return rc;
+    VCHECK(p->dy && p->dx && aligned16(p->dx));
+    const int64_t e = vec_elems(p->itype);
+    VCHECK(p->dx_batch_stride % e == 0 && p->dx_c_stride % e == 0);
+    if ((p->dweight || p->dbias) && !p->workspace)
+        return fail(VIVIM_ERR_INVALID, "layernorm_cm_bwd: dweight / dbias need the workspace (vivim_layernorm_bwd_workspace_bytes)");
+    return after_dispatch(vivim::layernorm_dispatch(*p, true, as_stream(stream)), "layernorm_cm_bwd",
+                          "layernorm_cm_bwd not implemented for input type %d / output type %d", p->itype, p->otype);
+}
+
+int vivim_add_layernorm_cm_fwd(const vivim_add_layernorm_params* p, void* stream) {
+    int64_t e = 0;
+    if (int rc = check_add_layernorm(p, &e)) return rc;
+    VCHECK(p->x && p->branch && p->x_new && aligned16(p->x) && aligned16(p->x_new));
+    VCHECK(p->x_batch_stride % e == 0 && p->x_c_stride % e == 0 && p->x_new_batch_stride % e == 0 && p->x_new_c_stride % e == 0);
+    if (p->weight) VCHECK(p->y && p->mean && p->rstd);
+    return after_dispatch(vivim::add_layernorm_dispatch(*p, false, as_stream(stream)), "add_layernorm_cm_fwd",
+                          "add_layernorm_cm_fwd not implemented for x type %d / branch type %d / output type %d", p->itype, p->btype, p->otype);
+}
+
+size_t vivim_add_layernorm_bwd_workspace_bytes(const vivim_add_layernorm_params* p) {
+    return p && p->batch > 0 && p->seqlen > 0 && p->channels > 0 ? vivim::add_layernorm_bwd_workspace_bytes(*p) : 0;
+}
+
+int vivim_add_layernorm_cm_bwd(const vivim_add_layernorm_params* p, void* stream) {
+    int64_t e = 0;
+    if (int rc = check_add_layernorm(p, &e)) return rc;
+    if (p->dres) VCHECK(aligned16(p->dres) && p->dres_batch_stride % e == 0 && p->dres_c_stride % e == 0);
+    if (p->weight) {
+        VCHECK(p->x_new && aligned16(p->x_new) && p->mean && p->rstd && (p->dy || p->dres));
+        VCHECK(p->x_new_batch_stride % e == 0 && p->x_new_c_stride % e == 0);
+        VCHECK(p->dx && aligned16(p->dx) && p->dx_batch_stride % e == 0 && p->dx_c_stride % e == 0);
+        if ((p->dweight || p->dbias) && !p->workspace)
+            return fail(VIVIM_ERR_INVALID,
+                        "add_layernorm_cm_bwd: dweight / dbias need the workspace (vivim_add_layernorm_bwd_workspace_bytes)");
+    } else {
+        VCHECK(p->dres && p->dbranch);                 // add-only: dbranch = scale * dres, dx is dres itself
+    }
+    return after_dispatch(vivim::add_layernorm_dispatch(*p, true, as_stream(stream)), "add_layernorm_cm_bwd",
+                          "add_layernorm_cm_bwd not implemented for x type %d / branch type %d / output type %d", p->itype, p->btype, p->otype);
+}
+
+}  // extern "C"

@@ -25,7 +25,8 @@
 // order and the results are those of the fp32 route fed the widened gradients, bit for bit.  A launch is homogeneous: the
 // caller orders its tables by type and no call straddles two.
 #include <math.h>
-#include "ops.cuh"
+#include <string.h>
+#include "capi.cuh"
 
 namespace vivim {
 
@@ -324,28 +325,28 @@ static OptArgs opt_args(const vivim_opt_step_params& q, const void* masters = nu
     return a;
 }
 
-void opt_grad_stats_launch(const vivim_opt_step_params& q, hipStream_t stream) {
+static void opt_grad_stats_launch(const vivim_opt_step_params& q, hipStream_t stream) {
     hipLaunchKernelGGL(opt_grad_stats_kernel<float>, dim3((unsigned)q.n_blocks), dim3(kOptThreads), 0, stream, opt_args(q));
 }
 
-void opt_adamw_launch(const vivim_opt_step_params& q, hipStream_t stream) {
+static void opt_adamw_launch(const vivim_opt_step_params& q, hipStream_t stream) {
     hipLaunchKernelGGL(opt_adamw_kernel<float>, dim3((unsigned)q.n_blocks), dim3(kOptThreads), 0, stream, opt_args(q));
 }
 
 // dtype: VIVIM_F16 or VIVIM_BF16 (checked by the caller)
-void opt_grad_stats_mw_launch(const vivim_opt_step_params& q, int dtype, hipStream_t stream) {
+static void opt_grad_stats_mw_launch(const vivim_opt_step_params& q, int dtype, hipStream_t stream) {
     const dim3 grid((unsigned)q.n_blocks), block(kOptThreads);
     if (dtype == VIVIM_F16) hipLaunchKernelGGL(opt_grad_stats_kernel<f16_t>, grid, block, 0, stream, opt_args(q));
     else hipLaunchKernelGGL(opt_grad_stats_kernel<bf16_t>, grid, block, 0, stream, opt_args(q));
 }
 
-void opt_adamw_mw_launch(const vivim_opt_step_params& q, const void* masters, int dtype, hipStream_t stream) {
+static void opt_adamw_mw_launch(const vivim_opt_step_params& q, const void* masters, int dtype, hipStream_t stream) {
     const dim3 grid((unsigned)q.n_blocks), block(kOptThreads);
     if (dtype == VIVIM_F16) hipLaunchKernelGGL(opt_adamw_kernel<f16_t>, grid, block, 0, stream, opt_args(q, masters));
     else hipLaunchKernelGGL(opt_adamw_kernel<bf16_t>, grid, block, 0, stream, opt_args(q, masters));
 }
 
-void opt_finalise_launch(const vivim_opt_step_params& q, hipStream_t stream) {
+static void opt_finalise_launch(const vivim_opt_step_params& q, hipStream_t stream) {
     OptFinArgs a;
     a.state = static_cast<uint32_t*>(q.state);
     a.workspace = static_cast<const float*>(q.workspace);
@@ -360,3 +361,116 @@ void opt_finalise_launch(const vivim_opt_step_params& q, hipStream_t stream) {
 }
 
 }  // namespace vivim
+
+// ---- the C entry points
+static int check_opt_common(const vivim_opt_step_params* p, const char* fn) {
+    VCHECK(p != nullptr);
+    if (int rc = check_struct_bytes(fn, "vivim_opt_step_params", p->struct_bytes, sizeof(*p))) return rc;
+    VCHECK(p->state != nullptr && aligned(p->state, 4));
+    if (p->total_blocks < 0) return fail(VIVIM_ERR_INVALID, "%s: total_blocks = %d", fn, p->total_blocks);
+    return VIVIM_OK;
+}
+
+// the tensors and map rows of one multi-tensor call
+static int check_opt_tensors(const vivim_opt_step_params* p, const char* fn, size_t grad_align = 4) {
+    if (p->count <= 0 || p->count > VIVIM_OPT_MAX_TENSORS)
+        return fail(VIVIM_ERR_INVALID, "%s: count = %d, a call takes 1 to %d tensors", fn, p->count, VIVIM_OPT_MAX_TENSORS);
+    VCHECK(p->grads != nullptr && p->numel != nullptr && p->block_map != nullptr);
+    VCHECK(aligned(p->block_map, 4) && p->first_tensor >= 0);
+    for (int i = 0; i < p->count; ++i) {
+        if (p->numel[i] <= 0) return fail(VIVIM_ERR_INVALID, "%s: numel[%d] = %lld", fn, i, (long long)p->numel[i]);
+        VCHECK(aligned(p->grads[i], grad_align));
+    }
+    if (p->first_block < 0 || p->n_blocks <= 0 || (int64_t)p->first_block + p->n_blocks > p->total_blocks)
+        return fail(VIVIM_ERR_INVALID, "%s: map rows %d .. %d + %d of %d", fn, p->first_block, p->first_block, p->n_blocks, p->total_blocks);
+    return VIVIM_OK;
+}
+
+static int check_opt_workspace(const vivim_opt_step_params* p, const char* fn) {
+    const size_t need = 8 * (size_t)p->total_blocks;
+    if (need && (p->workspace == nullptr || !aligned(p->workspace, 8) || p->workspace_bytes < (int64_t)need))
+        return bad_workspace(fn, "vivim_opt_step_workspace_bytes", (long long)p->workspace_bytes, p->workspace, 8, need);
+    return VIVIM_OK;
+}
+
+// the hyper-parameters of a step: the betas, and for the `update` itself lr, eps and weight_decay
+static int check_opt_hyper(const vivim_opt_step_params* p, const char* fn, bool update) {
+    if (!(p->beta1 >= 0.0 && p->beta1 < 1.0 && p->beta2 >= 0.0 && p->beta2 < 1.0))
+        return fail(VIVIM_ERR_INVALID, "%s: betas = (%g, %g), each must be in [0, 1)", fn, p->beta1, p->beta2);
+    if (update && !(p->lr >= 0.0 && p->eps >= 0.0 && p->weight_decay >= 0.0))
+        return fail(VIVIM_ERR_INVALID, "%s: lr = %g, eps = %g, weight_decay = %g: none may be negative", fn, p->lr, p->eps, p->weight_decay);
+    return VIVIM_OK;
+}
+
+// the same step for 16-bit parameters with fp32 masters: vivim_opt_mw_params is vivim_opt_step_params + masters + dtype
+static int check_opt_mw(const vivim_opt_mw_params* p, const char* fn, vivim_opt_step_params& q) {
+    VCHECK(p != nullptr);
+    if (int rc = check_struct_bytes(fn, "vivim_opt_mw_params", p->struct_bytes, sizeof(*p))) return rc;
+    static_assert(offsetof(vivim_opt_mw_params, masters) == sizeof(vivim_opt_step_params), "the common fields come first");
+    memcpy(&q, p, sizeof(q));
+    q.struct_bytes = (int32_t)sizeof(q);
+    if (int rc = check_opt_common(&q, fn)) return rc;
+    if (p->dtype != VIVIM_F16 && p->dtype != VIVIM_BF16)
+        return fail(VIVIM_ERR_INVALID, "%s: dtype = %d, master weights are for 1 (fp16) and 2 (bf16)", fn, p->dtype);
+    return VIVIM_OK;
+}
+
+extern "C" {
+
+size_t vivim_opt_step_workspace_bytes(const vivim_opt_step_params* p) {
+    return p && p->struct_bytes == (int32_t)sizeof(vivim_opt_step_params) && p->total_blocks > 0 ? 8 * (size_t)p->total_blocks : 0;
+}
+
+int vivim_opt_grad_stats(const vivim_opt_step_params* p, void* stream) {
+    const char* fn = "opt_grad_stats";
+    if (int rc = check_opt_common(p, fn)) return rc;
+    if (int rc = check_opt_tensors(p, fn)) return rc;
+    if (int rc = check_opt_workspace(p, fn)) return rc;
+    vivim::opt_grad_stats_launch(*p, as_stream(stream));
+    return after_launch(fn);
+}
+
+int vivim_opt_finalise(const vivim_opt_step_params* p, void* stream) {
+    const char* fn = "opt_finalise";
+    if (int rc = check_opt_common(p, fn)) return rc;
+    if (int rc = check_opt_hyper(p, fn, false)) return rc;
+    if (p->has_max_norm && !(p->max_norm >= 0.0)) return fail(VIVIM_ERR_INVALID, "%s: max_norm = %g", fn, p->max_norm);
+    if (int rc = check_opt_workspace(p, fn)) return rc;
+    vivim::opt_finalise_launch(*p, as_stream(stream));
+    return after_launch(fn);
+}
+
+int vivim_opt_adamw(const vivim_opt_step_params* p, void* stream) {
+    const char* fn = "opt_adamw";
+    if (int rc = check_opt_common(p, fn)) return rc;
+    VCHECK(p->params != nullptr && p->exp_avg != nullptr && p->exp_avg_sq != nullptr);
+    VCHECK(aligned(p->params, 8) && aligned(p->exp_avg, 8) && aligned(p->exp_avg_sq, 8));
+    if (int rc = check_opt_tensors(p, fn)) return rc;
+    if (int rc = check_opt_hyper(p, fn, true)) return rc;
+    vivim::opt_adamw_launch(*p, as_stream(stream));
+    return after_launch(fn);
+}
+
+int vivim_opt_grad_stats_mw(const vivim_opt_mw_params* p, void* stream) {
+    const char* fn = "opt_grad_stats_mw";
+    vivim_opt_step_params q;
+    if (int rc = check_opt_mw(p, fn, q)) return rc;
+    if (int rc = check_opt_tensors(&q, fn, 2)) return rc;
+    if (int rc = check_opt_workspace(&q, fn)) return rc;
+    vivim::opt_grad_stats_mw_launch(q, p->dtype, as_stream(stream));
+    return after_launch(fn);
+}
+
+int vivim_opt_adamw_mw(const vivim_opt_mw_params* p, void* stream) {
+    const char* fn = "opt_adamw_mw";
+    vivim_opt_step_params q;
+    if (int rc = check_opt_mw(p, fn, q)) return rc;
+    VCHECK(q.params != nullptr && q.exp_avg != nullptr && q.exp_avg_sq != nullptr && p->masters != nullptr);
+    VCHECK(aligned(q.params, 8) && aligned(q.exp_avg, 8) && aligned(q.exp_avg_sq, 8) && aligned(p->masters, 8));
+    if (int rc = check_opt_tensors(&q, fn, 2)) return rc;
+    if (int rc = check_opt_hyper(&q, fn, true)) return rc;
+    vivim::opt_adamw_mw_launch(q, p->masters, p->dtype, as_stream(stream));
+    return after_launch(fn);
+}
+
+}  // extern "C"

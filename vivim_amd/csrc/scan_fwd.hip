@@ -407,7 +407,7 @@ void launch_fwd_generic(const vivim_ssm_fwd_params& p, hipStream_t stream, bool 
     const int sets = ((cpg + R - 1) / R) * p.n_groups;
     const dim3 grid((sets + kScanWaves - 1) / kScanWaves, p.batch), block(kScanWaves * kWave);
     const size_t smem = (size_t)kScanWaves * R * p.dstate * sizeof(float);
-    const bool var = p.is_variable_B;   // capi enforces is_variable_B == is_variable_C
+    const bool var = p.is_variable_B;   // check_ssm_fwd (scan_plan.hip) enforces is_variable_B == is_variable_C
     with_itype(p.itype, [&](auto t) {
         typedef decltype(t) T;
         auto launch = [&](auto kernel) { hipLaunchKernelGGL(kernel, grid, block, smem, stream, p); };

@@ -3,7 +3,7 @@
 #include <algorithm>
 #include <atomic>
 #include "scan_plan.cuh"
-#include "ops.cuh"
+#include "capi.cuh"
 
 namespace vivim {
 
@@ -129,8 +129,8 @@ static bool ls_rows(const vivim_ssm_fwd_params& f) {
 // and lanes = states forward kernels; the n-split / generic kernels write one row per kChunk tokens (two per 512-token
 // n-split step) and are only reached for other shapes or when the tuning selector pins them.  A pure function of the
 // shape and of the forward tuning value: forward and backward calls must see the same one.
-int scan_ckpt_len(const vivim_ssm_fwd_params& f) { return ls_rows(f) ? ls_ckpt_len(f) : kChunk; }
-int scan_chunk_len(int) { return kChunk; }
+static int scan_ckpt_len(const vivim_ssm_fwd_params& f) { return ls_rows(f) ? ls_ckpt_len(f) : kChunk; }
+static int scan_chunk_len(int) { return kChunk; }
 
 // Token-axis cut of the lanes = states kernels.  All workgroups of a launch take about the same time, so the launch runs in
 // rounds of the resident workgroups; one workgroup over a whole number of rounds costs a full extra round (the first build
@@ -260,7 +260,7 @@ static FwdPlan plan_scan_fwd(const vivim_ssm_fwd_params& f, bool launch) {
     return q;
 }
 
-size_t scan_fwd_workspace_bytes(const vivim_ssm_fwd_params& f) { return plan_scan_fwd(f, false).ws; }
+static size_t scan_fwd_workspace_bytes(const vivim_ssm_fwd_params& f) { return plan_scan_fwd(f, false).ws; }
 
 // The launches of plan q on p, full or lean; false: no family is built for it.
 static bool launch_fwd_plan(const vivim_ssm_fwd_params& p, const FwdPlan& q, hipStream_t s, bool lean) {
@@ -274,13 +274,13 @@ static bool launch_fwd_plan(const vivim_ssm_fwd_params& p, const FwdPlan& q, hip
     return false;
 }
 
-bool ssm_fwd_dispatch(const vivim_ssm_fwd_params& p, hipStream_t s) { return launch_fwd_plan(p, plan_scan_fwd(p, true), s, false); }
+static bool ssm_fwd_dispatch(const vivim_ssm_fwd_params& p, hipStream_t s) { return launch_fwd_plan(p, plan_scan_fwd(p, true), s, false); }
 
 // The lean forward (vivim_selective_scan_fwd_lean): no checkpoints, no `out` beside `out_z`.  It is planned as the full call
 // on the same tensors would be -- same family, same cut of the token axis, hence the same bits -- with the `out` the full
 // call would have been given: one laid out like delta (what both Python wrappers allocate).  The kernels get `last_state`
 // (null, or fp32 (batch, dim, dstate)) in the place of `x`.
-bool ssm_fwd_lean_dispatch(const vivim_ssm_fwd_params& p, void* last_state, hipStream_t s) {
+static bool ssm_fwd_lean_dispatch(const vivim_ssm_fwd_params& p, void* last_state, hipStream_t s) {
     vivim_ssm_fwd_params f = p;
     if (p.z) {
         f.out = const_cast<void*>(p.delta);          // (planning only: nothing is written through it)
@@ -431,7 +431,7 @@ static BwdPlan plan_scan_bwd(const vivim_ssm_fwd_params& f, const vivim_ssm_bwd_
     return q;
 }
 
-size_t scan_bwd_workspace_bytes(const vivim_ssm_fwd_params& f) { return plan_scan_bwd(f, nullptr).ws; }
+static size_t scan_bwd_workspace_bytes(const vivim_ssm_fwd_params& f) { return plan_scan_bwd(f, nullptr).ws; }
 
 // ---- deterministic backward (vivim_selective_scan_bwd_det; slot scheme in det.cuh) ----
 // Slots per family: dA / dD / dbias one per (batch, segment) -- the generic kernel has no segments; dB / dC one per
@@ -480,7 +480,7 @@ static ScanDetLayout scan_det_layout(const vivim_ssm_fwd_params& f, BwdFamily fa
 
 // The shape level does not know which family the call's pointers allow: the larger of the shape's family (at its
 // segmentation; fewer segments only shrink it) and the generic fallback.
-size_t scan_bwd_det_workspace_bytes(const vivim_ssm_fwd_params& f) {
+static size_t scan_bwd_det_workspace_bytes(const vivim_ssm_fwd_params& f) {
     BwdPlan q = plan_scan_bwd(f, nullptr);
     det_tokens_width(f, nullptr, q);
     const size_t gen = scan_det_layout(f, BwdFamily::generic, 1, 0).bytes;
@@ -490,7 +490,7 @@ size_t scan_bwd_det_workspace_bytes(const vivim_ssm_fwd_params& f) {
 }
 
 // The slots of the family this call's pointers select (never more than the shape-level size above).
-size_t scan_bwd_det_call_workspace_bytes(const vivim_ssm_bwd_params& p) {
+static size_t scan_bwd_det_call_workspace_bytes(const vivim_ssm_bwd_params& p) {
     BwdPlan q = plan_scan_bwd(p.f, &p);
     if (q.family == BwdFamily::none) return 0;
     det_tokens_width(p.f, &p, q);
@@ -498,7 +498,7 @@ size_t scan_bwd_det_call_workspace_bytes(const vivim_ssm_bwd_params& p) {
 }
 
 // The deterministic protocol (det.cuh): a family that is not built and the slot workspace are refused before any launch.
-Launch ssm_bwd_det_dispatch(const vivim_ssm_bwd_params& p, void* det_ws, size_t det_ws_bytes, hipStream_t s) {
+static Launch ssm_bwd_det_dispatch(const vivim_ssm_bwd_params& p, void* det_ws, size_t det_ws_bytes, hipStream_t s) {
     const vivim_ssm_fwd_params& f = p.f;
     BwdPlan q = plan_scan_bwd(f, &p);
     if (q.family == BwdFamily::none) return Launch::unsupported;
@@ -547,7 +547,7 @@ Launch ssm_bwd_det_dispatch(const vivim_ssm_bwd_params& p, void* det_ws, size_t 
     return Launch::ok;
 }
 
-bool ssm_bwd_dispatch(const vivim_ssm_bwd_params& p, hipStream_t s) {
+static bool ssm_bwd_dispatch(const vivim_ssm_bwd_params& p, hipStream_t s) {
     const BwdPlan q = plan_scan_bwd(p.f, &p);
     switch (q.family) {
         case BwdFamily::states: launch_ls_bwd(p, q, s); return true;
@@ -559,3 +559,100 @@ bool ssm_bwd_dispatch(const vivim_ssm_bwd_params& p, hipStream_t s) {
 }
 
 }  // namespace vivim
+
+// ---- the C entry points.  The checks mirror the TORCH_CHECKs of the reference binding that still make sense below the
+// tensor layer (selective_scan.cpp:233-304, 352-438).
+
+// mode: the full forward, the backward (its `f` half), or the lean forward (no checkpoints; out_z alone when z is given)
+enum SsmCheck { kSsmFwd, kSsmBwd, kSsmFwdLean };
+static int check_ssm_fwd(const vivim_ssm_fwd_params* p, SsmCheck mode) {
+    const bool is_bwd = mode == kSsmBwd;
+    VCHECK(p != nullptr);
+    VCHECK(dtype_ok(p->itype));
+    VCHECK(p->batch > 0 && p->dim > 0 && p->seqlen > 0 && p->dstate > 0 && p->n_groups > 0);
+    VCHECK(p->dstate <= 256);                       // selective_scan.cpp:262
+    VCHECK(p->dim % p->n_groups == 0);
+    VCHECK(p->u && p->delta && p->A && p->B && p->C);
+    if (mode == kSsmFwdLean) {
+        if (p->x != nullptr)
+            return fail(VIVIM_ERR_INVALID, "selective_scan_fwd_lean: x must be NULL (this entry point writes no checkpoints; "
+                        "vivim_selective_scan_fwd is the call that fills x)");
+        if (p->z) {
+            VCHECK(p->out_z != nullptr);
+            if (p->out != nullptr)
+                return fail(VIVIM_ERR_INVALID, "selective_scan_fwd_lean: with z only out_z is written, out must be NULL");
+        } else {
+            VCHECK(p->out != nullptr);
+        }
+    } else {
+        VCHECK(p->x != nullptr || (is_bwd && p->seqlen <= vivim::scan_ckpt_len(*p)));
+        if (!is_bwd) VCHECK(p->out != nullptr);
+        if (p->z) {
+            if (!is_bwd) VCHECK(p->out_z != nullptr);
+            else VCHECK(p->out != nullptr);             // selective_scan.cpp:423 (saved out needed for dz)
+        }
+    }
+    if (p->is_variable_B != p->is_variable_C)
+        return fail(VIVIM_ERR_UNSUPPORTED,
+                    "selective_scan: mixed constant/variable B and C is not built (Vivim uses variable B and C)");
+    if (!p->is_variable_B) VCHECK(p->n_groups == 1);
+    return VIVIM_OK;
+}
+
+static int check_ssm_bwd(const vivim_ssm_bwd_params* p) {
+    VCHECK(p != nullptr);
+    if (int rc = check_ssm_fwd(&p->f, kSsmBwd)) return rc;
+    VCHECK(p->dout && p->du && p->ddelta && p->dA && p->dB && p->dC);
+    VCHECK((p->f.D == nullptr) == (p->dD == nullptr));
+    VCHECK((p->f.delta_bias == nullptr) == (p->ddelta_bias == nullptr));
+    VCHECK((p->f.z == nullptr) == (p->dz == nullptr));
+    return VIVIM_OK;
+}
+
+extern "C" {
+
+int vivim_scan_chunk_len(int itype) { return vivim::scan_chunk_len(itype); }
+int vivim_scan_ckpt_len(const vivim_ssm_fwd_params* f) { return f ? vivim::scan_ckpt_len(*f) : 0; }
+size_t vivim_scan_bwd_workspace_bytes(const vivim_ssm_fwd_params* f) {
+    return f ? vivim::scan_bwd_workspace_bytes(*f) : 0;
+}
+size_t vivim_scan_fwd_workspace_bytes(const vivim_ssm_fwd_params* f) {
+    return f ? vivim::scan_fwd_workspace_bytes(*f) : 0;
+}
+
+int vivim_selective_scan_fwd(const vivim_ssm_fwd_params* p, void* stream) {
+    if (int rc = check_ssm_fwd(p, kSsmFwd)) return rc;
+    return after_dispatch(vivim::ssm_fwd_dispatch(*p, as_stream(stream)), "selective_scan_fwd",
+                          "selective_scan_fwd not implemented for input type %d", p->itype);
+}
+
+int vivim_selective_scan_fwd_lean(const vivim_ssm_fwd_params* p, void* last_state, void* stream) {
+    if (int rc = check_ssm_fwd(p, kSsmFwdLean)) return rc;
+    return after_dispatch(vivim::ssm_fwd_lean_dispatch(*p, last_state, as_stream(stream)), "selective_scan_fwd_lean",
+                          "selective_scan_fwd_lean not implemented for input type %d", p->itype);
+}
+
+int vivim_selective_scan_bwd(const vivim_ssm_bwd_params* p, void* stream) {
+    if (int rc = check_ssm_bwd(p)) return rc;
+    return after_dispatch(vivim::ssm_bwd_dispatch(*p, as_stream(stream)), "selective_scan_bwd",
+                          "selective_scan_bwd not implemented for input type %d", p->f.itype);
+}
+
+size_t vivim_scan_bwd_det_workspace_bytes(const vivim_ssm_fwd_params* f) {
+    return f && f->batch > 0 && f->dim > 0 && f->seqlen > 0 && f->dstate > 0 && f->n_groups > 0
+               ? vivim::scan_bwd_det_workspace_bytes(*f) : 0;
+}
+
+size_t vivim_scan_bwd_det_call_workspace_bytes(const vivim_ssm_bwd_params* p) {
+    return check_ssm_bwd(p) == VIVIM_OK ? vivim::scan_bwd_det_call_workspace_bytes(*p) : 0;
+}
+
+int vivim_selective_scan_bwd_det(const vivim_ssm_bwd_params* p, void* det_ws, size_t det_ws_bytes, void* stream) {
+    if (int rc = check_ssm_bwd(p)) return rc;
+    const size_t need = vivim::scan_bwd_det_call_workspace_bytes(*p);
+    return after_det_dispatch(vivim::ssm_bwd_det_dispatch(*p, det_ws, det_ws_bytes, as_stream(stream)), "selective_scan_bwd_det",
+                              "vivim_scan_bwd_det_call_workspace_bytes", det_ws, det_ws_bytes, need,
+                              "selective_scan_bwd_det not implemented for input type %d", p->f.itype);
+}
+
+}  // extern "C"

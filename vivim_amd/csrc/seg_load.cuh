@@ -1,9 +1,11 @@
 // seg_load.cuh -- how the segmentation kernels (seg_loss.hip, seg_metrics.hip) read their inputs: a thread takes E consecutive
 // pixels (16 bytes of logits) of C channel rows plus the labels, in whole vectors where the host-side alignment verdict
-// (sl_aligned16: base pointer and every stride) allows and element by element otherwise.
+// (sl_aligned16: base pointer and every stride) allows and element by element otherwise.  And the argument checks that the
+// entry points of those two files share (check_seg_inputs).
 #pragma once
 #include <initializer_list>
-#include "common.cuh"
+#include <type_traits>
+#include "capi.cuh"
 
 namespace vivim {
 
@@ -69,4 +71,24 @@ static inline bool sl_aligned16(const void* q, int64_t elem_bytes, std::initiali
     return true;
 }
 
+constexpr int kSegMaxClasses = 8;    // the class switches of seg_loss.hip and seg_metrics.hip instantiate 2 .. 8
+
 }  // namespace vivim
+
+// the checks on logits, target and classes that the entry points of the segmentation loss (`name` "seg_loss") and metrics
+// ("seg_metrics") share; the loss's gamma is refused where it always was, between the class count and the grid bound
+template <class P> static int check_seg_inputs(const P* p, const char* name) {
+    VCHECK(p != nullptr);
+    VCHECK(dtype_ok(p->itype) && (p->ttype == 0 || p->ttype == 1));
+    VCHECK(p->batch > 0 && p->pixels > 0);
+    if (p->classes < 2 || p->classes > vivim::kSegMaxClasses)
+        return fail(VIVIM_ERR_UNSUPPORTED, "%s: %d classes: the kernels are built for 2 to %d classes", name, p->classes,
+                    vivim::kSegMaxClasses);
+    if constexpr (std::is_same<P, vivim_seg_loss_params>::value)
+        if (p->gamma != 2.0f)
+            return fail(VIVIM_ERR_UNSUPPORTED, "seg_loss: gamma = %g: the kernels are built for gamma = 2 only", (double)p->gamma);
+    VCHECK((int64_t)p->batch * 64 <= INT32_MAX);                  // one workgroup index per (image, block)
+    VCHECK(p->logits && aligned(p->logits, p->itype == VIVIM_F32 ? 4 : 2));
+    VCHECK(p->target && aligned(p->target, p->ttype == 0 ? 8 : 1));
+    return VIVIM_OK;
+}

@@ -12,8 +12,7 @@
 // slot order, writes the loss and, per (image, class), the two Tversky gradient factors the backward needs.
 // seg_loss_bwd_kernel recomputes the softmax with the same tiling and writes dlogits in the logits' type.
 // Labels are only ever COMPARED with the class index: a label outside [0, C) is a pixel that belongs to no class.
-#include "ops.cuh"
-#include "seg_load.cuh"      // sl_load, sl_labels, sl_aligned16: shared with seg_metrics.hip
+#include "seg_load.cuh"      // sl_load, sl_labels, sl_aligned16, check_seg_inputs: shared with seg_metrics.hip
 
 namespace vivim {
 
@@ -26,7 +25,7 @@ static int sl_blocks_per_image(const vivim_seg_loss_params& p) {
     return (int)(b < kSlMaxBlocks ? b : kSlMaxBlocks);
 }
 
-size_t seg_loss_workspace_bytes(const vivim_seg_loss_params& p) {
+static size_t seg_loss_workspace_bytes(const vivim_seg_loss_params& p) {
     return sizeof(float) * (size_t)p.batch * sl_blocks_per_image(p) * (3 * p.classes + 1);
 }
 
@@ -249,9 +248,45 @@ static bool sl_classes(const vivim_seg_loss_params& p, bool bwd, hipStream_t str
     return false;
 }
 
-bool seg_loss_dispatch(const vivim_seg_loss_params& p, bool bwd, hipStream_t stream) {
+static bool seg_loss_dispatch(const vivim_seg_loss_params& p, bool bwd, hipStream_t stream) {
     bool built = false;                  // false: no kernel for this class count
     return with_itype(p.itype, [&](auto t) { built = sl_classes<decltype(t)>(p, bwd, stream); }) && built;
 }
 
 }  // namespace vivim
+
+// ---- the C entry points
+// what the forward and the backward of the segmentation loss share
+static int check_seg_loss(const vivim_seg_loss_params* p) {
+    if (int rc = check_seg_inputs(p, "seg_loss")) return rc;
+    VCHECK(p->alpha && aligned(p->alpha, 4));
+    return VIVIM_OK;
+}
+
+extern "C" {
+
+size_t vivim_seg_loss_workspace_bytes(const vivim_seg_loss_params* p) {
+    return p && p->batch > 0 && p->pixels > 0 && p->classes > 0 && dtype_ok(p->itype) ? vivim::seg_loss_workspace_bytes(*p) : 0;
+}
+
+int vivim_seg_loss_fwd(const vivim_seg_loss_params* p, void* stream) {
+    if (int rc = check_seg_loss(p)) return rc;
+    VCHECK(p->loss && aligned(p->loss, 4));
+    VCHECK(aligned(p->coef, 4));                                    // NULL: not wanted
+    const size_t need = vivim::seg_loss_workspace_bytes(*p);
+    if (int rc = check_workspace("seg_loss_fwd", "vivim_seg_loss_workspace_bytes", p->workspace, p->workspace_bytes, 4, need)) return rc;
+    return after_dispatch(vivim::seg_loss_dispatch(*p, false, as_stream(stream)), "seg_loss_fwd",
+                          "seg_loss_fwd not implemented for input type %d / %d classes", p->itype, p->classes);
+}
+
+int vivim_seg_loss_bwd(const vivim_seg_loss_params* p, void* stream) {
+    if (int rc = check_seg_loss(p)) return rc;
+    const uintptr_t ib = elem_bytes(p->itype);
+    VCHECK(p->coef && aligned(p->coef, 4));
+    VCHECK(p->grad_out && aligned(p->grad_out, 4));
+    VCHECK(p->dlogits && aligned(p->dlogits, ib));
+    return after_dispatch(vivim::seg_loss_dispatch(*p, true, as_stream(stream)), "seg_loss_bwd",
+                          "seg_loss_bwd not implemented for input type %d / %d classes", p->itype, p->classes);
+}
+
+}  // extern "C"

@@ -13,8 +13,7 @@
 // present in image n (tp + fn > 0) into state[c][0..5] and 1 into state[c][6], in fp64: the state is bit-repeatable.
 // Labels are only ever COMPARED with the class index: a label outside [0, C) is a pixel of no class -- a false positive of the
 // class predicted there and nothing else.
-#include "ops.cuh"
-#include "seg_load.cuh"
+#include "seg_load.cuh"      // sl_load, sl_labels, sl_aligned16, check_seg_inputs: shared with seg_loss.hip
 
 namespace vivim {
 
@@ -27,7 +26,7 @@ static int sm_blocks_per_image(const vivim_seg_metrics_params& p) {
     return (int)(b < kSmMaxBlocks ? b : kSmMaxBlocks);
 }
 
-size_t seg_metrics_workspace_bytes(const vivim_seg_metrics_params& p) {
+static size_t seg_metrics_workspace_bytes(const vivim_seg_metrics_params& p) {
     return sizeof(int32_t) * (size_t)p.batch * sm_blocks_per_image(p) * (3 * p.classes);
 }
 
@@ -196,9 +195,27 @@ static bool sm_classes(const vivim_seg_metrics_params& p, hipStream_t stream) {
     return false;
 }
 
-bool seg_metrics_dispatch(const vivim_seg_metrics_params& p, hipStream_t stream) {
+static bool seg_metrics_dispatch(const vivim_seg_metrics_params& p, hipStream_t stream) {
     bool built = false;                  // false: no kernel for this class count
     return with_itype(p.itype, [&](auto t) { built = sm_classes<decltype(t)>(p, stream); }) && built;
 }
 
 }  // namespace vivim
+
+extern "C" {
+
+size_t vivim_seg_metrics_workspace_bytes(const vivim_seg_metrics_params* p) {
+    return p && p->batch > 0 && p->pixels > 0 && p->classes > 0 && dtype_ok(p->itype) ? vivim::seg_metrics_workspace_bytes(*p) : 0;
+}
+
+int vivim_seg_metrics(const vivim_seg_metrics_params* p, void* stream) {
+    if (int rc = check_seg_inputs(p, "seg_metrics")) return rc;
+    VCHECK(p->counts && aligned(p->counts, 4));
+    VCHECK(aligned(p->state, 8));         // NULL: not wanted (pred: any address)
+    const size_t need = vivim::seg_metrics_workspace_bytes(*p);
+    if (int rc = check_workspace("seg_metrics", "vivim_seg_metrics_workspace_bytes", p->workspace, p->workspace_bytes, 4, need)) return rc;
+    return after_dispatch(vivim::seg_metrics_dispatch(*p, as_stream(stream)), "seg_metrics",
+                          "seg_metrics not implemented for input type %d / %d classes", p->itype, p->classes);
+}
+
+}  // extern "C"

@@ -14,7 +14,7 @@
 // channel and thread, wave_sum, one LDS step across the waves, and the workgroup STORES its 4 * C floats into slot (image, tile)
 // of the workspace -- no atomics, the order of every sum depends on the shape alone.  sl_finalize adds the slots in slot order
 // in fp64.  The backward kernel recomputes k, w and the sigmoid with the same tiling and writes dlogits in the logits' type.
-#include "ops.cuh"
+#include "capi.cuh"
 #include "seg_load.cuh"      // sl_load, sl_labels, sl_aligned16
 
 namespace vivim {
@@ -32,9 +32,9 @@ static int64_t st_tiles_y(const vivim_structure_loss_params& p) {
     const int th = st_tile_rows(p.itype);
     return ((int64_t)p.height + th - 1) / th;
 }
-int64_t structure_loss_tiles(const vivim_structure_loss_params& p) { return st_tiles_x(p) * st_tiles_y(p); }
+static int64_t structure_loss_tiles(const vivim_structure_loss_params& p) { return st_tiles_x(p) * st_tiles_y(p); }
 
-size_t structure_loss_workspace_bytes(const vivim_structure_loss_params& p) {
+static size_t structure_loss_workspace_bytes(const vivim_structure_loss_params& p) {
     return sizeof(float) * 4 * (size_t)p.batch * (size_t)structure_loss_tiles(p) * (size_t)p.classes;
 }
 
@@ -260,8 +260,77 @@ static void st_launch(const vivim_structure_loss_params& p, bool bwd, hipStream_
     hipLaunchKernelGGL((structure_loss_kernel<T, true>), grid, block, 0, stream, p, tiles_x, tiles, flags, inv_nc);
 }
 
-bool structure_loss_dispatch(const vivim_structure_loss_params& p, bool bwd, hipStream_t stream) {
+static bool structure_loss_dispatch(const vivim_structure_loss_params& p, bool bwd, hipStream_t stream) {
     return with_itype(p.itype, [&](auto t) { st_launch<decltype(t)>(p, bwd, stream); });
 }
 
 }  // namespace vivim
+
+// ---- the C entry points
+using vivim::kStMaxC;
+
+static bool structure_loss_sizes_ok(const vivim_structure_loss_params* p) {
+    return p->batch > 0 && p->classes > 0 && p->height > 0 && p->width > 0;
+}
+
+// every refusal the forward and the backward of the structure loss share, before any launch
+static int check_structure_loss(const vivim_structure_loss_params* p, const char* fn) {
+    if (p == nullptr) return fail(VIVIM_ERR_INVALID, "%s: params is NULL", fn);
+    if (int rc = check_struct_bytes(fn, "vivim_structure_loss_params", p->struct_bytes, sizeof(*p))) return rc;
+    if (!dtype_ok(p->itype) || (p->ttype != 0 && p->ttype != 1))
+        return fail(VIVIM_ERR_INVALID, "%s: itype = %d, ttype = %d: logits are fp32 / fp16 / bf16 (0 / 1 / 2), targets int64 / uint8 (0 / 1)",
+                    fn, p->itype, p->ttype);
+    if (!structure_loss_sizes_ok(p))
+        return fail(VIVIM_ERR_INVALID, "%s: batch = %d, classes = %d, height = %d, width = %d: every size must be positive", fn, p->batch,
+                    p->classes, p->height, p->width);
+    if (p->classes > kStMaxC)
+        return fail(VIVIM_ERR_UNSUPPORTED, "%s: %d classes: the kernels are built for 1 to %d classes", fn, p->classes, kStMaxC);
+    if (p->first_class < 0 || p->first_class > 255)
+        return fail(VIVIM_ERR_INVALID, "%s: first_class = %d: labels are compared as values in [0, 256)", fn, p->first_class);
+    // pixel offsets inside a plane, tile origins + halo, and the grid are 32-bit integers
+    if ((int64_t)p->height * p->width > INT32_MAX - 4096 || (int64_t)p->batch * vivim::structure_loss_tiles(*p) > INT32_MAX)
+        return fail(VIVIM_ERR_INVALID, "%s: batch = %d, height = %d, width = %d: the index range overflows int32", fn, p->batch, p->height,
+                    p->width);
+    const uintptr_t ib = elem_bytes(p->itype);
+    if (p->logits == nullptr || !aligned(p->logits, ib))
+        return fail(VIVIM_ERR_INVALID, "%s: logits at %p: need a %d-byte aligned pointer", fn, p->logits, (int)ib);
+    if (p->target == nullptr || !aligned(p->target, p->ttype == 0 ? 8 : 1))
+        return fail(VIVIM_ERR_INVALID, "%s: target at %p: need a %d-byte aligned pointer", fn, p->target, p->ttype == 0 ? 8 : 1);
+    return VIVIM_OK;
+}
+
+extern "C" {
+
+size_t vivim_structure_loss_workspace_bytes(const vivim_structure_loss_params* p) {
+    if (p == nullptr || p->struct_bytes != (int32_t)sizeof(vivim_structure_loss_params) || !structure_loss_sizes_ok(p) ||
+        p->classes > kStMaxC || !dtype_ok(p->itype))
+        return 0;
+    return vivim::structure_loss_workspace_bytes(*p);
+}
+
+int vivim_structure_loss_fwd(const vivim_structure_loss_params* p, void* stream) {
+    const char* fn = "structure_loss_fwd";
+    if (int rc = check_structure_loss(p, fn)) return rc;
+    if (p->loss == nullptr || !aligned(p->loss, 4)) return fail(VIVIM_ERR_INVALID, "%s: loss at %p: need a 4-byte aligned pointer", fn, p->loss);
+    if (!aligned(p->coef, 4))                                          // NULL: not wanted
+        return fail(VIVIM_ERR_INVALID, "%s: coef at %p: need a 4-byte aligned pointer (or NULL)", fn, p->coef);
+    const size_t need = vivim::structure_loss_workspace_bytes(*p);
+    if (int rc = check_workspace(fn, "vivim_structure_loss_workspace_bytes", p->workspace, p->workspace_bytes, 8, need)) return rc;
+    return after_dispatch(vivim::structure_loss_dispatch(*p, false, as_stream(stream)), fn,
+                          "%s not implemented for input type %d", fn, p->itype);
+}
+
+int vivim_structure_loss_bwd(const vivim_structure_loss_params* p, void* stream) {
+    const char* fn = "structure_loss_bwd";
+    if (int rc = check_structure_loss(p, fn)) return rc;
+    const uintptr_t ib = elem_bytes(p->itype);
+    if (p->coef == nullptr || !aligned(p->coef, 4)) return fail(VIVIM_ERR_INVALID, "%s: coef at %p: need a 4-byte aligned pointer", fn, p->coef);
+    if (p->grad_out == nullptr || !aligned(p->grad_out, 4))
+        return fail(VIVIM_ERR_INVALID, "%s: grad_out at %p: need a 4-byte aligned pointer", fn, p->grad_out);
+    if (p->dlogits == nullptr || !aligned(p->dlogits, ib))
+        return fail(VIVIM_ERR_INVALID, "%s: dlogits at %p: need a %d-byte aligned pointer", fn, p->dlogits, (int)ib);
+    return after_dispatch(vivim::structure_loss_dispatch(*p, true, as_stream(stream)), fn,
+                          "%s not implemented for input type %d", fn, p->itype);
+}
+
+}  // extern "C"

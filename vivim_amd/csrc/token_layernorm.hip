@@ -24,13 +24,14 @@
 // entry points run the arithmetic they always ran.  E is then one 16-byte vector of the NARROWER of the two types, so that the
 // wider stream moves in two 16-byte accesses per chunk.
 #include <algorithm>
-#include "ops.cuh"
+#include "capi.cuh"
 
 namespace vivim {
 
 constexpr int kTlnWaves = 4;          // waves per workgroup
 constexpr int kTlnMaxSlots = 1024;    // workgroups of the backward = slots of its workspace
 constexpr int kTlnRedWaves = 16;      // waves of the slot-sum kernel: each adds a contiguous run of slots
+constexpr int kTlnMaxC = 1024;        // channels of a row: 64 lanes x 16 registers (tln_launch), what the entry points refuse beyond
 
 template <int G>
 __device__ __forceinline__ float tln_row_sum(float v) {
@@ -287,10 +288,10 @@ __global__ void __launch_bounds__(kWave * kTlnRedWaves) tln_slot_sum_kernel(cons
 
 
 static int tln_slots(int64_t rows) { return (int)std::min<int64_t>(kTlnMaxSlots, (rows + 3) / 4); }
-size_t token_layernorm_bwd_workspace_bytes(const vivim_token_layernorm_params& p) {
+static size_t token_layernorm_bwd_workspace_bytes(const vivim_token_layernorm_params& p) {
     return (size_t)tln_slots(p.rows) * 2 * p.channels * sizeof(float);
 }
-size_t token_add_norm_bwd_workspace_bytes(const vivim_token_add_norm_params& p) {
+static size_t token_add_norm_bwd_workspace_bytes(const vivim_token_add_norm_params& p) {
     return (size_t)tln_slots(p.rows) * 2 * p.channels * sizeof(float);
 }
 
@@ -340,12 +341,12 @@ static void tln_launch(const TlnArgs& p, bool bwd, bool vec, hipStream_t stream)
     }
 }
 
-bool token_layernorm_pair_ok(int itype, int otype) {
+static bool token_layernorm_pair_ok(int itype, int otype) {
     return otype == itype || otype == VIVIM_F32 || itype == VIVIM_F32;
 }
 
-bool token_layernorm_dispatch(const vivim_token_layernorm_params& p, bool bwd, hipStream_t stream) {
-    if (p.channels < 1 || p.channels > 1024 || !token_layernorm_pair_ok(p.itype, p.otype)) return false;
+static bool token_layernorm_dispatch(const vivim_token_layernorm_params& p, bool bwd, hipStream_t stream) {
+    if (p.channels < 1 || p.channels > kTlnMaxC || !token_layernorm_pair_ok(p.itype, p.otype)) return false;
     TlnArgs a = {};
     a.rows = p.rows, a.channels = p.channels, a.eps = p.eps;
     a.x_row_stride = p.x_row_stride, a.y_row_stride = p.y_row_stride, a.dy_row_stride = p.dy_row_stride, a.dx_row_stride = p.dx_row_stride;
@@ -370,12 +371,12 @@ bool token_layernorm_dispatch(const vivim_token_layernorm_params& p, bool bwd, h
 }
 
 // (branch = y type, residual type): the same, or a 16-bit branch on an f32 residual stream (the autocast case)
-bool token_add_norm_pair_ok(int btype, int rtype) {
+static bool token_add_norm_pair_ok(int btype, int rtype) {
     return rtype == btype || (rtype == VIVIM_F32 && (btype == VIVIM_F16 || btype == VIVIM_BF16));
 }
 
-bool token_add_norm_dispatch(const vivim_token_add_norm_params& p, bool bwd, hipStream_t stream) {
-    if (p.channels < 1 || p.channels > 1024 || !token_add_norm_pair_ok(p.btype, p.rtype) || p.otype != p.btype) return false;
+static bool token_add_norm_dispatch(const vivim_token_add_norm_params& p, bool bwd, hipStream_t stream) {
+    if (p.channels < 1 || p.channels > kTlnMaxC || !token_add_norm_pair_ok(p.btype, p.rtype) || p.otype != p.btype) return false;
     TlnArgs a = {};
     a.rows = p.rows, a.channels = p.channels, a.rows_per_sample = p.rows_per_sample, a.rms = p.rms, a.eps = p.eps;
     a.weight = p.weight, a.bias = p.bias, a.mean = p.mean, a.rstd = p.rstd, a.scale = p.scale;
@@ -413,3 +414,156 @@ bool token_add_norm_dispatch(const vivim_token_add_norm_params& p, bool bwd, hip
 }
 
 }  // namespace vivim
+
+// ---- the C entry points
+using vivim::kTlnMaxC;
+
+// every refusal the forward and the backward of the token-major LayerNorm share, before any launch
+static int check_token_layernorm(const vivim_token_layernorm_params* p, const char* fn) {
+    VCHECK(p != nullptr);
+    if (int rc = check_struct_bytes(fn, "vivim_token_layernorm_params", p->struct_bytes, sizeof(*p))) return rc;
+    VCHECK(dtype_ok(p->itype) && dtype_ok(p->otype));
+    VCHECK(p->rows > 0);
+    if (p->channels < 1)
+        return fail(VIVIM_ERR_INVALID, "%s: channels = %d: a row has at least one channel", fn, p->channels);
+    if (p->channels > kTlnMaxC)
+        return fail(VIVIM_ERR_UNSUPPORTED, "%s: channels = %d: a row of more than %d channels does not fit the lanes' registers", fn,
+                    p->channels, kTlnMaxC);
+    if (!vivim::token_layernorm_pair_ok(p->itype, p->otype))
+        return fail(VIVIM_ERR_UNSUPPORTED, "%s: input type %d with output type %d is not built (the same type, an f32 output, or an f32 input)",
+                    fn, p->itype, p->otype);
+    VCHECK(p->x != nullptr && aligned(p->x, p->itype == VIVIM_F32 ? 4 : 2));
+    VCHECK(p->weight != nullptr && aligned(p->weight, 4));
+    if (p->x_row_stride < p->channels)
+        return fail(VIVIM_ERR_INVALID, "%s: x_row_stride = %lld is less than the %d channels of a row", fn, (long long)p->x_row_stride,
+                    p->channels);
+    return VIVIM_OK;
+}
+
+// every refusal the forward and the backward of the token-major residual add + norm share, before any launch
+static int check_token_add_norm(const vivim_token_add_norm_params* p, const char* fn) {
+    VCHECK(p != nullptr);
+    if (int rc = check_struct_bytes(fn, "vivim_token_add_norm_params", p->struct_bytes, sizeof(*p))) return rc;
+    if (!dtype_ok(p->btype) || !dtype_ok(p->rtype) || !dtype_ok(p->otype))
+        return fail(VIVIM_ERR_INVALID, "%s: btype = %d, rtype = %d, otype = %d: a type tag is 0 (f32), 1 (f16) or 2 (bf16)", fn, p->btype,
+                    p->rtype, p->otype);
+    if (p->rows <= 0) return fail(VIVIM_ERR_INVALID, "%s: rows = %d: at least one row", fn, p->rows);
+    if (p->channels < 1)
+        return fail(VIVIM_ERR_INVALID, "%s: channels = %d: a row has at least one channel", fn, p->channels);
+    if (p->channels > kTlnMaxC)
+        return fail(VIVIM_ERR_UNSUPPORTED, "%s: channels = %d: a row of more than %d channels does not fit the lanes' registers", fn,
+                    p->channels, kTlnMaxC);
+    if (!vivim::token_add_norm_pair_ok(p->btype, p->rtype) || p->otype != p->btype)
+        return fail(VIVIM_ERR_UNSUPPORTED, "%s: branch type %d with residual type %d and output type %d is not built (one type, or an "
+                    "f16 / bf16 branch and output on an f32 residual)", fn, p->btype, p->rtype, p->otype);
+    if (p->rms != 0 && p->rms != 1) return fail(VIVIM_ERR_INVALID, "%s: rms = %d: 0 (LayerNorm) or 1 (RMSNorm)", fn, p->rms);
+    if (p->scale != nullptr && (p->rows_per_sample <= 0 || p->rows % p->rows_per_sample != 0))
+        return fail(VIVIM_ERR_INVALID, "%s: rows_per_sample = %d with scale: it must be positive and divide rows = %d", fn,
+                    p->rows_per_sample, p->rows);
+    return VIVIM_OK;
+}
+
+// one tensor of a call: required or not, element-aligned, a row stride that holds a row
+static int check_tan_tensor(const char* fn, const char* name, const void* q, bool required, int type, int64_t stride, int channels) {
+    if (q == nullptr)
+        return required ? fail(VIVIM_ERR_INVALID, "%s: %s is NULL", fn, name) : VIVIM_OK;
+    if (!aligned(q, elem_bytes(type)))
+        return fail(VIVIM_ERR_INVALID, "%s: %s = %p is not aligned to its element type", fn, name, q);
+    if (stride < channels)
+        return fail(VIVIM_ERR_INVALID, "%s: %s_row_stride = %lld is less than the %d channels of a row", fn, name, (long long)stride, channels);
+    return VIVIM_OK;
+}
+static int check_tan_f32(const char* fn, const char* name, const void* q, bool required) {
+    if (q == nullptr)
+        return required ? fail(VIVIM_ERR_INVALID, "%s: %s is NULL", fn, name) : VIVIM_OK;
+    return aligned(q, 4) ? VIVIM_OK : fail(VIVIM_ERR_INVALID, "%s: %s = %p is not aligned to its element type", fn, name, q);
+}
+
+extern "C" {
+
+int vivim_token_layernorm_fwd(const vivim_token_layernorm_params* p, void* stream) {
+    if (int rc = check_token_layernorm(p, "token_layernorm_fwd")) return rc;
+    VCHECK(p->y != nullptr && aligned(p->y, p->otype == VIVIM_F32 ? 4 : 2));
+    VCHECK(aligned(p->bias, 4));                                     // NULL: zeros
+    VCHECK((p->mean == nullptr) == (p->rstd == nullptr) && aligned(p->mean, 4) && aligned(p->rstd, 4));
+    if (p->y_row_stride < p->channels)
+        return fail(VIVIM_ERR_INVALID, "token_layernorm_fwd: y_row_stride = %lld is less than the %d channels of a row",
+                    (long long)p->y_row_stride, p->channels);
+    return after_dispatch(vivim::token_layernorm_dispatch(*p, false, as_stream(stream)), "token_layernorm_fwd",
+                          "token_layernorm_fwd not implemented for input type %d / output type %d", p->itype, p->otype);
+}
+
+size_t vivim_token_layernorm_bwd_workspace_bytes(const vivim_token_layernorm_params* p) {
+    return p && p->rows > 0 && p->channels > 0 && p->channels <= kTlnMaxC ? vivim::token_layernorm_bwd_workspace_bytes(*p) : 0;
+}
+
+int vivim_token_layernorm_bwd(const vivim_token_layernorm_params* p, void* stream) {
+    if (int rc = check_token_layernorm(p, "token_layernorm_bwd")) return rc;
+    VCHECK(p->dy != nullptr && aligned(p->dy, p->otype == VIVIM_F32 ? 4 : 2));
+    VCHECK(p->dx != nullptr && aligned(p->dx, p->itype == VIVIM_F32 ? 4 : 2));
+    VCHECK(p->mean != nullptr && p->rstd != nullptr && aligned(p->mean, 4) && aligned(p->rstd, 4));
+    VCHECK(aligned(p->dweight, 4) && aligned(p->dbias, 4) && aligned(p->workspace, 4));
+    if (p->dy_row_stride < p->channels || p->dx_row_stride < p->channels)
+        return fail(VIVIM_ERR_INVALID, "token_layernorm_bwd: dy_row_stride = %lld / dx_row_stride = %lld is less than the %d channels of a row",
+                    (long long)p->dy_row_stride, (long long)p->dx_row_stride, p->channels);
+    if ((p->dweight || p->dbias) && !p->workspace)
+        return fail(VIVIM_ERR_INVALID, "token_layernorm_bwd: dweight / dbias need the workspace (vivim_token_layernorm_bwd_workspace_bytes)");
+    return after_dispatch(vivim::token_layernorm_dispatch(*p, true, as_stream(stream)), "token_layernorm_bwd",
+                          "token_layernorm_bwd not implemented for input type %d / output type %d", p->itype, p->otype);
+}
+
+int vivim_token_add_norm_fwd(const vivim_token_add_norm_params* p, void* stream) {
+    const char* fn = "token_add_norm_fwd";
+    if (int rc = check_token_add_norm(p, fn)) return rc;
+    const bool norm = p->weight != nullptr;
+    const int C = p->channels;
+    if (int rc = check_tan_tensor(fn, "branch", p->branch, true, p->btype, p->branch_row_stride, C)) return rc;
+    if (int rc = check_tan_tensor(fn, "res", p->res, false, p->rtype, p->res_row_stride, C)) return rc;
+    // the add alone writes nothing else; a residual that is read is a sum that is stored (the backward reads it)
+    if (int rc = check_tan_tensor(fn, "res_out", p->res_out, !norm || p->res != nullptr, p->rtype, p->res_out_row_stride, C)) return rc;
+    if (int rc = check_tan_f32(fn, "scale", p->scale, false)) return rc;
+    if (norm) {
+        if (int rc = check_tan_tensor(fn, "y", p->y, true, p->otype, p->y_row_stride, C)) return rc;
+        if (int rc = check_tan_f32(fn, "weight", p->weight, true)) return rc;
+        if (int rc = check_tan_f32(fn, "bias", p->bias, false)) return rc;
+        if ((p->mean == nullptr) != (p->rstd == nullptr))
+            return fail(VIVIM_ERR_INVALID, "%s: mean = %p with rstd = %p: both or neither", fn, p->mean, p->rstd);
+        if (int rc = check_tan_f32(fn, "mean", p->mean, false)) return rc;
+        if (int rc = check_tan_f32(fn, "rstd", p->rstd, false)) return rc;
+    }
+    return after_dispatch(vivim::token_add_norm_dispatch(*p, false, as_stream(stream)), fn,
+                          "%s not implemented for branch type %d / residual type %d", fn, p->btype, p->rtype);
+}
+
+size_t vivim_token_add_norm_bwd_workspace_bytes(const vivim_token_add_norm_params* p) {
+    return p && p->rows > 0 && p->channels > 0 && p->channels <= kTlnMaxC ? vivim::token_add_norm_bwd_workspace_bytes(*p) : 0;
+}
+
+int vivim_token_add_norm_bwd(const vivim_token_add_norm_params* p, void* stream) {
+    const char* fn = "token_add_norm_bwd";
+    if (int rc = check_token_add_norm(p, fn)) return rc;
+    const bool norm = p->weight != nullptr;
+    const int C = p->channels;
+    if (p->dy == nullptr && p->dres == nullptr) return fail(VIVIM_ERR_INVALID, "%s: dy and dres are both NULL: nothing to propagate", fn);
+    if (!norm && p->dy != nullptr) return fail(VIVIM_ERR_INVALID, "%s: dy = %p without weight: the add alone has no y", fn, p->dy);
+    if (norm) {
+        if (int rc = check_tan_tensor(fn, "res_out", p->res_out, true, p->rtype, p->res_out_row_stride, C)) return rc;
+        if (int rc = check_tan_f32(fn, "mean", p->mean, true)) return rc;
+        if (int rc = check_tan_f32(fn, "rstd", p->rstd, true)) return rc;
+        if (int rc = check_tan_f32(fn, "weight", p->weight, true)) return rc;
+        if (int rc = check_tan_tensor(fn, "dy", p->dy, false, p->otype, p->dy_row_stride, C)) return rc;
+        if (int rc = check_tan_f32(fn, "dweight", p->dweight, false)) return rc;
+        if (int rc = check_tan_f32(fn, "dbias", p->dbias, false)) return rc;
+        if (int rc = check_tan_f32(fn, "workspace", p->workspace, false)) return rc;
+        if ((p->dweight || p->dbias) && !p->workspace)
+            return fail(VIVIM_ERR_INVALID, "%s: dweight / dbias need the workspace (vivim_token_add_norm_bwd_workspace_bytes)", fn);
+    }
+    if (int rc = check_tan_tensor(fn, "dres", p->dres, false, p->rtype, p->dres_row_stride, C)) return rc;
+    if (int rc = check_tan_tensor(fn, "dres_in", p->dres_in, false, p->rtype, p->dres_in_row_stride, C)) return rc;
+    if (int rc = check_tan_tensor(fn, "dbranch", p->dbranch, false, p->btype, p->dbranch_row_stride, C)) return rc;
+    if (int rc = check_tan_f32(fn, "scale", p->scale, false)) return rc;
+    return after_dispatch(vivim::token_add_norm_dispatch(*p, true, as_stream(stream)), fn,
+                          "%s not implemented for branch type %d / residual type %d", fn, p->btype, p->rtype);
+}
+
+}  // extern "C"

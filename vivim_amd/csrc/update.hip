@@ -3,7 +3,7 @@
 // launches are latency-bound (batch * dim threads), so the only design rule is coalescing: consecutive threads are
 // consecutive channels, a thread's state row (width or dstate elements) is contiguous in the usual layouts, and a
 // wave therefore touches one contiguous block.
-#include "ops.cuh"
+#include "capi.cuh"
 
 namespace vivim {
 
@@ -69,11 +69,35 @@ __global__ void __launch_bounds__(256) state_update_kernel(const vivim_state_upd
     st_any(p.out, (int64_t)b * p.out_batch_stride + (int64_t)d * p.out_d_stride, p.itype, acc);
 }
 
-void conv_update_launch(const vivim_conv_update_params& p, hipStream_t s) {
+static void conv_update_launch(const vivim_conv_update_params& p, hipStream_t s) {
     hipLaunchKernelGGL(conv_update_kernel, dim3((p.dim + 255) / 256, p.batch), dim3(256), 0, s, p);
 }
-void state_update_launch(const vivim_state_update_params& p, hipStream_t s) {
+static void state_update_launch(const vivim_state_update_params& p, hipStream_t s) {
     hipLaunchKernelGGL(state_update_kernel, dim3((p.dim + 255) / 256, p.batch), dim3(256), 0, s, p);
 }
 
 }  // namespace vivim
+
+extern "C" {
+
+int vivim_causal_conv1d_update(const vivim_conv_update_params* p, void* stream) {
+    VCHECK(p != nullptr);
+    VCHECK(dtype_ok(p->itype) && dtype_ok(p->wtype));
+    VCHECK(p->batch > 0 && p->dim > 0 && p->batch <= 65535);
+    if (p->width < 2 || p->width > 4)
+        return fail(VIVIM_ERR_UNSUPPORTED, "causal_conv1d only supports width between 2 and 4");   // causal_conv1d.cpp:295
+    VCHECK(p->x && p->conv_state && p->weight && p->out);
+    vivim::conv_update_launch(*p, as_stream(stream));
+    return after_launch("causal_conv1d_update");
+}
+
+int vivim_selective_state_update(const vivim_state_update_params* p, void* stream) {
+    VCHECK(p != nullptr);
+    VCHECK(dtype_ok(p->itype) && (p->stype == VIVIM_F32 || p->stype == p->itype));
+    VCHECK(p->batch > 0 && p->dim > 0 && p->dstate > 0 && p->batch <= 65535);
+    VCHECK(p->state && p->x && p->dt && p->A && p->B && p->C && p->out);
+    vivim::state_update_launch(*p, as_stream(stream));
+    return after_launch("selective_state_update");
+}
+
+}  // extern "C"

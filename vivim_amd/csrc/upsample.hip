@@ -14,7 +14,7 @@
 // lanes over output columns (coalesced reads of dy) into an fp32 LDS tile of kUpTileH input rows, then a horizontal pass out of
 // LDS -- and walks a column window wider than the tile in chunks, in ascending order.
 // Every grid is one-dimensional (blockIdx.x decoded on the scalar unit), so N * C planes are not bound by the y / z limits.
-#include "ops.cuh"
+#include "capi.cuh"
 #include "seg_load.cuh"
 #include "up_tap.cuh"
 
@@ -162,8 +162,8 @@ static bool up_cl_vec(const vivim_upsample_params& p, bool bwd, int64_t elem) {
     return sl_aligned16(bwd ? p.dx : p.x, elem, {p.x_batch_stride}) && sl_aligned16(bwd ? p.dy : p.y, elem, {p.y_batch_stride});
 }
 
-// workgroups of the launch (the capi check keeps it within a 31-bit grid)
-int64_t upsample_blocks(const vivim_upsample_params& p, bool bwd) {
+// workgroups of the launch (check_upsample keeps it within a 31-bit grid)
+static int64_t upsample_blocks(const vivim_upsample_params& p, bool bwd) {
     if (p.layout == 1) {
         const int64_t elem = elem_bytes(p.itype), E = up_cl_vec(p, bwd, elem) ? 16 / elem : 1;
         const int64_t rows = bwd ? p.in_h : p.out_h, cols = bwd ? p.in_w : p.out_w;
@@ -200,8 +200,46 @@ static void up_launch(const vivim_upsample_params& p, bool bwd, hipStream_t stre
                            (int)up_ceil_div(p.out_w, kUpTileW));
 }
 
-bool upsample_dispatch(const vivim_upsample_params& p, bool bwd, hipStream_t stream) {
+static bool upsample_dispatch(const vivim_upsample_params& p, bool bwd, hipStream_t stream) {
     return with_itype(p.itype, [&](auto t) { up_launch<decltype(t)>(p, bwd, stream); });
 }
 
 }  // namespace vivim
+
+// ---- the C entry points
+// every refusal of the upsampling calls, before any launch
+static int check_upsample(const vivim_upsample_params* p, bool bwd) {
+    VCHECK(p != nullptr);
+    VCHECK(dtype_ok(p->itype) && (p->layout == 0 || p->layout == 1));
+    VCHECK(p->batch > 0 && p->channels > 0 && p->in_h > 0 && p->in_w > 0 && p->out_h > 0 && p->out_w > 0);
+    if (p->out_h < p->in_h || p->out_w < p->in_w)
+        return fail(VIVIM_ERR_UNSUPPORTED, "upsample_bilinear2d: (%d, %d) -> (%d, %d): upsampling only", p->in_h, p->in_w, p->out_h,
+                    p->out_w);
+    const uintptr_t ib = elem_bytes(p->itype);
+    const void* src = bwd ? p->dy : p->x;
+    const void* dst = bwd ? p->dx : p->y;
+    VCHECK(src != nullptr && aligned(src, ib));
+    VCHECK(dst != nullptr && aligned(dst, ib));
+    // the kernels above index inside an image, and build their windows (up_window) and their grid, with 32-bit integers
+    VCHECK((int64_t)p->channels * p->in_h * p->in_w <= INT32_MAX && (int64_t)p->channels * p->out_h * p->out_w <= INT32_MAX);
+    VCHECK((2 * (int64_t)p->in_h + 3) * p->out_h <= INT32_MAX && (2 * (int64_t)p->in_w + 3) * p->out_w <= INT32_MAX);
+    VCHECK((int64_t)p->batch * p->channels <= INT32_MAX && (int64_t)p->batch * p->out_h <= INT32_MAX);
+    VCHECK(vivim::upsample_blocks(*p, bwd) <= INT32_MAX);
+    return VIVIM_OK;
+}
+
+extern "C" {
+
+int vivim_upsample_bilinear2d_fwd(const vivim_upsample_params* p, void* stream) {
+    if (int rc = check_upsample(p, false)) return rc;
+    return after_dispatch(vivim::upsample_dispatch(*p, false, as_stream(stream)), "upsample_bilinear2d_fwd",
+                          "upsample_bilinear2d_fwd not implemented for type %d", p->itype);
+}
+
+int vivim_upsample_bilinear2d_bwd(const vivim_upsample_params* p, void* stream) {
+    if (int rc = check_upsample(p, true)) return rc;
+    return after_dispatch(vivim::upsample_dispatch(*p, true, as_stream(stream)), "upsample_bilinear2d_bwd",
+                          "upsample_bilinear2d_bwd not implemented for type %d", p->itype);
+}
+
+}  // extern "C"

@@ -17,7 +17,7 @@
 // stage-0 products took 166 / 103 us, with sixteen 24 / 22 (profiles/r03_wgrad_sweep.txt; torch.bmm: 74 / 63).  (Adding the four waves of a workgroup up in LDS first
 // was tried: 64 ds_add_f32 per lane cost 20-38 us, more than the global atomics they saved.)  Rows beyond M / N are read from
 // the last valid row and dropped.  HBM-bound by design: both operands once (a again per column tile of b).
-#include "ops.cuh"
+#include "capi.cuh"
 
 namespace vivim {
 
@@ -125,7 +125,7 @@ static void wgrad_launch(const vivim_wgrad_nt_params& p, hipStream_t stream) {
     else hipLaunchKernelGGL((wgrad_nt_kernel<T, 4, 3>), grid, block, 0, stream, p, sps, col_tiles);
 }
 
-bool wgrad_nt_dispatch(const vivim_wgrad_nt_params& p, hipStream_t stream) {
+static bool wgrad_nt_dispatch(const vivim_wgrad_nt_params& p, hipStream_t stream) {
     switch (p.itype) {
         case VIVIM_BF16: wgrad_launch<bf16_t>(p, stream); return true;
         case VIVIM_F16: wgrad_launch<f16_t>(p, stream); return true;
@@ -134,3 +134,16 @@ bool wgrad_nt_dispatch(const vivim_wgrad_nt_params& p, hipStream_t stream) {
 }
 
 }  // namespace vivim
+
+extern "C" int vivim_wgrad_nt(const vivim_wgrad_nt_params* p, void* stream) {
+    VCHECK(p != nullptr);
+    VCHECK(p->groups > 0 && p->groups <= 65535 && p->m > 0 && p->n > 0 && p->k > 0);
+    VCHECK(p->a && p->b && p->out);
+    if (p->itype != VIVIM_F16 && p->itype != VIVIM_BF16)
+        return fail(VIVIM_ERR_UNSUPPORTED, "wgrad_nt takes f16 or bf16 operands (type %d given): f32 products stay on the library GEMM", p->itype);
+    VCHECK(p->k % 8 == 0 && p->a_row_stride % 8 == 0 && p->b_row_stride % 8 == 0 && p->a_group_stride % 8 == 0 &&
+           p->b_group_stride % 8 == 0);
+    VCHECK(aligned16(p->a) && aligned16(p->b));
+    VCHECK((int64_t)((p->m + 63) / 64) * ((p->n + 15) / 16) <= 65535);
+    return after_dispatch(vivim::wgrad_nt_dispatch(*p, as_stream(stream)), "wgrad_nt", "wgrad_nt not implemented for type %d", p->itype);
+}
